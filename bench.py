@@ -7,8 +7,16 @@ default batch is the north_star's: BASELINE config 3, 8nodes.top +
 8nodes-concurrent-snapshots.events x 2^20 instances, each with its own Go delay stream
 (instance i: rand.Seed(REFERENCE_SEED + i)).  Inputs (topology, event program, delay
 schedule) are resident in HBM before timing; the timed region is K launches of the exec
-kernel.  After timing, the batch checksums of the timed path are compared with the CPU
-oracle's values for the same instances (tests/golden/bench_sums.json): "parity".
+kernel.
+
+A plain run does only what the headline figure needs: set up, warm up, time --steps steps,
+and print the line (metric, value, ms_per_step, the batch, its status counts).  --full adds,
+after timing and outside `value`, every secondary measurement and check: the batch checksums
+of the timed path against the CPU oracle's values for the same instances
+(tests/golden/bench_sums.json: "parity"), the fresh-seed first launch, the full-batch
+CollectSnapshot, the replay plan, the roofline figures and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (the inputs
+are a function of the arguments alone, so two builds can be compared array for array).
 
 Multi-GPU: one process per GPU; the fixed 2^20-instance batch is split into disjoint
 instance ranges (rank r: instances [r*I/N, (r+1)*I/N), seeds base + global index), so
@@ -97,12 +105,19 @@ def parse_args(argv=None):
     ap.add_argument("--graph-fifo", type=int, default=0, help="override FIFO slots per channel (c4/c5)")
     ap.add_argument("--instances", type=int, default=0, help="instances in total (default: the config's batch)")
     ap.add_argument("--fifo-slots", type=int, default=0, help="LDS ring slots per channel (0 = automatic)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary measurement and check: parity with the "
+                         "oracle fixtures, the fresh-seed launch, the full-batch collect, the roofline figures "
+                         "and the CPU baseline (the --no-* options below drop single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32/float64, <= 64 MB)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fresh", action="store_true", help="skip the fresh-seed first-launch measurement")
-    ap.add_argument("--no-collect", action="store_true", help="skip the full-batch CollectSnapshot measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-fresh", action="store_true", help="--full: skip the fresh-seed first-launch measurement")
+    ap.add_argument("--no-collect", action="store_true", help="--full: skip the full-batch CollectSnapshot measurement")
     ap.add_argument("--no-parity", action="store_true",
-                    help="graph configs: skip the after-timing parity run (profiler passes that must see one program)")
+                    help="--full, graph configs: skip the after-timing parity run (profiler passes that must see "
+                         "one program)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on GPUs; gloo for rehearsals")
     ap.add_argument("--shared-device", action="store_true",
                     help="every rank on cuda:0 (multi-rank rehearsal on a one-GPU box)")
@@ -112,6 +127,8 @@ def parse_args(argv=None):
     steps, warmup = STEP_DEFAULTS.get(args.config, (20, 3))
     args.steps = steps if args.steps is None else args.steps
     args.warmup = warmup if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     return args
 
 
@@ -245,7 +262,7 @@ def main(argv=None):
     sim.read_topology_file(os.path.join(TEST_DATA, top))
     sim.read_events_file(os.path.join(TEST_DATA, events))
     sim.flush()                      # uploads topology/program/delays, first full run
-    counters = sim.counters(only_ok=False)
+    counters = sim.counters(only_ok=False) if args.full else None
     n_nodes = sim.num_nodes
 
     for _ in range(args.warmup):
@@ -260,7 +277,8 @@ def main(argv=None):
     sim.synchronize()
     t1 = time.perf_counter()
     # The last timed step writes into output planes poisoned just before it (outside the
-    # timed region): the parity checksums below can only come from that timed launch.
+    # timed region): the checksums, --dump-outputs and --full's parity below can only come from
+    # that timed launch.
     sim.poison_outputs()
     sim.synchronize()
     t2 = time.perf_counter()
@@ -272,6 +290,49 @@ def main(argv=None):
 
     # checksums of the LAST timed rerun (the timed path itself), all-reduced over ranks
     sums = sim.checksums()
+    if args.dump_outputs:
+        dump_batch_outputs(sim, args.dump_outputs, rank)
+    t_max, red = cldist.reduce_results(elapsed, sums.tolist(), coll_dev)
+    tot = dict(zip(cl.SUM_NAMES, red))
+    delivered_ok = tot["delivered"]              # packets of OK instances, all ranks
+    per_step = t_max / args.steps
+    value = delivered_ok / per_step
+
+    line = {
+        "metric": "delivered packets/sec (whole node)",
+        "value": value,
+        "unit": "packets/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": per_step * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "int32",
+        "data": "synthetic: reference test_data scenario, per-instance Go math/rand delay streams",
+        "config": {"workload": desc, "instances_total": total, "instances_per_gpu": per_rank,
+                   "parallelism": f"instances sharded over {world} GPU(s)",
+                   "fifo_lds_slots": args.fifo_slots},
+        "packets_per_step": delivered_ok,
+        "status": {"ok": tot["ok"], "fatal": tot["fatal"], "other": tot["other"]},
+        "full": args.full,
+    }
+    if args.full:
+        line.update(batch_full_figures(args, sim, cl, cldist, rank, world, device, coll_dev, seed_base, per_rank,
+                                       total, top, events, tot, counters, n_nodes, k_total_ms, k_launches))
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def batch_full_figures(args, sim, cl, cldist, rank, world, device, coll_dev, seed_base, per_rank, total, top, events,
+                       tot, counters, n_nodes, k_total_ms, k_launches):
+    """--full: the line's secondary entries, measured after the timed steps and outside
+    `value`: parity with the oracle fixture, the fresh-seed launch, the full-batch collect,
+    the replay plan, the roofline figures and the CPU baseline."""
+    import torch
     recorded_ok = sim.counters(only_ok=True)["recorded"]
     collect = collect_all(sim, args) if not args.no_collect else None
     engine = sim.exec_engine()
@@ -282,10 +343,7 @@ def main(argv=None):
     replay = {"slot_map": sim.mapped_replays(), "spill_free": sim.spill_free_replays(),
               "spilled_instances": spilled, "split_slot": split}
     fresh = fresh_run(cl, per_rank, device, seed_base + total, top, events, args) if not args.no_fresh else None
-    t_max, red = cldist.reduce_results(elapsed, sums.tolist() + [recorded_ok], coll_dev)
-    tot = dict(zip(cl.SUM_NAMES, red[:len(cl.SUM_NAMES)]))
-    tot["recorded"] = red[len(cl.SUM_NAMES)]
-    delivered_ok = tot["delivered"]              # packets of OK instances, all ranks
+    tot = dict(tot, recorded=cldist.reduce_results(0.0, [recorded_ok], coll_dev)[1][0])
 
     parity, parity_note = None, "no fixture for this batch"
     if os.path.exists(FIXTURE):
@@ -300,8 +358,6 @@ def main(argv=None):
             parity_note = "tests/golden/bench_sums.json (CPU oracle over every instance)" + \
                 ("" if parity else f"; mismatches {diff}")
 
-    per_step = t_max / args.steps
-    value = delivered_ok / per_step
     alg_rank = b_alg(counters, n_nodes)             # bytes per launch (this rank)
     # whole node: algorithmic bytes of every rank's launch over the slowest rank's average
     # kernel time, against N x the HBM peak
@@ -358,69 +414,111 @@ def main(argv=None):
     peak = HBM_PEAK_GBS * world
     hbm_frac = achieved / peak
 
-    if rank == 0:
-        line = {
-            "metric": "delivered packets/sec (whole node)",
-            "value": value,
-            "unit": "packets/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": per_step * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "int32",
-            "data": "synthetic: reference test_data scenario, per-instance Go math/rand delay streams",
-            "config": {"workload": desc, "instances_total": total, "instances_per_gpu": per_rank,
-                       "parallelism": f"instances sharded over {world} GPU(s)",
-                       "fifo_lds_slots": args.fifo_slots},
-            "packets_per_step": delivered_ok,
-            "parity": parity,
-            "parity_ref": parity_note,
-            "status": {"ok": tot["ok"], "fatal": tot["fatal"], "other": tot["other"]},
-            "checks": {"cut_residual": tot["cut_residual"], "final_residual": tot["final_residual"],
-                       "snapshot_hash": tot["snapshot_hash"], "completed": tot["completed"],
-                       "recorded": tot["recorded"]},
-            "fresh_run": fresh,
-            "collect": collect,
-            "replay": dict(replay, note="value is the replay rate: the timed steps re-run the same "
-                                        "program and delays, launched through the slot map that the "
-                                        "first run's final ticks give (DESIGN.md section 6); fresh_run is "
-                                        "the first launch on new seeds, with no map; split replays run "
-                                        "slots [0, split_slot) on the spill-free kernel and the instances "
-                                        "that spilled in the first run on the spill-capable one, "
-                                        "concurrently (section 5), both inside kernel_ms; replays write "
-                                        "their snapshot records block-major by slot (section 5)",
-                           records_blocked=sim.records_blocked()),
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
-                         "frac": hbm_frac,
-                         "traffic": traffic, "traffic_detail": traffic_detail,
-                         "kernel": ("clsnap_lanes_nospill (instance per lane, hipRTC-specialized to the "
-                                    "topology)" + ((" + clsnap_lanes_spill" if spill_on_lanes else " + cl_exec_kernel")
-                                                   + " on the spilling instances" if split else "")
-                                    if engine == cl.ChandyLamportSim.ENGINE_LANES else "cl_exec_kernel"),
-                         "kernel_ms": avg_kernel_ms, "alg_bytes_per_launch": alg,
-                         "scope": f"whole node: {world} GPU(s), bytes summed over ranks, slowest rank's "
-                                  f"average kernel time, peak {world} x {HBM_PEAK_GBS:g} GB/s",
-                         "valu": valu,
-                         "binding_resource": (
-                             "instruction issue per wave: the instance-per-lane kernel runs 3 waves per SIMD "
-                             "(168 VGPRs, 13 KB of LDS per wave), each wave bound by its own dependent chains, "
-                             "the snapshot-record stores' drain among them (the registers spilled around each "
-                             "tick loop reload through vmcnt, which also counts stores: a no-store ablation runs "
-                             "the replay 22 % faster); neither the B_alg HBM fraction nor the VALU issue "
-                             "fraction is near 1 (DESIGN.md sections 5 and 9)"
-                             if engine == cl.ChandyLamportSim.ENGINE_LANES else
-                             "instruction issue per wave-tick at ~5 resident waves per SIMD (LDS-capped): "
-                             "neither the B_alg HBM fraction nor the VALU issue fraction is near 1; "
-                             "fewer issued instructions (register pressure, compile-time LDS offsets) "
-                             "moved the time, fewer dependent LDS round trips did not; DESIGN.md section 9")},
-            "cpu_baseline": cpu,
-        }
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    return {
+        "parity": parity,
+        "parity_ref": parity_note,
+        "checks": {"cut_residual": tot["cut_residual"], "final_residual": tot["final_residual"],
+                   "snapshot_hash": tot["snapshot_hash"], "completed": tot["completed"],
+                   "recorded": tot["recorded"]},
+        "fresh_run": fresh,
+        "collect": collect,
+        "replay": dict(replay, note="value is the replay rate: the timed steps re-run the same "
+                                    "program and delays, launched through the slot map that the "
+                                    "first run's final ticks give (DESIGN.md section 6); fresh_run is "
+                                    "the first launch on new seeds, with no map; split replays run "
+                                    "slots [0, split_slot) on the spill-free kernel and the instances "
+                                    "that spilled in the first run on the spill-capable one, "
+                                    "concurrently (section 5), both inside kernel_ms; replays write "
+                                    "their snapshot records block-major by slot (section 5)",
+                       records_blocked=sim.records_blocked()),
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
+                     "frac": hbm_frac,
+                     "traffic": traffic, "traffic_detail": traffic_detail,
+                     "kernel": ("clsnap_lanes_nospill (instance per lane, hipRTC-specialized to the "
+                                "topology)" + ((" + clsnap_lanes_spill" if spill_on_lanes else " + cl_exec_kernel")
+                                               + " on the spilling instances" if split else "")
+                                if engine == cl.ChandyLamportSim.ENGINE_LANES else "cl_exec_kernel"),
+                     "kernel_ms": avg_kernel_ms, "alg_bytes_per_launch": alg,
+                     "scope": f"whole node: {world} GPU(s), bytes summed over ranks, slowest rank's "
+                              f"average kernel time, peak {world} x {HBM_PEAK_GBS:g} GB/s",
+                     "valu": valu,
+                     "binding_resource": (
+                         "instruction issue per wave: the instance-per-lane kernel runs 3 waves per SIMD "
+                         "(168 VGPRs, 13 KB of LDS per wave), each wave bound by its own dependent chains, "
+                         "the snapshot-record stores' drain among them (the registers spilled around each "
+                         "tick loop reload through vmcnt, which also counts stores: a no-store ablation runs "
+                         "the replay 22 % faster); neither the B_alg HBM fraction nor the VALU issue "
+                         "fraction is near 1 (DESIGN.md sections 5 and 9)"
+                         if engine == cl.ChandyLamportSim.ENGINE_LANES else
+                         "instruction issue per wave-tick at ~5 resident waves per SIMD (LDS-capped): "
+                         "neither the B_alg HBM fraction nor the VALU issue fraction is near 1; "
+                         "fewer issued instructions (register pressure, compile-time LDS offsets) "
+                         "moved the time, fewer dependent LDS round trips did not; DESIGN.md section 9")},
+        "cpu_baseline": cpu,
+    }
+
+
+DUMP_LIMIT = 64 << 20   # bytes of .npy data one --dump-outputs run may write
+DUMP_SEED = 20241       # places the instance sample of the dump
+
+
+def save_outputs(dirname, arrays, rank):
+    """DIR/<name>.npy (rank 0 of a multi-rank run; rank r > 0 writes DIR/rank<r>_<name>.npy)."""
+    os.makedirs(dirname, exist_ok=True)
+    nbytes = sum(a.nbytes for a in arrays.values())
+    if nbytes > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {nbytes} bytes (limit {DUMP_LIMIT})")
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(dirname, (f"rank{rank}_" if rank else "") + name + ".npy"), a)
+
+
+def dump_batch_outputs(sim, dirname, rank):
+    """--dump-outputs: what a caller reads after the last timed rerun (it wrote into planes
+    poisoned just before it).  Over the whole batch: status, time and the per-instance
+    snapshot hash (uint64 as [hi32, lo32]).  Over a fixed block of instances placed by
+    DUMP_SEED: every snapshot as collect_snapshot_packed returns it, and the final node
+    tokens.  Integers are stored as floats that hold them exactly."""
+    n, nn, ch, ns = sim.n_instances, sim.num_nodes, sim.num_channels, sim.num_snapshots
+    h = sim.instance_hashes()
+    out = {"status": sim.status().astype(np.float32), "time": sim.time().astype(np.float32),
+           "instance_hash": np.stack([(h >> np.uint64(32)).astype(np.float64),
+                                      (h & np.uint64(0xffffffff)).astype(np.float64)], axis=1)}
+    # per sampled instance and snapshot: N tokens, C offsets and a completion flag, and room for
+    # one recorded message per channel, in half of what is left (save_outputs checks the real size)
+    room = (DUMP_LIMIT - sum(a.nbytes for a in out.values())) // 2
+    k = int(min(n, 16384, max(1, room // (max(ns, 1) * (8 * nn + 8 * ch + 4 + 8 * ch)))))
+    lo = int(np.random.default_rng(DUMP_SEED).integers(0, n - k + 1))
+    out["sample_range"] = np.array([lo, lo + k], dtype=np.float64)
+    for sid in range(ns):
+        tok, done, off, msg = sim.collect_snapshot_packed(sid, lo, lo + k)
+        out[f"snap{sid}_tokens"] = tok.astype(np.float64)
+        out[f"snap{sid}_complete"] = done.astype(np.float32)
+        out[f"snap{sid}_offsets"] = off.astype(np.float64)
+        out[f"snap{sid}_messages"] = msg.astype(np.float64)
+    kt = min(k, 2048)
+    out["final_tokens"] = np.array([list(sim.node_tokens(i).values()) for i in range(lo, lo + kt)], dtype=np.float64)
+    save_outputs(dirname, out, rank)
+
+
+def dump_graph_outputs(g, dirname, rank):
+    """--dump-outputs of a graph config: status and time, the final node tokens, every
+    snapshot's completion tick, and the first completed snapshot as collect_arrays returns
+    it (its tokens; offsets and messages over a block of channels placed by DUMP_SEED)."""
+    ns, e = g.num_snapshots, g.num_channels
+    ctick = np.array([g.snapshot_tick(s) for s in range(ns)], dtype=np.float32)
+    out = {"status_time": np.array([g.status(), g.time()], dtype=np.float64),
+           "final_tokens": g.node_tokens_array().astype(np.float64), "snapshot_tick": ctick}
+    done = np.flatnonzero(ctick >= 0)
+    if done.size:
+        tok, off, msg = g.collect_arrays(int(done[0]))
+        k = int(min(e, 1 << 20))
+        lo = int(np.random.default_rng(DUMP_SEED).integers(0, e - k + 1))
+        out["snap_id_channels"] = np.array([done[0], lo, lo + k], dtype=np.float64)
+        out["snap_tokens"] = tok.astype(np.float64)
+        out["snap_offsets"] = off[lo:lo + k + 1].astype(np.float64)
+        out["snap_messages"] = msg[off[lo]:off[lo + k]][:1 << 20].astype(np.float64)
+    save_outputs(dirname, out, rank)
 
 
 def collect_all(sim, args):
@@ -517,7 +615,7 @@ def bench_graph(args, rank, world, local_rank):
     if cfg.get("drain"):
         g.drain()                           # test_common.go:123-137, on the device
     g.flush()                               # allocates, uploads, first full run
-    counters = g.counters()
+    counters = g.counters() if args.full else None
     for _ in range(args.warmup):
         g.rerun()
     g.synchronize()
@@ -540,7 +638,9 @@ def bench_graph(args, rank, world, local_rank):
     (pre_ms, pre_ticks), (drain_ms, drain_ticks) = g.phase_time()   # the last timed run
     sums = g.checksums()
     status = g.status()
-    parity, parity_ref = (None, "skipped (--no-parity)") if args.no_parity else \
+    if args.dump_outputs:
+        dump_graph_outputs(g, args.dump_outputs, rank)
+    parity, parity_ref = (None, "skipped (--no-parity)") if args.no_parity or not args.full else \
         graph_parity(args.config, g, rank, n, steps, device)
     vals = [sums[k] for k in clg.GSUM_NAMES]
     t_max, red = cldist.reduce_results(elapsed, vals, coll_dev)
@@ -548,16 +648,14 @@ def bench_graph(args, rank, world, local_rank):
     per_step = t_max / args.steps
     value = tot["delivered"] / per_step if tot["ok"] == world else 0.0
     avg_run_ms = run_ms / max(runs, 1)
-    alg = b_alg_graph(counters, n)
-    achieved = alg / (avg_run_ms * 1e-3) / 1e9
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_graph(g, cfg, n, steps, snap_steps, snap_nodes, rs, args.cpu_baseline_seconds)
 
     traffic, traffic_detail = None, None
     tr_path = os.path.join(ROOT, "profiles", f"traffic_{args.config}.json")
-    if os.path.exists(tr_path):
+    if args.full and os.path.exists(tr_path):
         with open(tr_path) as f:
             tr = json.load(f)
         if tr.get("nodes") == n and tr.get("steps") == steps and tr.get("drain", False) == bool(cfg.get("drain")):
@@ -585,8 +683,7 @@ def bench_graph(args, rank, world, local_rank):
                        "snapshots": len(snap_steps), "fifo_slots": fifo,
                        "parallelism": f"one replica per GPU, {world} GPU(s)"},
             "packets_per_step": tot["delivered"],
-            "parity": parity,
-            "parity_ref": parity_ref,
+            "full": args.full,
             "phases": {"traffic": {"ticks": pre_ticks, "ms": pre_ms,
                                    "us_per_tick": 1e3 * pre_ms / max(pre_ticks, 1)},
                        "drain": {"ticks": drain_ticks, "ms": drain_ms,
@@ -595,12 +692,19 @@ def bench_graph(args, rank, world, local_rank):
             "status": {"ok_replicas": tot["ok"], "replicas": world, "rank0_status": status},
             "checks": {"completed": tot["completed"], "cut_residual": tot["cut_residual"],
                        "final_residual": tot["final_residual"], "digest": tot["digest"]},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_detail": traffic_detail,
-                         "kernel": "graph tick pipeline (k_hostops, k_pick, k_marker, k_scan, k_push)",
-                         "kernel_ms": avg_run_ms, "alg_bytes_per_launch": alg},
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            alg = b_alg_graph(counters, n)
+            achieved = alg / (avg_run_ms * 1e-3) / 1e9
+            line.update({
+                "parity": parity,
+                "parity_ref": parity_ref,
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_detail": traffic_detail,
+                             "kernel": "graph tick pipeline (k_hostops, k_pick, k_marker, k_scan, k_push)",
+                             "kernel_ms": avg_run_ms, "alg_bytes_per_launch": alg},
+                "cpu_baseline": cpu,
+            })
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -77,7 +77,7 @@ def test_two_rank_bench_by_hand_shared_device():
     """The whole bench with two ranks on the box's one GPU (gloo collective): the line is the
     2-GPU line of the 2^20 batch, and its parity holds against the oracle fixture."""
     r = subprocess.run([sys.executable, "-u", BENCH, "--gpus", "2", "--shared-device", "--dist-backend", "gloo",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-collect", "--no-fresh"],
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-collect", "--no-fresh"],
                        env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

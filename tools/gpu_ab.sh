@@ -33,19 +33,19 @@ for s in ${STEPS:-launch exec graph abx abg}; do
            if [ $v = base ]; then VAR=""; else VAR=$v; fi
            for c in ${CFGS:-c3 c2}; do
              CLSNAP_VARIANT=$VAR timeout -k 10 200 python -u bench.py --config $c --steps 50 --warmup 5 \
-               --no-cpu-baseline --no-collect ${EXTRA} > $O/abx_${v}_${c}_$r.log 2>&1
+               --full --no-cpu-baseline --no-collect ${EXTRA} > $O/abx_${v}_${c}_$r.log 2>&1
            done; done; done ;;
     abk) for r in 1 2; do for kv in ${KNOBS}; do
            k=${kv%%:*}; envs=${kv#*:}
            for c in ${CFGS:-c3}; do
              env CLSNAP_VARIANT=dbg ${envs//,/ } timeout -k 10 200 python -u bench.py --config $c --steps 50 --warmup 5 \
-               --no-cpu-baseline --no-collect ${EXTRA} > $O/abk_${k}_${c}_$r.log 2>&1
+               --full --no-cpu-baseline --no-collect ${EXTRA} > $O/abk_${k}_${c}_$r.log 2>&1
            done; done; done ;;
     abg) for r in 1 2; do for v in base ${GVARIANTS}; do
            if [ $v = base ]; then VAR=""; else VAR=$v; fi
            for c in ${GCFGS:-c4 c5}; do
              CLSNAP_VARIANT=$VAR timeout -k 10 300 python -u bench.py --config $c --steps 3 --warmup 1 \
-               --no-cpu-baseline > $O/abg_${v}_${c}_$r.log 2>&1
+               --full --no-cpu-baseline > $O/abg_${v}_${c}_$r.log 2>&1
            done; done; done ;;
     tprof) for v in base ${GVARIANTS}; do  # per-dispatch tick kernel durations (tools/tick_profile.py)
              if [ $v = base ]; then VAR=""; else VAR=$v; fi

@@ -21,20 +21,20 @@ if [ "${PART:-bench}" = c5traffic ]; then
   PMCG_DIR=/tmp/pmcg_c5 OUT_DIR=$O/profiles python3 tools/graph_traffic.py c5 100000 4100 drain > $O/traffic_c5.log
 elif [ "${PART:-bench}" = graph ]; then
   # the graph configs again after a graph-engine change: bench lines, kernel stats, C4 traffic
-  timeout -k 10 300 python -u bench.py --config c4 --steps 10 --warmup 2 > $O/bench_c4.json 2> $O/bench_c4.err
-  timeout -k 10 300 python -u bench.py --config c5 --steps 1 --warmup 1 > $O/bench_c5.json 2> $O/bench_c5.err
+  timeout -k 10 300 python -u bench.py --full --config c4 --steps 10 --warmup 2 > $O/bench_c4.json 2> $O/bench_c4.err
+  timeout -k 10 300 python -u bench.py --full --config c5 --steps 1 --warmup 1 > $O/bench_c5.json 2> $O/bench_c5.err
   CFG=c4 ARGS="--steps 3 --warmup 1" bash tools/gpu_prof_graph.sh
   CFG=c5 ARGS="--steps 1 --warmup 1" bash tools/gpu_prof_graph.sh
   PMCG_ROOT=/tmp CFG=c4 bash tools/gpu_pmc_graph.sh
   PMCG_DIR=/tmp/pmcg_c4 OUT_DIR=$O/profiles python3 tools/graph_traffic.py c4 1048576 80 > $O/traffic_c4.log
 elif [ "${PART:-bench}" = bench ]; then
-  timeout -k 10 300 python -u bench.py > $O/bench_c3.json 2> $O/bench_c3.err
-  timeout -k 10 300 python -u bench.py --instances 131072 --no-cpu-baseline > $O/bench_c3_s17.json 2> $O/bench_c3_s17.err
-  timeout -k 10 300 python -u bench.py --config c2 --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err
-  timeout -k 10 300 python -u bench.py --config c4 --steps 10 --warmup 2 > $O/bench_c4.json 2> $O/bench_c4.err
-  timeout -k 10 300 python -u bench.py --config c5 --steps 1 --warmup 1 > $O/bench_c5.json 2> $O/bench_c5.err
+  timeout -k 10 300 python -u bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err
+  timeout -k 10 300 python -u bench.py --full --instances 131072 --no-cpu-baseline > $O/bench_c3_s17.json 2> $O/bench_c3_s17.err
+  timeout -k 10 300 python -u bench.py --full --config c2 --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err
+  timeout -k 10 300 python -u bench.py --full --config c4 --steps 10 --warmup 2 > $O/bench_c4.json 2> $O/bench_c4.err
+  timeout -k 10 300 python -u bench.py --full --config c5 --steps 1 --warmup 1 > $O/bench_c5.json 2> $O/bench_c5.err
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=2 --master-addr=127.0.0.1 --master-port=29533 \
-    bench.py --gpus 2 --steps 5 --warmup 1 --no-cpu-baseline --dist-backend gloo --shared-device > $O/dist2_rehearsal.json 2> $O/dist2_rehearsal.err
+    bench.py --full --gpus 2 --steps 5 --warmup 1 --no-cpu-baseline --dist-backend gloo --shared-device > $O/dist2_rehearsal.json 2> $O/dist2_rehearsal.err
 else
   CFG=c3 bash tools/gpu_pmc.sh
   CFG=c3 SUFFIX=_s17 EXTRA="--instances 131072" bash tools/gpu_pmc.sh

@@ -4,6 +4,7 @@ file exists at bench time -- for lines measured in the same GPU call as the PMC 
 produced the summary.
 
 usage: python tools/refresh_bench_line.py <bench.json> <cfg> > profiles/<round>_bench_<cfg>.json
+(<bench.json>: the line of a `bench.py --full` run; a plain run's line has no roofline)
 """
 import json
 import os

@@ -1,3 +1,4 @@
+"""One summary row per bench line file (lines of `bench.py --full` runs: roofline, checks)."""
 import json
 import sys
 for f in sys.argv[1:]:
