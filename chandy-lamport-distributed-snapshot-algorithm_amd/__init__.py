@@ -18,7 +18,7 @@ import os
 
 import numpy as np
 
-__all__ = ["ChandyLamportSim", "GlobalSnapshot", "MsgSnapshot", "PassTokenEvent", "SnapshotEvent",
+__all__ = ["ChandyLamportSim", "SnapshotStats", "STATS_LAYOUT_FIELDS", "GlobalSnapshot", "MsgSnapshot", "PassTokenEvent", "SnapshotEvent",
            "ClSnapError", "lib", "go_delay_schedule", "go_int63", "go_intn", "REFERENCE_SEED",
            "INST_OK", "INST_FATAL_INSUFFICIENT_TOKENS", "INST_FATAL_UNKNOWN_DEST",
            "INST_FIFO_OVERFLOW", "INST_HANG", "INST_DELAY_EXHAUSTED", "COUNTER_NAMES",
@@ -122,6 +122,9 @@ def lib():
         "cl_exec_engine": [vp, vp],
         "cl_jit_stats": [vp, vp],
         "cl_lanes_compile_check": [vp, vp, vp, i64],
+        "cl_stats_layout_of": [vp, vp, vp],
+        "cl_snapshot_stats": [vp, i32, i64, i64, vp, vp, i64],
+        "cl_stats_time": [vp, vp],
     }
     for name, args in sig.items():
         if os.environ.get("CLSNAP_VARIANT") and not hasattr(L, name):
@@ -226,6 +229,99 @@ class MsgSnapshot:  # common.go:20-24
 class GlobalSnapshot:  # common.go:13-17
     def __init__(self, sid, token_map, messages):
         self.id, self.tokenMap, self.messages = sid, token_map, messages
+
+
+# cl_stats_layout (include/clsnap.h), field by field: int64 word offsets into the flat result
+STATS_LAYOUT_FIELDS = (
+    "n_nodes", "n_channels", "tick_lo", "tick_bins", "msg_bins",
+    "total_words", "sum_begin", "sum_end", "min_begin", "min_end", "max_begin", "max_end",
+    "instances", "ok", "sample", "tick_sum", "tick_sumsq", "tick_hist", "msgs_sum", "msgs_sumsq",
+    "inflight_sum", "inflight_sumsq", "node_sum", "node_sumsq", "ch_msgs_sum", "ch_msgs_sumsq",
+    "ch_tok_sum", "ch_tok_sumsq", "ch_msg_hist",
+    "min_tick", "min_msgs", "min_inflight", "min_node", "min_ch_msgs", "min_ch_tok",
+    "max_tick", "max_msgs", "max_inflight", "max_node", "max_ch_msgs", "max_ch_tok")
+STATS_INT64_MAX, STATS_INT64_MIN = np.iinfo(np.int64).max, np.iinfo(np.int64).min
+
+
+class SnapshotStats:
+    """The result of ``ChandyLamportSim.snapshot_stats``: named numpy views over the flat int64
+    array ``raw`` (cl_snapshot_stats, include/clsnap.h).
+
+    ``layout`` maps the cl_stats_layout field names to word offsets.  Scalars (``instances``,
+    ``ok``, ``sample``, ``tick_sum``, ``min_tick``, ...) read as ints; ``tick_hist[tick_bins]``,
+    ``node_sum[N]``, ``ch_msgs_sum[C]``, ``ch_msg_hist[C, msg_bins]``, ``min_node[N]``, ... are
+    views.  The sums of squares are modulo 2**64."""
+
+    MOMENT_FIELDS = ("tick", "msgs", "inflight", "node", "ch_msgs", "ch_tok")
+
+    def __init__(self, layout, raw):
+        self.layout = dict(layout)
+        self.raw = np.ascontiguousarray(raw, dtype=np.int64)
+        L = self.layout
+        if self.raw.shape != (L["total_words"],):
+            raise ValueError(f"SnapshotStats: raw must hold {L['total_words']} int64 words")
+        n, c, t, m = L["n_nodes"], L["n_channels"], L["tick_bins"], L["msg_bins"]
+        shapes = {"tick_hist": (t,), "node_sum": (n,), "node_sumsq": (n,), "ch_msg_hist": (c, m)}
+        for k in ("ch_msgs_sum", "ch_msgs_sumsq", "ch_tok_sum", "ch_tok_sumsq"):
+            shapes[k] = (c,)
+        for p in ("min_", "max_"):
+            shapes[p + "node"] = (n,)
+            shapes[p + "ch_msgs"] = shapes[p + "ch_tok"] = (c,)
+        self._shapes = shapes
+
+    def __getattr__(self, name):
+        L = self.__dict__.get("layout")
+        if L is None or name not in STATS_LAYOUT_FIELDS[12:]:
+            raise AttributeError(name)
+        shape = self._shapes.get(name)
+        if shape is None:
+            return int(self.raw[L[name]])
+        size = int(np.prod(shape))
+        return self.raw[L[name]:L[name] + size].reshape(shape)
+
+    def _moments(self, field):
+        if field not in self.MOMENT_FIELDS:
+            raise ValueError(f"SnapshotStats: field must be one of {self.MOMENT_FIELDS}")
+        s = np.atleast_1d(getattr(self, field + "_sum"))
+        q = np.atleast_1d(getattr(self, field + "_sumsq"))
+        return [int(x) for x in s.ravel()], [int(x) & (2**64 - 1) for x in q.ravel()], field in self.MOMENT_FIELDS[:3]
+
+    def mean(self, field):
+        """Mean over the sample of "tick", "msgs", "inflight" (floats) or "node", "ch_msgs",
+        "ch_tok" (float arrays); nan on an empty sample."""
+        s, _, scalar = self._moments(field)
+        n = self.sample
+        out = np.array([x / n if n else np.nan for x in s], dtype=np.float64)
+        return float(out[0]) if scalar else out
+
+    def variance(self, field):
+        """Population variance over the sample, from the exact integer moments (valid while the
+        true sum of squares is below 2**64); nan on an empty sample."""
+        s, q, scalar = self._moments(field)
+        n = self.sample
+        out = np.array([(n * b - a * a) / (n * n) if n else np.nan for a, b in zip(s, q)], dtype=np.float64)
+        return float(out[0]) if scalar else out
+
+    def merge(self, other):
+        """The statistics of the union of two disjoint samples (other ranks, other instance
+        ranges): SUM, MIN and MAX over the three sections.  Raises ValueError when the layouts differ."""
+        if not isinstance(other, SnapshotStats) or other.layout != self.layout:
+            raise ValueError("SnapshotStats.merge: the layouts differ")
+        L = self.layout
+        raw = np.empty_like(self.raw)
+        a, b = L["sum_begin"], L["sum_end"]
+        raw[a:b] = (self.raw[a:b].view(np.uint64) + other.raw[a:b].view(np.uint64)).view(np.int64)  # wraps
+        a, b = L["min_begin"], L["min_end"]
+        raw[a:b] = np.minimum(self.raw[a:b], other.raw[a:b])
+        a, b = L["max_begin"], L["max_end"]
+        raw[a:b] = np.maximum(self.raw[a:b], other.raw[a:b])
+        return SnapshotStats(L, raw)
+
+    def __eq__(self, other):
+        return (isinstance(other, SnapshotStats) and other.layout == self.layout
+                and bool(np.array_equal(other.raw, self.raw)))
+
+    __hash__ = None
 
 
 class ChandyLamportSim:
@@ -380,6 +476,31 @@ class ChandyLamportSim:
         _check(self._L.cl_collect_time(self._h, C.byref(ms)))
         return ms.value
 
+    def stats_layout(self, tick_lo=0, tick_bins=256, msg_bins=16):
+        """cl_stats_layout_of as a dict (STATS_LAYOUT_FIELDS): host only, no device."""
+        spec = np.array([tick_lo, tick_bins, msg_bins], dtype=np.int32)
+        out = np.zeros(len(STATS_LAYOUT_FIELDS), dtype=np.int64)
+        _check(self._L.cl_stats_layout_of(self._h, _p(spec), _p(out)))
+        return dict(zip(STATS_LAYOUT_FIELDS, out.tolist()))
+
+    def snapshot_stats(self, snapshot_id, inst_lo=0, inst_hi=None, tick_lo=0, tick_bins=256, msg_bins=16):
+        """Distribution of snapshot `snapshot_id` over the OK instances of [inst_lo, inst_hi) in
+        which it completed, reduced on the GPU (cl_snapshot_stats): a SnapshotStats with count,
+        sum, sum of squares, min, max and histograms of the completion tick, each node's
+        tokenMap entry, each channel's recorded messages and tokens, and the per-instance totals."""
+        hi = self.n_instances if inst_hi is None else inst_hi
+        layout = self.stats_layout(tick_lo, tick_bins, msg_bins)
+        spec = np.array([tick_lo, tick_bins, msg_bins], dtype=np.int32)
+        raw = np.zeros(layout["total_words"], dtype=np.int64)
+        _check(self._L.cl_snapshot_stats(self._h, snapshot_id, inst_lo, hi, _p(spec), _p(raw), raw.size))
+        return SnapshotStats(layout, raw)
+
+    def stats_time(self):
+        """Device ms of the latest snapshot_stats kernel(s)."""
+        ms = C.c_double(0)
+        _check(self._L.cl_stats_time(self._h, C.byref(ms)))
+        return ms.value
+
     # ---- drivers (test_common.go) -------------------------------------------
     def read_topology_file(self, path):           # test_common.go:29
         _check(self._L.cl_read_topology_file(self._h, path.encode()))
@@ -452,8 +573,9 @@ class ChandyLamportSim:
         return bool(v.value)
 
     def records_blocked(self):
-        """True when the device's snapshot records are block-major by replay slot (the latest
-        launch from the initial state replayed through the slot map on the lanes kernels)."""
+        """True when the device's snapshot records are block-major by replay slot: the latest
+        launch from the initial state was a replay through the slot map that saved no state
+        image (rerun() of a mapped plan), on either exec kernel."""
         v = C.c_int32(0)
         _check(self._L.cl_records_blocked(self._h, C.byref(v)))
         return bool(v.value)

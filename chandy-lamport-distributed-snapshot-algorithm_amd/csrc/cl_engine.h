@@ -294,8 +294,12 @@ inline size_t rec_word(int64_t stride, int32_t n_nodes, int32_t rw, int32_t sid,
                        const int32_t* rec_slot, int32_t idx) {
   if (!rec_slot) return ((size_t)sid * (size_t)stride + (size_t)inst) * (size_t)n_nodes * (size_t)rw + (size_t)idx;
   const size_t r = (size_t)rec_slot[inst];
+  // node v = idx / rw, word w = idx % rw of its record: v * 64 * rw + (r & 63) * rw + w, what the
+  // writers store (cl_kernels.hip nod_lane).  rw is a power of two for the unrolled degree
+  // bounds only (rec_words): 1 + in-degree otherwise, e.g. 3
+  const size_t v = (rw & (rw - 1)) == 0 ? (size_t)(idx & ~(rw - 1)) : (size_t)(idx / rw) * (size_t)rw;
   return (((size_t)sid * (size_t)stride + (r & ~(size_t)63)) * (size_t)n_nodes + (size_t)(r & 63)) * (size_t)rw +
-         (size_t)(idx & ~(rw - 1)) * 64 + (size_t)(idx & (rw - 1));
+         v * 64 + ((size_t)idx - v);
 }
 
 struct SumParams {
@@ -389,6 +393,122 @@ int launch_pack_fill(const PackParams& p, void* stream);
 // Recorded message copies (node.go:179-183) over every instance's completed snapshots:
 // out[0] all instances, out[1] status-OK instances.
 int launch_recorded(const SumParams& p, void* stream);
+
+// ---- per-snapshot batch statistics (cl_stats.hip; include/clsnap.h cl_snapshot_stats) ----------
+// Offsets, in int64 words, of every field of the flat result: mirrors cl_stats_layout field by
+// field (cl_host.cpp asserts the sizes agree).
+struct StatsLayout {
+  int64_t n_nodes, n_channels, tick_lo, tick_bins, msg_bins;
+  int64_t total_words, sum_begin, sum_end, min_begin, min_end, max_begin, max_end;
+  int64_t instances, ok, sample, tick_sum, tick_sumsq, tick_hist, msgs_sum, msgs_sumsq, inflight_sum,
+      inflight_sumsq, node_sum, node_sumsq, ch_msgs_sum, ch_msgs_sumsq, ch_tok_sum, ch_tok_sumsq, ch_msg_hist;
+  int64_t min_tick, min_msgs, min_inflight, min_node, min_ch_msgs, min_ch_tok;
+  int64_t max_tick, max_msgs, max_inflight, max_node, max_ch_msgs, max_ch_tok;
+};
+inline StatsLayout stats_layout(int64_t N, int64_t C, int64_t tick_lo, int64_t T, int64_t M) {
+  StatsLayout L{};
+  L.n_nodes = N, L.n_channels = C, L.tick_lo = tick_lo, L.tick_bins = T, L.msg_bins = M;
+  int64_t o = 0;
+  auto take = [&o](int64_t n) { const int64_t at = o; o += n; return at; };
+  L.sum_begin = o;
+  L.instances = take(1), L.ok = take(1), L.sample = take(1);
+  L.tick_sum = take(1), L.tick_sumsq = take(1), L.tick_hist = take(T);
+  L.msgs_sum = take(1), L.msgs_sumsq = take(1), L.inflight_sum = take(1), L.inflight_sumsq = take(1);
+  L.node_sum = take(N), L.node_sumsq = take(N);
+  L.ch_msgs_sum = take(C), L.ch_msgs_sumsq = take(C), L.ch_tok_sum = take(C), L.ch_tok_sumsq = take(C);
+  L.ch_msg_hist = take(C * M);
+  L.sum_end = L.min_begin = o;
+  L.min_tick = take(1), L.min_msgs = take(1), L.min_inflight = take(1);
+  L.min_node = take(N), L.min_ch_msgs = take(C), L.min_ch_tok = take(C);
+  L.min_end = L.max_begin = o;
+  L.max_tick = take(1), L.max_msgs = take(1), L.max_inflight = take(1);
+  L.max_node = take(N), L.max_ch_msgs = take(C), L.max_ch_tok = take(C);
+  L.max_end = L.total_words = o;
+  return L;
+}
+
+// The statistics kernel walks the records in tiles of 64 record slots x one chunk of record
+// words, staged in LDS.  A chunk is at most kStatsChunkWords words of every instance: whole node
+// records (rw <= kStatsChunkWords) or a piece of one node's record.  Chunk i covers the words
+// [word0, word0 + nv * kw) of an instance's N * rw record words.
+constexpr int32_t kStatsChunkWords = 32;
+constexpr int32_t kStatsThreads = 256;
+// LDS budget of one statistics workgroup (dynamic LDS, no opt-in needed; at least two workgroups
+// share a CU's 160 KB, more when the pass needs less): the staging tiles of its 4 waves, the tick histogram, and per record word of
+// the pass 8 int64 accumulators and msg_bins histogram counters.  Topologies whose N * rw
+// words do not fit run as several passes over chunk ranges (cl_host.cpp stats()).
+constexpr int32_t kStatsLdsBytes = 64 * 1024;
+constexpr int32_t kStatsStageWords = kWave * (kStatsChunkWords + 1);  // per wave, rows padded odd
+constexpr int32_t kStatsScalars = 16;                                  // int64 words (15 used)
+struct StatsChunk {
+  int32_t v0, nv, k0, kw;
+};
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int32_t stats_chunks(int32_t n_nodes, int32_t rw) {
+  if (rw <= kStatsChunkWords) {
+    const int32_t g = kStatsChunkWords / rw;
+    return (n_nodes + g - 1) / g;
+  }
+  return n_nodes * ((rw + kStatsChunkWords - 1) / kStatsChunkWords);
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline StatsChunk stats_chunk(int32_t n_nodes, int32_t rw, int32_t i) {
+  StatsChunk c;
+  if (rw <= kStatsChunkWords) {
+    const int32_t g = kStatsChunkWords / rw;
+    c.v0 = i * g;
+    c.nv = n_nodes - c.v0 < g ? n_nodes - c.v0 : g;
+    c.k0 = 0;
+    c.kw = rw;
+  } else {
+    const int32_t pieces = (rw + kStatsChunkWords - 1) / kStatsChunkWords;
+    c.v0 = i / pieces;
+    c.nv = 1;
+    c.k0 = (i % pieces) * kStatsChunkWords;
+    c.kw = rw - c.k0 < kStatsChunkWords ? rw - c.k0 : kStatsChunkWords;
+  }
+  return c;
+}
+// Record words a pass may accumulate within the LDS budget (>= kStatsChunkWords for every legal
+// spec: 4096 tick bins, 64 message bins leave 47).
+inline int32_t stats_pass_words(int32_t tick_bins, int32_t msg_bins) {
+  const int32_t fixed = kWavesPerBlock * kStatsStageWords * 4 + tick_bins * 4 + kStatsScalars * 8;
+  return (kStatsLdsBytes - fixed) / (8 * 8 + msg_bins * 4);
+}
+// LDS bytes of a workgroup whose pass accumulates acc_words record words.
+inline int32_t stats_lds_bytes(int32_t acc_words, int32_t tick_bins, int32_t msg_bins) {
+  return kWavesPerBlock * kStatsStageWords * 4 + tick_bins * 4 + kStatsScalars * 8 + acc_words * (8 * 8 + msg_bins * 4);
+}
+// Workgroups per CU the grid is sized for: what the CU's LDS holds of them, at most 8 (32 waves).
+inline int32_t stats_blocks_per_cu(int32_t lds_bytes) {
+  const int32_t b = kMaxLdsBytes / (lds_bytes > 0 ? lds_bytes : 1);
+  return b < 1 ? 1 : b > 8 ? 8 : b;
+}
+
+struct StatsParams {
+  int32_t n_nodes, n_ch, s_cap, rw, sid;
+  int64_t n_inst, stride;
+  int64_t lo, hi;            // the sample's instance range
+  int64_t tile_lo, tile_hi;  // 64-slot tiles to walk (instance-major: those overlapping [lo, hi))
+  const int32_t* regs;
+  const int32_t* snap_tick;
+  const uint32_t* snap_nod;
+  int32_t blocked;           // records block-major by slot (rec_word)
+  const int32_t* inst_map;   // slot -> instance of a block-major replay (nullptr: identity)
+  const int32_t* word_ch;    // [N * rw] record word -> channel, -2 token word, -1 padding
+  const int32_t* hist_off;   // [C + 1]
+  const long long* hist_pre; // prefix sums of the token histories: channel c at hist_off[c] + c
+  int32_t chunk_lo, chunk_hi;  // chunks whose words this pass accumulates
+  int32_t totals;              // this pass also takes the counts, tick, msgs and inflight
+  int32_t acc_words;           // record words of the pass (LDS accumulator rows)
+  StatsLayout lay;
+  long long* out;  // [lay.total_words], initialised by the host (0 / INT64_MAX / INT64_MIN)
+};
+int launch_stats(const StatsParams& p, int32_t blocks, void* stream);
 
 // Snapshot content hash (shared definition with oracle/cl_oracle.c orc_snapshot_hash).
 #if defined(__HIPCC__)

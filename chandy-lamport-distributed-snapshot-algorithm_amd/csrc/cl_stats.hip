@@ -1,0 +1,348 @@
+// cl_stats.hip -- per-snapshot batch statistics of the batch engine (cl_snapshot_stats).
+//
+// One pass over the result planes of a run: the status word of `regs`, the completion tick of
+// snapshot `sid` in `snap_tick`, and snapshot sid's slice of the node records `snap_nod`.  The
+// sample is every instance of [lo, hi) with status OK in which the snapshot completed; for it
+// the kernel reduces count / sum / sum of squares / min / max / histograms of the completion
+// tick, of every node's tokenMap entry, of every channel's recorded messages and tokens, and of
+// the per-instance totals, into one flat int64 array (StatsLayout).  All integer, so the result
+// does not depend on the grid, the record layout or the exec kernel that wrote the records.
+//
+// Read pattern.  A wave walks tiles of 64 record slots (grid-stride, the grid sized to the chip).
+// Per tile and chunk of record words (cl_engine.h stats_chunk) it stages 64 x K words in LDS:
+//   block-major records [S][I/64][N][64][rw]: the tile is one 64-slot block, a chunk of whole
+//     nodes is nv * 64 * rw contiguous words, read lane-linear (dwordx4 when rw % 4 == 0); the
+//     slot's instance comes from the replay's slot -> instance map, and a sub-range filters on it;
+//   instance-major records [S][I][N][rw]: the tile's 64 instances are 64 * N * rw contiguous
+//     words; a chunk takes K contiguous words of each (all of them when N * rw <= 32, e.g. the
+//     8-node degree-3 topology's 128 B), again lane-linear.
+// Rows are padded to an odd pitch, so both phases below read the tile without bank conflicts.
+//
+// Reduction.  Two views of the staged tile:
+//   lane = slot      the instance's totals (recorded messages, recorded tokens) over the chunk's
+//                    channel words; tick, msgs and inflight then accumulate in the lane's
+//                    registers over all its tiles and are wave-reduced once at the end;
+//   lane = word      each lane owns one record word of the chunk (a node's token word, or a
+//                    channel's cursor word) and runs over the tile's sample instances (a scalar
+//                    loop over the ballot mask): sum, sum of squares, min, max in registers, the
+//                    message-count histogram in LDS; one LDS atomic per statistic and tile folds
+//                    them into the workgroup's accumulators.
+// A channel's recorded tokens are two loads of the host-built int64 prefix of its token history.
+// At the end each workgroup issues one global integer atomic per accumulator that is not at its
+// identity.  No per-lane global atomics, no floating point.
+//
+// LDS: kStatsLdsBytes per workgroup (cl_engine.h).  When the N * rw record words of the topology
+// need more accumulator rows than fit, the host runs several passes, each accumulating a range
+// of chunks; the first also takes the per-instance totals (it reads every chunk).
+#include <hip/hip_runtime.h>
+
+#include "cl_engine.h"
+
+namespace clsnap {
+namespace {
+
+constexpr long long kI64Max = 0x7fffffffffffffffLL;
+constexpr long long kI64Min = -kI64Max - 1;
+
+__device__ __forceinline__ void stats_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+struct Stat4 {
+  unsigned long long sum, sq;
+  long long mn, mx;
+  __device__ __forceinline__ void init() { sum = 0, sq = 0, mn = kI64Max, mx = kI64Min; }
+  __device__ __forceinline__ void add(long long v) {
+    sum += (unsigned long long)v;
+    sq += (unsigned long long)v * (unsigned long long)v;  // modulo 2^64
+    mn = v < mn ? v : mn;
+    mx = v > mx ? v : mx;
+  }
+  // values known to fit 32 bits: the square is one 32 x 32 -> 64 multiply-add
+  __device__ __forceinline__ void add_i32(int32_t v) {
+    sum += (unsigned long long)(long long)v;
+    sq += (unsigned long long)((long long)v * (long long)v);
+    mn = v < mn ? v : mn;
+    mx = v > mx ? v : mx;
+  }
+  __device__ __forceinline__ void add_u32(uint32_t v) {
+    sum += v;
+    sq += (unsigned long long)v * (unsigned long long)v;
+    mn = (long long)v < mn ? (long long)v : mn;
+    mx = (long long)v > mx ? (long long)v : mx;
+  }
+  __device__ __forceinline__ void wave_reduce() {
+    for (int o = 32; o > 0; o >>= 1) {
+      sum += __shfl_xor(sum, o);
+      sq += __shfl_xor(sq, o);
+      const long long a = __shfl_xor(mn, o), b = __shfl_xor(mx, o);
+      mn = a < mn ? a : mn;
+      mx = b > mx ? b : mx;
+    }
+  }
+};
+
+// Accumulator rows in LDS: [8][acc_words] int64 -- sum, sumsq, min, max of the word's first
+// statistic (tokenMap entry / recorded messages), then of its second (recorded tokens).
+__device__ __forceinline__ void fold(long long* acc, int32_t aw, int32_t row, int32_t k, const Stat4& s) {
+  long long* a = acc + (size_t)(4 * k) * aw + row;
+  if (s.sum) atomicAdd((unsigned long long*)a, s.sum);
+  if (s.sq) atomicAdd((unsigned long long*)(a + aw), s.sq);
+  atomicMin(a + 2 * (size_t)aw, s.mn);
+  atomicMax(a + 3 * (size_t)aw, s.mx);
+}
+
+__global__ __launch_bounds__(kStatsThreads) void cl_stats_kernel(StatsParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char stats_lds[];
+  const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int32_t AW = p.acc_words, M = (int32_t)p.lay.msg_bins, T = (int32_t)p.lay.tick_bins;
+  long long* acc = reinterpret_cast<long long*>(stats_lds);            // [8][AW]
+  long long* scal = acc + 8 * (size_t)AW;                              // [kStatsScalars]
+  uint32_t* mh = reinterpret_cast<uint32_t*>(scal + kStatsScalars);    // [AW][M]
+  uint32_t* th = mh + (size_t)AW * M;                                  // [T]
+  uint32_t* tile = th + T + (size_t)wave * kStatsStageWords;           // [64][K | 1]
+
+  for (int32_t i = threadIdx.x; i < 8 * AW; i += kStatsThreads) {
+    const int32_t k = (i / AW) & 3;
+    acc[i] = k == 2 ? kI64Max : k == 3 ? kI64Min : 0;
+  }
+  for (int32_t i = threadIdx.x; i < kStatsScalars; i += kStatsThreads)
+    scal[i] = (i == 5 || i == 9 || i == 13) ? kI64Max : (i == 6 || i == 10 || i == 14) ? kI64Min : 0;
+  for (int32_t i = threadIdx.x; i < AW * M + T; i += kStatsThreads) mh[i] = 0;  // (mh and th are adjacent)
+  __syncthreads();
+
+  const int32_t N = p.n_nodes, rw = p.rw;
+  const int32_t n_chunks = stats_chunks(N, rw);
+  const int32_t word_lo = [&] {
+    const StatsChunk c = stats_chunk(N, rw, p.chunk_lo);
+    return c.v0 * rw + c.k0;
+  }();
+  const size_t plane = (size_t)p.sid * (size_t)p.stride * (size_t)N * (size_t)rw;
+  const bool vec = (rw & 3) == 0;  // every chunk then starts and ends on 16 bytes
+
+  unsigned long long n_all = 0, n_ok = 0, n_sample = 0;
+  Stat4 s_tick, s_msgs, s_infl;
+  s_tick.init(), s_msgs.init(), s_infl.init();
+
+  const int64_t wave_stride = (int64_t)gridDim.x * kWavesPerBlock;
+  for (int64_t t = p.tile_lo + (int64_t)blockIdx.x * kWavesPerBlock + wave; t < p.tile_hi; t += wave_stride) {
+    const int64_t slot = t * 64 + lane;
+    int64_t inst = -1;
+    if (slot < p.n_inst) inst = p.blocked && p.inst_map ? (int64_t)p.inst_map[slot] : slot;
+    const bool in = inst >= p.lo && inst < p.hi;
+    bool ok = false, sample = false;
+    int32_t tick = -1;
+    if (in) {
+      ok = p.regs[inst * R_NUM + R_STATUS] == ST_OK;
+      tick = p.snap_tick[inst * p.s_cap + p.sid];
+      sample = ok && tick >= 0;
+    }
+    const unsigned long long mask = __ballot(sample);
+    if (p.totals) {
+      n_all += in, n_ok += ok, n_sample += sample;
+      if (sample) {
+        s_tick.add(tick);
+        long long bin = (long long)tick - p.lay.tick_lo;
+        bin = bin < 0 ? 0 : bin > T - 1 ? T - 1 : bin;
+        atomicAdd(&th[bin], 1u);
+      }
+    }
+    if (mask == 0) continue;  // (wave-uniform: no records of this tile are in the sample)
+
+    unsigned long long tot_msgs = 0, tot_tok = 0;
+    // a pass without the totals reads its own chunks only
+    const int32_t c_begin = p.totals ? 0 : p.chunk_lo, c_end = p.totals ? n_chunks : p.chunk_hi;
+    for (int32_t ci = c_begin; ci < c_end; ++ci) {
+      const StatsChunk ch = stats_chunk(N, rw, ci);
+      const int32_t K = ch.nv * ch.kw, pitch = K | 1, w0 = ch.v0 * rw + ch.k0;
+      // ---- stage 64 rows x K words, in memory order
+      stats_wave_sync();  // (the previous chunk's readers are done with the tile)
+      if (p.blocked) {
+        // rows of node v: 64 records at pitch rw, nodes at pitch 64 * rw
+        const uint32_t* src = p.snap_nod + plane + (size_t)t * 64 * (size_t)N * (size_t)rw;
+        if (vec) {
+          const int32_t kq = ch.kw >> 2, per_node = 64 * kq;
+          for (int32_t f = lane; f < ch.nv * per_node; f += 64) {
+            const int32_t vl = f / per_node, rem = f - vl * per_node, r = rem / kq, q = rem - r * kq;
+            const uint4 x = *reinterpret_cast<const uint4*>(src + ((size_t)(ch.v0 + vl) * 64 + r) * rw + ch.k0 + 4 * q);
+            uint32_t* d = tile + r * pitch + vl * ch.kw + 4 * q;
+            d[0] = x.x, d[1] = x.y, d[2] = x.z, d[3] = x.w;
+          }
+        } else {
+          const int32_t per_node = 64 * ch.kw;
+          for (int32_t f = lane; f < ch.nv * per_node; f += 64) {
+            const int32_t vl = f / per_node, rem = f - vl * per_node, r = rem / ch.kw, k = rem - r * ch.kw;
+            tile[r * pitch + vl * ch.kw + k] = src[((size_t)(ch.v0 + vl) * 64 + r) * rw + ch.k0 + k];
+          }
+        }
+      } else {
+        // row r = instance 64 t + r: its K words start at word w0 of its N * rw
+        const uint32_t* src = p.snap_nod + plane + (size_t)t * 64 * (size_t)N * (size_t)rw + w0;
+        const size_t row = (size_t)N * (size_t)rw;
+        if (vec) {
+          const int32_t kq = K >> 2;
+          for (int32_t f = lane; f < 64 * kq; f += 64) {
+            const int32_t r = f / kq, q = f - r * kq;
+            const uint4 x = *reinterpret_cast<const uint4*>(src + r * row + 4 * q);
+            uint32_t* d = tile + r * pitch + 4 * q;
+            d[0] = x.x, d[1] = x.y, d[2] = x.z, d[3] = x.w;
+          }
+        } else {
+          for (int32_t f = lane; f < 64 * K; f += 64) {
+            const int32_t r = f / K, k = f - r * K;
+            tile[r * pitch + k] = src[r * row + k];
+          }
+        }
+      }
+      stats_wave_sync();
+
+      // ---- lane = slot: the instance's totals over this chunk's channel words
+      if (p.totals && sample) {
+        for (int32_t k = 0; k < K; ++k) {
+          const int32_t c = p.word_ch[w0 + k];
+          if (c < 0) continue;
+          const uint32_t rec = tile[lane * pitch + k], b = rec & 0xffffu, e = rec >> 16;
+          tot_msgs += e - b;
+          if (e != b) {
+            const long long* pre = p.hist_pre + p.hist_off[c] + c;
+            tot_tok += (unsigned long long)(pre[e] - pre[b]);
+          }
+        }
+      }
+
+      // ---- lane = word: every word of the chunk over the tile's sample instances
+      if (ci >= p.chunk_lo && ci < p.chunk_hi) {
+        for (int32_t k0 = 0; k0 < K; k0 += 64) {
+          const int32_t k = k0 + lane;
+          const int32_t c = k < K ? p.word_ch[w0 + k] : -1;
+          if (c == -1) continue;
+          const int32_t row = w0 + k - word_lo;
+          Stat4 a, b2;
+          a.init(), b2.init();
+          if (c == -2) {
+            for (unsigned long long m = mask; m; m &= m - 1) {
+              const int32_t i = __builtin_ctzll(m);
+              a.add_i32((int32_t)tile[i * pitch + k]);
+            }
+            fold(acc, AW, row, 0, a);
+          } else {
+            const long long* pre = p.hist_pre + p.hist_off[c] + c;
+            uint32_t* h = mh + (size_t)row * M;
+            for (unsigned long long m = mask; m; m &= m - 1) {
+              const int32_t i = __builtin_ctzll(m);
+              const uint32_t rec = tile[i * pitch + k], b = rec & 0xffffu, e = rec >> 16;
+              const uint32_t cnt = e - b;
+              a.add_u32(cnt);
+              // (the full 64 bits, as the lane = slot side keeps for the instance's total)
+              b2.add(e != b ? pre[e] - pre[b] : 0);
+              atomicAdd(&h[cnt < (uint32_t)(M - 1) ? cnt : (uint32_t)(M - 1)], 1u);
+            }
+            fold(acc, AW, row, 0, a);
+            fold(acc, AW, row, 1, b2);
+          }
+        }
+      }
+    }
+    if (p.totals && sample) {
+      s_msgs.add((long long)tot_msgs);
+      s_infl.add((long long)tot_tok);
+    }
+  }
+
+  if (p.totals) {
+    for (int o = 32; o > 0; o >>= 1) {
+      n_all += __shfl_xor(n_all, o);
+      n_ok += __shfl_xor(n_ok, o);
+      n_sample += __shfl_xor(n_sample, o);
+    }
+    s_tick.wave_reduce(), s_msgs.wave_reduce(), s_infl.wave_reduce();
+    if (lane == 0) {
+      unsigned long long* u = (unsigned long long*)scal;
+      if (n_all) atomicAdd(&u[0], n_all);
+      if (n_ok) atomicAdd(&u[1], n_ok);
+      if (n_sample) atomicAdd(&u[2], n_sample);
+      const Stat4* s3[3] = {&s_tick, &s_msgs, &s_infl};
+      for (int q = 0; q < 3; ++q) {
+        if (s3[q]->sum) atomicAdd(&u[3 + 4 * q], s3[q]->sum);
+        if (s3[q]->sq) atomicAdd(&u[4 + 4 * q], s3[q]->sq);
+        atomicMin(&scal[5 + 4 * q], s3[q]->mn);
+        atomicMax(&scal[6 + 4 * q], s3[q]->mx);
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- one global atomic per accumulator of the workgroup that left its identity
+  const StatsLayout& L = p.lay;
+  auto g_add = [&](int64_t at, unsigned long long v) {
+    if (v) atomicAdd((unsigned long long*)(p.out + at), v);
+  };
+  auto g_min = [&](int64_t at, long long v) {
+    if (v != kI64Max) atomicMin(p.out + at, v);
+  };
+  auto g_max = [&](int64_t at, long long v) {
+    if (v != kI64Min) atomicMax(p.out + at, v);
+  };
+  if (p.totals) {
+    if (threadIdx.x == 0) {
+      g_add(L.instances, (unsigned long long)scal[0]);
+      g_add(L.ok, (unsigned long long)scal[1]);
+      g_add(L.sample, (unsigned long long)scal[2]);
+      const int64_t sum_at[3] = {L.tick_sum, L.msgs_sum, L.inflight_sum};
+      const int64_t sq_at[3] = {L.tick_sumsq, L.msgs_sumsq, L.inflight_sumsq};
+      for (int q = 0; q < 3; ++q) {
+        g_add(sum_at[q], (unsigned long long)scal[3 + 4 * q]);
+        g_add(sq_at[q], (unsigned long long)scal[4 + 4 * q]);
+        g_min(L.min_tick + q, scal[5 + 4 * q]);
+        g_max(L.max_tick + q, scal[6 + 4 * q]);
+      }
+    }
+    for (int32_t i = threadIdx.x; i < T; i += kStatsThreads) g_add(L.tick_hist + i, th[i]);
+  }
+  const int32_t n_words = [&] {
+    if (p.chunk_hi <= p.chunk_lo) return 0;
+    const StatsChunk c = stats_chunk(N, rw, p.chunk_hi - 1);
+    return c.v0 * rw + c.k0 + c.nv * c.kw - word_lo;
+  }();
+  for (int32_t row = threadIdx.x; row < n_words; row += kStatsThreads) {
+    const int32_t w = word_lo + row, c = p.word_ch[w];
+    if (c == -1) continue;
+    const long long* a = acc + row;
+    if (c == -2) {
+      const int32_t v = w / rw;
+      g_add(L.node_sum + v, (unsigned long long)a[0]);
+      g_add(L.node_sumsq + v, (unsigned long long)a[(size_t)AW]);
+      g_min(L.min_node + v, a[2 * (size_t)AW]);
+      g_max(L.max_node + v, a[3 * (size_t)AW]);
+    } else {
+      g_add(L.ch_msgs_sum + c, (unsigned long long)a[0]);
+      g_add(L.ch_msgs_sumsq + c, (unsigned long long)a[(size_t)AW]);
+      g_min(L.min_ch_msgs + c, a[2 * (size_t)AW]);
+      g_max(L.max_ch_msgs + c, a[3 * (size_t)AW]);
+      g_add(L.ch_tok_sum + c, (unsigned long long)a[4 * (size_t)AW]);
+      g_add(L.ch_tok_sumsq + c, (unsigned long long)a[5 * (size_t)AW]);
+      g_min(L.min_ch_tok + c, a[6 * (size_t)AW]);
+      g_max(L.max_ch_tok + c, a[7 * (size_t)AW]);
+    }
+  }
+  // the message-count histograms: rows of channel words only
+  for (int32_t i = threadIdx.x; i < n_words * M; i += kStatsThreads) {
+    const uint32_t v = mh[i];
+    if (!v) continue;
+    const int32_t row = i / M, c = p.word_ch[word_lo + row];
+    if (c >= 0) g_add(L.ch_msg_hist + (int64_t)c * M + (i - row * M), v);
+  }
+}
+
+}  // namespace
+
+int launch_stats(const StatsParams& p, int32_t blocks, void* stream) {
+  const size_t lds = (size_t)stats_lds_bytes(p.acc_words, (int32_t)p.lay.tick_bins, (int32_t)p.lay.msg_bins);
+  if (lds > (size_t)kStatsLdsBytes || blocks < 1) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(cl_stats_kernel, dim3((unsigned)blocks), dim3(kStatsThreads), lds, (hipStream_t)stream, p);
+  return (int)hipGetLastError();
+}
+
+}  // namespace clsnap

@@ -35,6 +35,23 @@ def reduce_max(values, device):
     return [float(v) for v in t.tolist()]
 
 
+def reduce_stats(stats, device):
+    """A rank's SnapshotStats (ChandyLamportSim.snapshot_stats of its shard) reduced over all
+    ranks: one all_reduce each -- SUM, MIN, MAX -- over the three sections of the flat array
+    (the int64 sums wrap modulo 2**64, like the sums of squares themselves).  Every rank must
+    pass the same layout.  Returns a new SnapshotStats; without an initialised group, a copy."""
+    L = stats.layout
+    t = torch.from_numpy(stats.raw.copy()).to(device)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        for lo, hi, op in ((L["sum_begin"], L["sum_end"], dist.ReduceOp.SUM),
+                           (L["min_begin"], L["min_end"], dist.ReduceOp.MIN),
+                           (L["max_begin"], L["max_end"], dist.ReduceOp.MAX)):
+            part = t[lo:hi].contiguous()
+            dist.all_reduce(part, op=op)
+            t[lo:hi] = part
+    return type(stats)(L, t.cpu().numpy())
+
+
 # ---- exchange layer of the graph-partitioned mode (DESIGN.md §11) ---------------------
 # One simulation whose nodes are split into rank ranges exchanges, every tick, records
 # addressed to the owners of other nodes (deliveries, broadcast-trigger reports, draw

@@ -163,9 +163,10 @@ int cl_replay_split(cl_sim* sim, int64_t* spill_instances, int64_t* split_slot);
  * results unchanged). */
 int cl_replay_mapped(cl_sim* sim, int32_t* on);
 
-/* 1 when the snapshot records in device memory are block-major by replay slot (the latest launch
- * from the initial state was a replay through the slot map on the instance-per-lane kernels);
- * engine-internal, every reader (CollectSnapshot, checksums, packed collects) handles both. */
+/* 1 when the snapshot records in device memory are block-major by replay slot: the latest launch
+ * from the initial state was a replay through the slot map that saved no state image (cl_rerun
+ * of a mapped plan), on either exec kernel.  Engine-internal: every reader (CollectSnapshot,
+ * checksums, counters, packed collects, instance hashes, statistics) handles both layouts. */
 int cl_records_blocked(cl_sim* sim, int32_t* on);
 
 /* Which exec kernel runs the program (engine-internal; results are identical):
@@ -269,6 +270,56 @@ int cl_get_checksums(cl_sim* sim, int64_t* out /* [CL_NUM_SUMS] */);
  * instance (the sum over its completed snapshots of the content hash; 0 unless the instance is
  * CL_INST_OK), for instance-by-instance parity checks of a whole batch. */
 int cl_instance_hashes(cl_sim* sim, int64_t lo, int64_t n, uint64_t* out);
+
+/* ---- per-snapshot batch statistics (no reference counterpart: the batch is a Monte-Carlo
+ * experiment over the delay streams, this is its distribution) ------------------------------
+ * The sample of cl_snapshot_stats(sid, [inst_lo, inst_hi)) is every instance of the range with
+ * status CL_INST_OK in which snapshot sid has completed (the instances CL_SUM_COMPLETED counts).
+ * One reduction kernel reads the status, completion-tick and snapshot-record planes on the
+ * device; only the result crosses PCIe.  `out` is one flat int64 array of three contiguous
+ * sections, so ranks and sub-ranges merge with one SUM, one MIN and one MAX over three slices:
+ *   SUM  instances (all of the range), ok, sample;
+ *        tick_sum, tick_sumsq, tick_hist[tick_bins]   bin clamp(tick - tick_lo, 0, tick_bins - 1)
+ *        msgs_sum, msgs_sumsq          recorded messages of an instance, over all channels
+ *        inflight_sum, inflight_sumsq  recorded tokens of an instance (the in-flight part of the cut)
+ *        node_sum[N], node_sumsq[N]    tokenMap entry per node, rank order
+ *        ch_msgs_sum[C], ch_msgs_sumsq[C], ch_tok_sum[C], ch_tok_sumsq[C]   per channel (cl_channel order)
+ *        ch_msg_hist[C][msg_bins]      bin min(recorded messages, msg_bins - 1)
+ *   MIN  tick, msgs, inflight, node[N], ch_msgs[C], ch_tok[C]   (INT64_MAX on an empty sample)
+ *   MAX  the same fields                                          (INT64_MIN on an empty sample)
+ * Total words: 15 + tick_bins + 4 N + 8 C + C * msg_bins.  Everything is exact integer arithmetic
+ * and independent of the grid, the record layout and the exec kernel; the sums of squares
+ * accumulate modulo 2^64 (two's complement wrap-around; merge them with wrapping adds). */
+#define CL_STATS_MAX_TICK_BINS 4096
+#define CL_STATS_MAX_MSG_BINS 64
+typedef struct {
+  int32_t tick_lo;   /* completion tick of histogram bin 0 */
+  int32_t tick_bins; /* 1 .. CL_STATS_MAX_TICK_BINS */
+  int32_t msg_bins;  /* 1 .. CL_STATS_MAX_MSG_BINS */
+} cl_stats_spec;
+/* Offsets, in int64 words, of every field of `out` (array fields: their first word), the three
+ * section bounds and the total; the first five fields restate the shape the layout is for. */
+typedef struct {
+  int64_t n_nodes, n_channels, tick_lo, tick_bins, msg_bins;
+  int64_t total_words, sum_begin, sum_end, min_begin, min_end, max_begin, max_end;
+  int64_t instances, ok, sample, tick_sum, tick_sumsq, tick_hist, msgs_sum, msgs_sumsq, inflight_sum,
+      inflight_sumsq, node_sum, node_sumsq, ch_msgs_sum, ch_msgs_sumsq, ch_tok_sum, ch_tok_sumsq, ch_msg_hist;
+  int64_t min_tick, min_msgs, min_inflight, min_node, min_ch_msgs, min_ch_tok;
+  int64_t max_tick, max_msgs, max_inflight, max_node, max_ch_msgs, max_ch_tok;
+} cl_stats_layout;
+#define CL_STATS_LAYOUT_FIELDS 41
+/* The layout for this sim's topology and a spec.  Host only, no device. */
+int cl_stats_layout_of(const cl_sim* sim, const cl_stats_spec* spec, cl_stats_layout* out);
+/* The statistics of snapshot sid over instances [inst_lo, inst_hi) into out[out_words].  Like
+ * the other result queries it executes pending events and never adds a tick, holds the sim's
+ * lock and waits for a split replay's second half.  Arguments are checked before any device
+ * work: CL_E_INVALID (bad spec, sid or range out of bounds, NULL pointer), CL_E_STATE (no event
+ * was ever issued: nothing has run), CL_E_LIMIT (out_words below the layout's total_words).
+ * inst_lo == inst_hi is valid: the empty sample. */
+int cl_snapshot_stats(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_stats_spec* spec,
+                      int64_t* out, int64_t out_words);
+/* Device time of the latest cl_snapshot_stats kernel(s) (HIP events), like cl_collect_time. */
+int cl_stats_time(cl_sim* sim, double* device_ms);
 
 /* ---- device event trace: the reference's debug Logger (logger.go:12-76) ---- */
 /* One LogEvent (logger.go:18-23) per record, in the Logger's order.  Node ranks refer

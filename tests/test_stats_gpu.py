@@ -1,0 +1,258 @@
+"""ChandyLamportSim.snapshot_stats (cl_snapshot_stats, cl_stats.hip) against the oracle.
+
+Expected values: numpy over one OracleSim per instance (statscheck.expected); every field of every
+section must be equal exactly.  Each scenario runs on the library's choice of exec kernel (AUTO)
+and with the instance-per-lane kernel forced where the topology fits it, in both record layouts
+(instance-major after flush(), block-major by slot after rerun() of a mapped plan).
+"""
+import importlib
+
+import numpy as np
+import pytest
+
+import oracle as O
+from snapcheck import read_text
+from statscheck import I64_MAX, I64_MIN, Rows, assert_stats_equal, expected, scenario_rows
+
+cl = importlib.import_module("chandy-lamport-distributed-snapshot-algorithm_amd")
+pytestmark = pytest.mark.gpu
+
+AUTO, LANES = cl.ChandyLamportSim.ENGINE_AUTO, cl.ChandyLamportSim.ENGINE_LANES
+ENGINES = pytest.mark.parametrize("engine", [AUTO, LANES], ids=["auto", "lanes"])
+
+C3_TOP, C3_EVENTS = "8nodes.top", "8nodes-concurrent-snapshots.events"
+
+# case 3: every node can pay for every send; N1->N2 carries up to 12 recorded messages
+TOP3 = "3\nN1 30\nN2 30\nN3 30\nN1 N2\nN2 N1\nN1 N3\nN3 N1\nN2 N3\nN3 N2\n"
+_ROUND = "send N1 N2 1\nsend N1 N2 2\nsend N2 N3 1\nsend N1 N3 1\nsend N3 N1 1\nsend N1 N2 1\ntick 1\n"
+EVENTS3 = (_ROUND * 3 + "snapshot N3\n" + "send N1 N2 1\nsend N2 N1 1\ntick 1\n" * 2
+           + "snapshot N1\nsend N1 N2 1\ntick 2\n")
+
+# case 4: the hub of test_gpu_parity.test_uneven_fan_out_runtime_loop_kernel, 4 snapshots: degree
+# bound 16, max in-degree 2, so a node record has 3 words -- not a power of two
+_LEAVES = [f"L{k}" for k in range(10)]
+HUB_TOP = (f"{len(_LEAVES) + 1}\nH 40\n" + "".join(f"{x} 5\n" for x in _LEAVES)
+           + "".join(f"H {x}\n" for x in _LEAVES)
+           + "".join(f"{_LEAVES[k]} {_LEAVES[(k + 1) % 10]}\n" for k in range(10)) + "L0 H\n")
+HUB_EVENTS = "".join(f"send H {_LEAVES[(3 * r) % 10]} 2\nsnapshot {'H' if r % 2 == 0 else _LEAVES[r]}\n"
+                     f"send L{r} L{r + 1} 1\ntick 2\n" for r in range(4))
+
+
+def text(x):
+    return x if "\n" in x else read_text(x)
+
+
+def make_sim(top, events, n, engine):
+    sim = cl.ChandyLamportSim(n)
+    sim.set_exec_engine(engine)
+    sim.read_topology_text(text(top))
+    if events is not None:
+        sim.read_events_text(text(events))
+    return sim
+
+
+def flush_on(sim, engine):
+    """flush(); a forced engine must be the one the launch used."""
+    sim.flush()
+    if engine != AUTO:
+        assert sim.exec_engine() == engine
+
+
+def replay_blocked(sim):
+    """rerun() of the flushed program with poisoned outputs: the records come from the replay,
+    block-major by slot."""
+    sim.poison_outputs()
+    sim.rerun()
+    sim.synchronize()
+    assert sim.records_blocked()
+
+
+def check(sim, rows, ranges, what, sids=None, **spec):
+    layout = sim.stats_layout(**spec)
+    for sid in range(rows.n_sids) if sids is None else sids:
+        for lo, hi in ranges:
+            st = sim.snapshot_stats(sid, lo, hi, **spec)
+            assert st.layout == layout
+            assert_stats_equal(st.raw, expected(layout, rows, sid, lo, hi), layout, f"{what} sid {sid} [{lo}, {hi})")
+
+
+# ---- 1 / 2: mixed statuses, instance-major and block-major -----------------------------------
+@ENGINES
+def test_c3_mixed_statuses_both_layouts(engine):
+    n = 4096
+    rows = scenario_rows(C3_TOP, C3_EVENTS, n)
+    assert rows.n_sids == 5
+    assert int((rows.status == O.FATAL_INSUFFICIENT_TOKENS).sum()) == 117  # the exclusion is exercised
+    sim = make_sim(C3_TOP, C3_EVENTS, n, engine)
+    flush_on(sim, engine)
+    assert not sim.records_blocked()
+    ranges = [(0, n), (37, 3001)]
+    check(sim, rows, ranges, "instance-major")
+    replay_blocked(sim)
+    check(sim, rows, ranges, "block-major")
+    assert sim.stats_time() > 0
+
+
+# ---- 3: histogram clamps and multi-message channels --------------------------------------------
+@ENGINES
+def test_histogram_clamps_and_multi_message_channels(engine):
+    n = 4096
+    rows = scenario_rows(TOP3, EVENTS3, n)
+    assert (rows.status == O.OK).all()
+    msgs0 = np.array(rows.ch_msgs[0])
+    assert msgs0.max() == 12 and msgs0.max() > 8 - 1          # the message clamp is hit
+    assert rows.tick[0].min() < 20 and rows.tick[0].max() >= 23  # both tick clamps are hit
+    spec = dict(tick_lo=20, tick_bins=4, msg_bins=8)
+    sim = make_sim(TOP3, EVENTS3, n, engine)
+    flush_on(sim, engine)
+    check(sim, rows, [(0, n)], "after flush", **spec)
+    replay_blocked(sim)
+    check(sim, rows, [(0, n)], "after rerun", **spec)
+
+
+# ---- 4: node records of 3 words (not a power of two) --------------------------------------------
+def test_hub_three_word_records_instance_major():
+    n = 512
+    rows = scenario_rows(HUB_TOP, HUB_EVENTS, 4096)   # (instance i is seeded by i alone)
+    assert (rows.status == O.OK).all() and rows.n_sids == 4
+    sim = make_sim(HUB_TOP, HUB_EVENTS, n, AUTO)
+    sim.flush()
+    assert not sim.records_blocked()
+    check(sim, rows, [(0, n), (5, 300)], "hub after flush")
+
+
+def test_hub_three_word_records_block_major():
+    n = 4096
+    rows = scenario_rows(HUB_TOP, HUB_EVENTS, n)
+    sim = make_sim(HUB_TOP, HUB_EVENTS, n, AUTO)
+    sim.flush()
+    replay_blocked(sim)
+    check(sim, rows, [(0, n), (37, 3001)], "hub after rerun")
+
+
+# ---- 5: incomplete but OK, and the state-image path -------------------------------------------
+@ENGINES
+def test_incomplete_ok_instances_and_resumed_program(engine):
+    n = 512
+    refs = []
+    for i in range(n):
+        r = O.OracleSim()
+        r.seed_go(O.REFERENCE_SEED + i)
+        assert r.read_topology_text(read_text("3nodes.top")) == 0
+        assert r.send_tokens("N1", "N2", 1) == 0 and r.send_tokens("N2", "N3", 2) == 0
+        assert r.start_snapshot("N1")[0] == 0
+        for _ in range(8):
+            r.tick()
+        refs.append(r)
+    rows = Rows(refs)
+    complete = int(rows.done[0].sum())
+    assert (rows.status == O.OK).all() and 0 < complete < n
+    sim = make_sim("3nodes.top", None, n, engine)
+    sim.ProcessEvent(cl.PassTokenEvent("N1", "N2", 1))
+    sim.ProcessEvent(cl.PassTokenEvent("N2", "N3", 2))
+    assert sim.StartSnapshot("N1") == 0
+    sim.Tick(8)
+    st = sim.snapshot_stats(0)          # executes the pending events, adds no tick
+    assert st.sample == complete and st.ok == n and st.instances == n
+    check(sim, rows, [(0, n), (3, 401)], "mid-program")
+    for r in refs:
+        for _ in range(8):
+            r.tick()
+    rows2 = Rows(refs)
+    sim.Tick(8)                         # resumes from the saved state image
+    check(sim, rows2, [(0, n)], "resumed")
+    assert sim.snapshot_stats(0).sample == int(rows2.done[0].sum())
+
+
+# ---- 6: the empty sample -----------------------------------------------------------------------
+def _assert_empty(st, instances, ok):
+    L = st.layout
+    assert (st.instances, st.ok, st.sample) == (instances, ok, 0)
+    assert not st.raw[L["sum_begin"] + 2:L["sum_end"]].any()
+    assert (st.raw[L["min_begin"]:L["min_end"]] == I64_MAX).all()
+    assert (st.raw[L["max_begin"]:L["max_end"]] == I64_MIN).all()
+
+
+@ENGINES
+def test_empty_sample(engine):
+    n = 64
+    rows = scenario_rows("3nodes.top", EVENTS3, n)
+    assert (rows.status == O.FATAL_INSUFFICIENT_TOKENS).all()   # N3 starts with 0 tokens
+    sim = make_sim("3nodes.top", EVENTS3, n, engine)
+    flush_on(sim, engine)
+    assert (sim.status() == cl.INST_FATAL_INSUFFICIENT_TOKENS).all()
+    for sid in range(2):
+        _assert_empty(sim.snapshot_stats(sid), n, 0)
+    check(sim, rows, [(0, n)], "all fatal", sids=range(2))
+    healthy = make_sim(TOP3, EVENTS3, n, engine)
+    flush_on(healthy, engine)
+    _assert_empty(healthy.snapshot_stats(0, 17, 17), 0, 0)
+    assert healthy.snapshot_stats(0).sample == n
+
+
+# ---- 7: accumulators beyond the LDS budget (several passes) -----------------------------------
+def test_accumulators_beyond_lds():
+    n, k = 128, 24
+    ids = [f"N{v:02d}" for v in range(k)]
+    top = f"{k}\n" + "".join(f"{x} 100\n" for x in ids) + "".join(f"{a} {b}\n" for a in ids for b in ids if a != b)
+    events = ("send N00 N01 3\nsend N05 N02 1\nsnapshot N03\nsend N01 N00 2\ntick 1\n"
+              "send N10 N11 4\nsnapshot N20\nsend N02 N05 1\ntick 2\n")
+    rows = scenario_rows(top, events, n)
+    assert (rows.status == O.OK).all() and rows.n_sids == 2
+    sim = make_sim(top, events, n, AUTO)
+    assert sim.num_channels == 552
+    sim.flush()
+    check(sim, rows, [(0, n), (5, 70)], "24-node complete digraph", tick_lo=0, tick_bins=4096, msg_bins=64)
+
+
+# ---- 7b: node records longer than a staging chunk (rw > 32: a chunk is a piece of one record) ----
+@pytest.mark.parametrize("leaves", [33, 35], ids=["rw34_scalar", "rw36_dwordx4"])
+def test_records_longer_than_a_chunk(leaves):
+    """A star whose hub has `leaves` links in and out: degree bound 64, so a node record is 1 + leaves
+    words -- 34 (staged word by word) or 36 (a multiple of 4: staged with dwordx4 loads), each
+    more than the 32 words of a staging chunk, and N * rw words need several passes."""
+    n = 130
+    ids = [f"L{k:02d}" for k in range(leaves)]
+    top = (f"{leaves + 1}\nH 9\n" + "".join(f"{x} 6\n" for x in ids) + "".join(f"{x} H\n" for x in ids)
+           + "".join(f"H {x}\n" for x in ids))
+    events = ("".join(f"send {x} H {1 + k % 3}\n" for k, x in enumerate(ids)) + "send H L00 2\nsnapshot L01\n"
+              + "".join(f"send {x} H 1\n" for x in ids[::2]) + "tick 1\nsnapshot H\n"
+              + "".join(f"send {x} H 2\n" for x in ids[1::2]) + "send H L02 1\ntick 2\n")
+    rows = scenario_rows(top, events, n)
+    assert (rows.status == O.OK).all() and rows.n_sids == 2
+    assert max(int(rows.ch_msgs[s].max()) for s in range(2)) >= 1    # some channel records messages
+    sim = make_sim(top, events, n, AUTO)
+    assert sim.num_channels == 2 * leaves
+    sim.flush()
+    assert not sim.records_blocked()
+    check(sim, rows, [(0, n), (3, 77)], f"star with {leaves} leaves", tick_lo=0, tick_bins=64, msg_bins=4)
+
+
+# ---- 8: ragged sizes and merge --------------------------------------------------------------------
+@ENGINES
+@pytest.mark.parametrize("n", [1, 63, 65, 257])
+def test_ragged_batch_sizes(n, engine):
+    rows = scenario_rows(TOP3, EVENTS3, 4096)   # (instance i is seeded by i alone)
+    sim = make_sim(TOP3, EVENTS3, n, engine)
+    flush_on(sim, engine)
+    check(sim, rows, [(0, n)], f"n = {n}", tick_lo=16, tick_bins=16, msg_bins=16)
+
+
+@ENGINES
+def test_merge_of_sub_ranges(engine):
+    n = 4096
+    sim = make_sim(TOP3, EVENTS3, n, engine)
+    flush_on(sim, engine)
+    for blocked in (False, True):
+        if blocked:
+            replay_blocked(sim)
+        for sid in range(2):
+            whole = sim.snapshot_stats(sid, 0, n, tick_lo=16, tick_bins=16)
+            for a in (1, 64, 1000):
+                parts = sim.snapshot_stats(sid, 0, a, tick_lo=16, tick_bins=16).merge(
+                    sim.snapshot_stats(sid, a, n, tick_lo=16, tick_bins=16))
+                assert_stats_equal(parts.raw, whole.raw, whole.layout, f"merge at {a} blocked {blocked}")
+                assert parts == whole
+    other = sim.snapshot_stats(0, tick_bins=8)
+    with pytest.raises(ValueError):
+        whole.merge(other)
