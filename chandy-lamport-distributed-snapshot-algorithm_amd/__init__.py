@@ -125,6 +125,9 @@ def lib():
         "cl_stats_layout_of": [vp, vp, vp],
         "cl_snapshot_stats": [vp, i32, i64, i64, vp, vp, i64],
         "cl_stats_time": [vp, vp],
+        "cl_snapshot_census": [vp, i32, i64, i64, vp, vp, vp, vp],
+        "cl_census_time": [vp, vp],
+        "cl_collect_snapshot_list": [vp, i32, vp, i64, vp, vp, vp, vp, i64, vp],
     }
     for name, args in sig.items():
         if os.environ.get("CLSNAP_VARIANT") and not hasattr(L, name):
@@ -324,6 +327,92 @@ class SnapshotStats:
     __hash__ = None
 
 
+# cl_census_class / cl_census_spec / cl_census_info (include/clsnap.h)
+CENSUS_CLASS_DTYPE = np.dtype([("key", np.uint64), ("count", np.int64), ("first_inst", np.int64),
+                               ("min_tick", np.int32), ("max_tick", np.int32)])
+
+
+class _CensusSpec(C.Structure):
+    _fields_ = [("max_classes", C.c_int64), ("lds_slots", C.c_int32)]
+
+
+def _sort_classes(classes):
+    """count descending, then key ascending (unsigned): the order cl_snapshot_census returns."""
+    order = np.lexsort((classes["key"], -classes["count"]))
+    return np.ascontiguousarray(classes[order])
+
+
+class SnapshotCensus:
+    """The result of ``ChandyLamportSim.snapshot_census``: the distinct global snapshots of a batch.
+
+    ``classes`` is a structured array (CENSUS_CLASS_DTYPE: key, count, first_inst, min_tick,
+    max_tick) of the returned classes, ordered by count descending, then key ascending;
+    ``n_classes`` counts all distinct keys, also those beyond ``max_classes``.  ``class_of``
+    (or None) maps each instance of the range to its class index, -1 outside the sample.  Classes
+    are keyed by the 64-bit snapshot content hash."""
+
+    def __init__(self, snapshot_id, instances, ok, sample, n_classes, classes, class_of=None):
+        self.snapshot_id = int(snapshot_id)
+        self.instances, self.ok, self.sample, self.n_classes = int(instances), int(ok), int(sample), int(n_classes)
+        self.classes = np.ascontiguousarray(classes, dtype=CENSUS_CLASS_DTYPE)
+        self.class_of = class_of
+
+    @property
+    def n_returned(self):
+        return int(self.classes.shape[0])
+
+    def frequency(self, k):
+        """Share of the sample in returned class k; nan on an empty sample."""
+        return float(self.classes["count"][k]) / self.sample if self.sample else float("nan")
+
+    def merge(self, other, offset=0):
+        """The census of the union of two disjoint instance sets (other ranks, other ranges);
+        ``offset`` is added to ``other``'s instance indices.  Same key: counts add, first_inst and
+        min_tick take the minimum, max_tick the maximum.  Re-sorted; class_of is dropped.  Raises
+        ValueError when either side was truncated (n_returned < n_classes) or the snapshot ids differ."""
+        if not isinstance(other, SnapshotCensus) or other.snapshot_id != self.snapshot_id:
+            raise ValueError("SnapshotCensus.merge: not a census of the same snapshot id")
+        if self.n_returned < self.n_classes or other.n_returned < other.n_classes:
+            raise ValueError("SnapshotCensus.merge: a truncated census (n_returned < n_classes) cannot be merged")
+        b = other.classes.copy()
+        b["first_inst"] += offset
+        both = np.concatenate([self.classes, b])
+        keys, inv = np.unique(both["key"], return_inverse=True)
+        out = np.zeros(keys.size, dtype=CENSUS_CLASS_DTYPE)
+        out["key"] = keys
+        out["first_inst"] = np.iinfo(np.int64).max
+        out["min_tick"] = np.iinfo(np.int32).max
+        out["max_tick"] = np.iinfo(np.int32).min
+        np.add.at(out["count"], inv, both["count"])
+        np.minimum.at(out["first_inst"], inv, both["first_inst"])
+        np.minimum.at(out["min_tick"], inv, both["min_tick"])
+        np.maximum.at(out["max_tick"], inv, both["max_tick"])
+        return SnapshotCensus(self.snapshot_id, self.instances + other.instances, self.ok + other.ok,
+                              self.sample + other.sample, keys.size, _sort_classes(out))
+
+    def snapshots(self, sim):
+        """One GlobalSnapshot per returned class: its representative's contents, all collected in
+        one collect_snapshot_list call."""
+        tok, _, off, msg = sim.collect_snapshot_list(self.snapshot_id, self.classes["first_inst"])
+        ids, chans = sim.node_ids(), sim.channels()
+        ch = len(chans)
+        order = sorted(range(ch), key=lambda c: (chans[c][1], chans[c][0]))
+        out = []
+        for r in range(self.n_returned):
+            msgs = [MsgSnapshot(ids[chans[c][0]], ids[chans[c][1]], int(msg[k]))
+                    for c in order for k in range(off[r * ch + c], off[r * ch + c + 1])]
+            out.append(GlobalSnapshot(self.snapshot_id, {ids[v]: int(tok[r, v]) for v in range(len(ids))}, msgs))
+        return out
+
+    def __eq__(self, other):
+        return (isinstance(other, SnapshotCensus) and self.snapshot_id == other.snapshot_id
+                and (self.instances, self.ok, self.sample, self.n_classes)
+                == (other.instances, other.ok, other.sample, other.n_classes)
+                and self.classes.tobytes() == other.classes.tobytes())
+
+    __hash__ = None
+
+
 class ChandyLamportSim:
     """A batch of ``n_instances`` reference simulators (sim.go ChandyLamportSim).
 
@@ -500,6 +589,46 @@ class ChandyLamportSim:
         ms = C.c_double(0)
         _check(self._L.cl_stats_time(self._h, C.byref(ms)))
         return ms.value
+
+    def snapshot_census(self, snapshot_id, inst_lo=0, inst_hi=None, max_classes=4096, class_of=False, lds_slots=0):
+        """The distinct global snapshots `snapshot_id` produced over the OK instances of
+        [inst_lo, inst_hi) in which it completed, grouped on the GPU by content hash
+        (cl_snapshot_census): a SnapshotCensus of at most `max_classes` classes, most frequent
+        first.  class_of=True also returns each instance's class index.  lds_slots: 0 = the
+        engine's workgroup table, -1 = none, else a power of two in [16, 4096] (results are the same)."""
+        hi = self.n_instances if inst_hi is None else inst_hi
+        spec = _CensusSpec(max_classes, lds_slots)
+        classes = np.zeros(max(max_classes, 0), dtype=CENSUS_CLASS_DTYPE)
+        cls = np.full(max(hi - inst_lo, 0), -1, dtype=np.int32) if class_of else None
+        info = np.zeros(5, dtype=np.int64)
+        _check(self._L.cl_snapshot_census(self._h, snapshot_id, inst_lo, hi, C.byref(spec),
+                                          _p(classes) if max_classes > 0 else None,
+                                          _p(cls) if class_of else None, _p(info)))
+        instances, ok, sample, n_classes, n_returned = info.tolist()
+        return SnapshotCensus(snapshot_id, instances, ok, sample, n_classes, classes[:n_returned].copy(), cls)
+
+    def census_time(self):
+        """Device ms of the latest snapshot_census kernels."""
+        ms = C.c_double(0)
+        _check(self._L.cl_census_time(self._h, C.byref(ms)))
+        return ms.value
+
+    def collect_snapshot_list(self, snapshot_id, insts):
+        """collect_snapshot_packed over an instance list (cl_collect_snapshot_list): row r is
+        instance insts[r]; any order, duplicates allowed.  Same tuple as collect_snapshot_packed."""
+        insts = np.ascontiguousarray(insts, dtype=np.int64).ravel()
+        k, n, ch = insts.size, self.num_nodes, self.num_channels
+        tok, done = np.zeros((k, n), dtype=np.int32), np.zeros(k, dtype=np.int32)
+        off, msg = np.zeros(k * ch + 1, dtype=np.int64), np.zeros(max(1024, 4 * k), dtype=np.int32)
+        m = C.c_int64(0)
+        for _ in range(2):
+            rc = self._L.cl_collect_snapshot_list(self._h, snapshot_id, _p(insts), k, _p(tok), _p(done), _p(off),
+                                                  _p(msg), msg.size, C.byref(m))
+            if rc != -7 or m.value <= msg.size:
+                break
+            msg = np.zeros(m.value, dtype=np.int32)
+        _check(rc)
+        return tok, done.astype(bool), off, msg[:m.value]
 
     # ---- drivers (test_common.go) -------------------------------------------
     def read_topology_file(self, path):           # test_common.go:29

@@ -373,6 +373,8 @@ int launch_checksums(const SumParams& p, void* stream);
 struct PackParams {
   int32_t n_nodes, n_ch, s_cap, rw, sid;
   int64_t lo, n, stride;
+  const long long* insts;   // [n] row r packs instance insts[r] (any order, duplicates allowed), or
+                            // nullptr: row r packs instance lo + r
   const uint32_t* snap_nod;
   const int32_t* rec_slot;  // as SumParams::rec_slot
   const int32_t* snap_tick;
@@ -509,6 +511,62 @@ struct StatsParams {
   long long* out;  // [lay.total_words], initialised by the host (0 / INT64_MAX / INT64_MIN)
 };
 int launch_stats(const StatsParams& p, int32_t blocks, void* stream);
+
+// ---- snapshot outcome census (cl_census.hip; include/clsnap.h cl_snapshot_census) --------------
+// A group-by of the snapshot content hash over the sample of cl_snapshot_stats.  One entry of the
+// global open-addressing table, and of the compacted class array (the layout of cl_census_class).
+struct CensusEntry {
+  unsigned long long key;
+  unsigned long long count;  // (the class's rank, once the host has sorted: cl_census_rank)
+  long long first;           // smallest instance of the class
+  int32_t min_tick, max_tick;
+};
+// The table's "empty" marker.  A snapshot whose key has this value is a class like any other: it
+// bypasses the hashed slots and lives in the extra entry table[slots] (CensusParams::empty_key).
+constexpr unsigned long long kCensusEmptyKey = ~0ULL;
+constexpr int32_t kCensusThreads = 256;
+constexpr int32_t kCensusMinLdsSlots = 16, kCensusMaxLdsSlots = 4096;
+// The engine's choice of workgroup table: with the staging tiles it stays below 64 KB of LDS, so
+// two workgroups and more share a CU (the scenarios measured have 2 .. 413 classes).
+constexpr int32_t kCensusAutoLdsSlots = 1024;
+// Probes before an LDS insert gives up and goes to the global table (a full or crowded table).
+constexpr int32_t kCensusLdsProbes = 16;
+// Records of at most this many words per instance are staged in LDS tile by tile (address-ordered
+// loads, cl_stats.hip's pattern); longer ones are read word by word by the instance's lane.
+constexpr int32_t kCensusStageWords = kStatsChunkWords;
+constexpr int32_t kCensusLdsEntryBytes = 8 + 8 + 4 + 4 + 4;  // key, first, count, min tick, max tick
+inline int32_t census_lds_bytes(int32_t lds_slots, bool staged) {
+  return lds_slots * kCensusLdsEntryBytes + 4 * 8 + (staged ? kWavesPerBlock * kStatsStageWords * 4 : 0);
+}
+struct CensusParams {
+  int32_t n_nodes, n_ch, s_cap, rw, sid;
+  int64_t n_inst, stride;
+  int64_t lo, hi;            // the sample's instance range
+  int64_t tile_lo, tile_hi;  // 64-slot tiles to walk (as StatsParams)
+  const int32_t* regs;
+  const int32_t* snap_tick;
+  const uint32_t* snap_nod;
+  int32_t blocked;           // records block-major by slot (rec_word)
+  const int32_t* inst_map;   // slot -> instance of a block-major replay (nullptr: identity)
+  const int32_t* ch_slot;    // [C] record word of channel c
+  const int32_t* hist_off;   // [C + 1]
+  const int32_t* hist_val;
+  int32_t lds_slots;         // workgroup table entries (a power of two), 0: none
+  int32_t staged;            // N * rw <= kCensusStageWords: records staged in LDS
+  unsigned long long empty_key;
+  CensusEntry* table;        // [slots + 1], initialised by launch_census_init
+  int64_t slots;             // a power of two >= 2 * (hi - lo)
+  uint32_t* list;            // [hi - lo] table slots in the order they were claimed
+  unsigned long long* info;  // instances, ok, sample, n_classes
+  unsigned long long* keys;  // [hi - lo] each sample instance's key, or nullptr
+  int32_t* class_of;         // [hi - lo] 0 for sample instances, -1 for the others (with keys)
+};
+int launch_census_init(const CensusParams& p, void* stream);
+int launch_census_keys(const CensusParams& p, int32_t blocks, void* stream);
+// out[j] = table[list[j]], j < n
+int launch_census_gather(const CensusParams& p, int64_t n, CensusEntry* out, void* stream);
+// table[list[j]].count = rank[j], j < n; then class_of[i] = rank of keys[i]'s class
+int launch_census_class_of(const CensusParams& p, int64_t n, const int32_t* rank, void* stream);
 
 // Snapshot content hash (shared definition with oracle/cl_oracle.c orc_snapshot_hash).
 #if defined(__HIPCC__)

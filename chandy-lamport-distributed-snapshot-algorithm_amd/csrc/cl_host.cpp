@@ -18,6 +18,7 @@
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <mutex>
@@ -381,6 +382,14 @@ struct cl_sim {
   hipEvent_t st_ev[2] = {nullptr, nullptr};
   bool st_timed = false;
   int32_t n_cus = 0;
+  // snapshot outcome census (cl_snapshot_census, cl_census.hip)
+  DevBuf<CensusEntry> d_cs_table, d_cs_out;
+  DevBuf<uint32_t> d_cs_list;
+  DevBuf<unsigned long long> d_cs_info, d_cs_keys;
+  DevBuf<int32_t> d_cs_class, d_cs_rank;
+  DevBuf<long long> d_pk_list;  // instance list of cl_collect_snapshot_list
+  hipEvent_t cs_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int32_t cs_timed = 0;  // event pairs of the latest census (0: none has run)
   size_t hist_uploaded = (size_t)-1;  // history entries on the device
 
   ~cl_sim() {
@@ -396,6 +405,10 @@ struct cl_sim {
       d_pk_tok.release(); d_pk_done.release(); d_pk_msg.release(); d_pk_cnt.release(); d_pk_bsum.release();
       d_pk_off.release(); d_rec2.release(); d_ihash.release();
       d_word_ch.release(); d_hist_pre.release(); d_stats.release();
+      d_cs_table.release(); d_cs_out.release(); d_cs_list.release(); d_cs_info.release(); d_cs_keys.release();
+      d_cs_class.release(); d_cs_rank.release(); d_pk_list.release();
+      for (auto& e : cs_ev)
+        if (e) (void)hipEventDestroy(e);
       for (auto& e : pk_ev)
         if (e) (void)hipEventDestroy(e);
       for (auto& e : st_ev)
@@ -1108,13 +1121,18 @@ struct cl_sim {
 
   // CollectSnapshot of instances [lo, hi) packed on the device (cl_pack_count / cl_pack_fill):
   // the packed arrays stay in d_pk_*; *total = messages.  Times the kernels (cl_collect_time).
-  int pack(int32_t sid, int64_t lo, int64_t hi, int64_t* total) {
+  // With `insts` (cl_collect_snapshot_list) row r packs instance insts[r], r < hi - lo.
+  int pack(int32_t sid, int64_t lo, int64_t hi, int64_t* total, const int64_t* insts = nullptr) {
     int rc = flush();
     if (rc) return rc;
     if (!dev_ready) return set_err(CL_E_STATE, "nothing has run on the device yet");
     HIP_TRY(hipSetDevice(device));
     if ((rc = upload_hist())) return rc;
     const int64_t n = hi - lo;
+    if (insts && n > 0) {
+      if ((rc = d_pk_list.ensure((size_t)n))) return rc;
+      HIP_TRY(hipMemcpyAsync(d_pk_list.p, insts, (size_t)n * sizeof(long long), hipMemcpyHostToDevice, stream));
+    }
     const int N = (int)ids.size(), C = (int)ch_dst.size();
     if ((rc = d_pk_tok.ensure((size_t)std::max<int64_t>(n, 1) * N)) || (rc = d_pk_done.ensure((size_t)n + 1)) ||
         (rc = d_pk_cnt.ensure((size_t)n + 1)) || (rc = d_pk_bsum.ensure((size_t)(n / kScanItems + 1))) ||
@@ -1131,6 +1149,7 @@ struct cl_sim {
     p.lo = lo;
     p.n = n;
     p.stride = stride;
+    p.insts = insts && n > 0 ? d_pk_list.p : nullptr;
     p.snap_nod = d_snap_nod.p;
     p.rec_slot = rec_blocked ? d_rec_slot.p : nullptr;
     p.snap_tick = d_snap_tick.p;
@@ -1233,6 +1252,116 @@ struct cl_sim {
     st_timed = true;
     HIP_TRY(hipMemcpyAsync(out, d_stats.p, h.size() * sizeof(long long), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
+    return CL_OK;
+  }
+
+  // cl_snapshot_census (arguments checked by the caller): the classes of snapshot sid over
+  // [lo, hi), sorted, into *out; class_of[hi - lo] when asked for.  lds_slots: the workgroup
+  // table's entries, 0 for none.
+  int census(int32_t sid, int64_t lo, int64_t hi, int32_t lds_slots, std::vector<CensusEntry>* out,
+             int32_t* class_of, cl_census_info* info) {
+    int rc = flush();
+    if (rc) return rc;
+    if (!dev_ready) return set_err(CL_E_STATE, "nothing has run on the device yet");
+    HIP_TRY(hipSetDevice(device));
+    if ((rc = upload_hist())) return rc;
+    if (!n_cus) HIP_TRY(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device));
+    for (auto& e : cs_ev)
+      if (!e) HIP_TRY(hipEventCreate(&e));
+    const int64_t n = hi - lo;
+    out->clear();
+    *info = cl_census_info{};
+    if (n == 0) {
+      cs_timed = 0;
+      return CL_OK;
+    }
+    if (n > ((int64_t)1 << 29)) return set_err(CL_E_LIMIT, "census of more than 2^29 instances");
+    CensusParams p{};
+    p.slots = 16;
+    while (p.slots < 2 * n) p.slots <<= 1;
+    if ((rc = d_cs_table.ensure((size_t)p.slots + 1)) || (rc = d_cs_list.ensure((size_t)n)) ||
+        (rc = d_cs_info.ensure(4)))
+      return rc;
+    if (class_of && ((rc = d_cs_keys.ensure((size_t)n)) || (rc = d_cs_class.ensure((size_t)n)))) return rc;
+    p.n_nodes = (int32_t)ids.size();
+    p.n_ch = (int32_t)ch_dst.size();
+    p.s_cap = s_cap;
+    p.rw = lay.rw;
+    p.sid = sid;
+    p.n_inst = n_inst;
+    p.stride = stride;
+    p.lo = lo;
+    p.hi = hi;
+    p.regs = d_regs.p;
+    p.snap_tick = d_snap_tick.p;
+    p.snap_nod = d_snap_nod.p;
+    p.blocked = rec_blocked ? 1 : 0;
+    p.inst_map = rec_blocked && rec_slot_gen != -2 ? d_map.p : nullptr;  // (as stats())
+    p.ch_slot = d_ch_slot.p;
+    p.hist_off = d_hist.p;
+    p.hist_val = d_hist.p + hist.size() + 1;
+    p.lds_slots = lds_slots;
+    p.staged = p.n_nodes * p.rw <= kCensusStageWords ? 1 : 0;
+    p.empty_key = kCensusEmptyKey;
+    // (tests move the marker onto a key that occurs, to run the extra entry's path)
+    if (const char* v = std::getenv("CLSNAP_CENSUS_EMPTY_KEY")) p.empty_key = std::strtoull(v, nullptr, 0);
+    p.table = d_cs_table.p;
+    p.list = d_cs_list.p;
+    p.info = d_cs_info.p;
+    p.keys = class_of ? d_cs_keys.p : nullptr;
+    p.class_of = class_of ? d_cs_class.p : nullptr;
+    p.tile_lo = rec_blocked ? 0 : lo / kWave;
+    p.tile_hi = rec_blocked ? stride / kWave : (hi + kWave - 1) / kWave;
+    const int64_t tiles = p.tile_hi - p.tile_lo;
+    const int32_t per_cu = stats_blocks_per_cu(census_lds_bytes(lds_slots, p.staged != 0));
+    const int32_t blocks = (int32_t)std::min<int64_t>((tiles + kWavesPerBlock - 1) / kWavesPerBlock,
+                                                      (int64_t)per_cu * std::max(n_cus, 1));
+    HIP_TRY(hipEventRecord(cs_ev[0], stream));
+    HIP_TRY(hipMemsetAsync(d_cs_info.p, 0, 4 * sizeof(unsigned long long), stream));
+    int e = launch_census_init(p, stream);
+    if (!e) e = launch_census_keys(p, blocks, stream);
+    if (e) return set_err(CL_E_DEVICE, "census kernels: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipEventRecord(cs_ev[1], stream));
+    unsigned long long h[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, d_cs_info.p, sizeof h, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    cs_timed = 1;
+    const int64_t k = (int64_t)h[3];
+    if (k > n) return set_err(CL_E_DEVICE, "census: %lld classes of %lld instances", (long long)k, (long long)n);
+    info->instances = (int64_t)h[0], info->ok = (int64_t)h[1], info->sample = (int64_t)h[2], info->n_classes = k;
+    // ---- the k classes: compacted on the device, sorted here
+    std::vector<CensusEntry> got((size_t)k);
+    if (k > 0) {
+      if ((rc = d_cs_out.ensure((size_t)k))) return rc;
+      HIP_TRY(hipEventRecord(cs_ev[2], stream));
+      if ((e = launch_census_gather(p, k, d_cs_out.p, stream)))
+        return set_err(CL_E_DEVICE, "census kernels: %s", hipGetErrorString((hipError_t)e));
+      HIP_TRY(hipEventRecord(cs_ev[3], stream));
+      HIP_TRY(hipMemcpyAsync(got.data(), d_cs_out.p, (size_t)k * sizeof(CensusEntry), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      cs_timed = 2;
+    }
+    std::vector<int32_t> order((size_t)k);
+    for (int64_t j = 0; j < k; ++j) order[(size_t)j] = (int32_t)j;
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+      const CensusEntry &x = got[(size_t)a], &y = got[(size_t)b];
+      return x.count != y.count ? x.count > y.count : x.key < y.key;
+    });
+    out->resize((size_t)k);
+    for (int64_t j = 0; j < k; ++j) (*out)[(size_t)j] = got[(size_t)order[(size_t)j]];
+    if (!class_of) return CL_OK;
+    // ---- class_of: the ranks go back into the table, a lookup maps key -> rank per instance
+    std::vector<int32_t> rank((size_t)std::max<int64_t>(k, 1));
+    for (int64_t j = 0; j < k; ++j) rank[(size_t)order[(size_t)j]] = (int32_t)j;
+    if ((rc = d_cs_rank.ensure(rank.size()))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_cs_rank.p, rank.data(), rank.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(cs_ev[4], stream));
+    if ((e = launch_census_class_of(p, k, d_cs_rank.p, stream)))
+      return set_err(CL_E_DEVICE, "census kernels: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipEventRecord(cs_ev[5], stream));
+    HIP_TRY(hipMemcpyAsync(class_of, d_cs_class.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    cs_timed = 3;
     return CL_OK;
   }
 
@@ -1859,6 +1988,23 @@ int cl_collect_snapshot_range(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t
   return CL_OK;
 }
 
+// The packed arrays pack() left on the device (rows = instances packed, tot = messages) into the
+// caller's buffers: cl_collect_snapshot_packed's output contract.
+static int copy_packed(cl_sim* sim, int64_t rows, int64_t tot, int32_t* tokens, int32_t* complete,
+                       int64_t* msg_offsets, int32_t* msg_tokens, int64_t msg_cap, int64_t* n_msgs) {
+  if (n_msgs) *n_msgs = tot;
+  const size_t n = (size_t)rows, N = sim->ids.size(), C = sim->ch_dst.size();
+  if (tokens && n) HIP_TRY(hipMemcpyAsync(tokens, sim->d_pk_tok.p, n * N * 4, hipMemcpyDeviceToHost, sim->stream));
+  if (complete && n) HIP_TRY(hipMemcpyAsync(complete, sim->d_pk_done.p, n * 4, hipMemcpyDeviceToHost, sim->stream));
+  if (msg_offsets)
+    HIP_TRY(hipMemcpyAsync(msg_offsets, sim->d_pk_off.p, (n * C + 1) * 8, hipMemcpyDeviceToHost, sim->stream));
+  const bool fits = tot <= msg_cap && (tot == 0 || msg_tokens);
+  if (fits && tot > 0)
+    HIP_TRY(hipMemcpyAsync(msg_tokens, sim->d_pk_msg.p, (size_t)tot * 4, hipMemcpyDeviceToHost, sim->stream));
+  HIP_TRY(hipStreamSynchronize(sim->stream));
+  return fits ? CL_OK : set_err(CL_E_LIMIT, "msg_cap %lld < %lld messages", (long long)msg_cap, (long long)tot);
+}
+
 int cl_collect_snapshot_packed(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, int32_t* tokens,
                                int32_t* complete, int64_t* msg_offsets, int32_t* msg_tokens, int64_t msg_cap,
                                int64_t* n_msgs) {
@@ -1868,16 +2014,23 @@ int cl_collect_snapshot_packed(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_
   int64_t tot = 0;
   int rc = sim->pack(sid, inst_lo, inst_hi, &tot);
   if (rc) return rc;
-  if (n_msgs) *n_msgs = tot;
-  const size_t n = (size_t)(inst_hi - inst_lo), N = sim->ids.size(), C = sim->ch_dst.size();
-  if (tokens && n) HIP_TRY(hipMemcpyAsync(tokens, sim->d_pk_tok.p, n * N * 4, hipMemcpyDeviceToHost, sim->stream));
-  if (complete && n) HIP_TRY(hipMemcpyAsync(complete, sim->d_pk_done.p, n * 4, hipMemcpyDeviceToHost, sim->stream));
-  if (msg_offsets) HIP_TRY(hipMemcpyAsync(msg_offsets, sim->d_pk_off.p, (n * C + 1) * 8, hipMemcpyDeviceToHost, sim->stream));
-  const bool fits = tot <= msg_cap && (tot == 0 || msg_tokens);
-  if (fits && tot > 0)
-    HIP_TRY(hipMemcpyAsync(msg_tokens, sim->d_pk_msg.p, (size_t)tot * 4, hipMemcpyDeviceToHost, sim->stream));
-  HIP_TRY(hipStreamSynchronize(sim->stream));
-  return fits ? CL_OK : set_err(CL_E_LIMIT, "msg_cap %lld < %lld messages", (long long)msg_cap, (long long)tot);
+  return copy_packed(sim, inst_hi - inst_lo, tot, tokens, complete, msg_offsets, msg_tokens, msg_cap, n_msgs);
+}
+
+int cl_collect_snapshot_list(cl_sim* sim, int32_t sid, const int64_t* insts, int64_t n, int32_t* tokens,
+                             int32_t* complete, int64_t* msg_offsets, int32_t* msg_tokens, int64_t msg_cap,
+                             int64_t* n_msgs) {
+  SIM_CHECK(sim);
+  if (sid < 0 || sid >= sim->n_sids || n < 0 || (n > 0 && !insts))
+    return set_err(CL_E_INVALID, "snapshot id or instance list out of range");
+  for (int64_t r = 0; r < n; ++r)
+    if (insts[r] < 0 || insts[r] >= sim->n_inst)
+      return set_err(CL_E_INVALID, "instance list entry %lld: instance %lld out of range", (long long)r,
+                     (long long)insts[r]);
+  int64_t tot = 0;
+  int rc = sim->pack(sid, 0, n, &tot, insts);
+  if (rc) return rc;
+  return copy_packed(sim, n, tot, tokens, complete, msg_offsets, msg_tokens, msg_cap, n_msgs);
 }
 
 int cl_collect_time(cl_sim* sim, double* device_ms) {
@@ -1940,6 +2093,48 @@ int cl_stats_time(cl_sim* sim, double* device_ms) {
   float f = 0.f;
   HIP_TRY(hipEventElapsedTime(&f, sim->st_ev[0], sim->st_ev[1]));
   *device_ms = f;
+  return CL_OK;
+}
+
+static_assert(sizeof(cl_census_class) == sizeof(CensusEntry) && sizeof(CensusEntry) == 32,
+              "cl_census_class mirrors CensusEntry");
+
+int cl_snapshot_census(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_census_spec* spec,
+                       cl_census_class* classes, int32_t* class_of, cl_census_info* info) {
+  SIM_CHECK(sim);
+  // every argument is checked before any device work
+  if (!spec || !info) return set_err(CL_E_INVALID, "null census spec or info");
+  const int32_t ls = spec->lds_slots;
+  if (spec->max_classes < 0 ||
+      !(ls == 0 || ls == -1 || (ls >= kCensusMinLdsSlots && ls <= kCensusMaxLdsSlots && (ls & (ls - 1)) == 0)))
+    return set_err(CL_E_INVALID, "census spec: max_classes >= 0; lds_slots 0, -1 or a power of two in [%d, %d]",
+                   kCensusMinLdsSlots, kCensusMaxLdsSlots);
+  if (spec->max_classes > 0 && !classes) return set_err(CL_E_INVALID, "null classes with max_classes > 0");
+  if (inst_lo < 0 || inst_hi > sim->n_inst || inst_lo > inst_hi)
+    return set_err(CL_E_INVALID, "instance range out of range");
+  if (sim->ops.empty() && !sim->dev_ready) return set_err(CL_E_STATE, "nothing has run yet: no event was issued");
+  if (sid < 0 || sid >= sim->n_sids) return set_err(CL_E_INVALID, "snapshot id out of range");
+  std::vector<CensusEntry> got;
+  const int32_t lds_slots = ls == 0 ? kCensusAutoLdsSlots : ls < 0 ? 0 : ls;
+  const int rc = sim->census(sid, inst_lo, inst_hi, lds_slots, &got, class_of, info);
+  if (rc) return rc;
+  info->n_returned = std::min<int64_t>(info->n_classes, spec->max_classes);
+  if (info->n_returned > 0) std::memcpy(classes, got.data(), (size_t)info->n_returned * sizeof(cl_census_class));
+  return CL_OK;
+}
+
+int cl_census_time(cl_sim* sim, double* device_ms) {
+  SIM_CHECK(sim);
+  if (!device_ms) return set_err(CL_E_INVALID, "null output");
+  if (!sim->cs_timed) return set_err(CL_E_STATE, "no census call has run");
+  HIP_TRY(hipStreamSynchronize(sim->stream));
+  double ms = 0;
+  for (int32_t q = 0; q < sim->cs_timed; ++q) {  // key pass, gather, class_of: the host's sort lies between
+    float f = 0.f;
+    HIP_TRY(hipEventElapsedTime(&f, sim->cs_ev[2 * q], sim->cs_ev[2 * q + 1]));
+    ms += f;
+  }
+  *device_ms = ms;
   return CL_OK;
 }
 

@@ -1124,7 +1124,7 @@ __global__ __launch_bounds__(256) void cl_recorded_kernel(SumParams p) {
 __global__ __launch_bounds__(256) void cl_pack_count(PackParams p) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
-  const int64_t inst = p.lo + i;
+  const int64_t inst = p.insts ? (int64_t)p.insts[i] : p.lo + i;
   const bool done = p.snap_tick[inst * p.s_cap + p.sid] >= 0;
   auto rb = [&](int32_t idx) { return p.snap_nod[rec_word(p.stride, p.n_nodes, p.rw, p.sid, inst, p.rec_slot, idx)]; };
   long long cnt = 0;
@@ -1203,7 +1203,7 @@ __global__ __launch_bounds__(256) void cl_pack_fill(PackParams p) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0) p.offsets[p.n * p.n_ch] = p.count[p.n];
   if (i >= p.n) return;
-  const int64_t inst = p.lo + i;
+  const int64_t inst = p.insts ? (int64_t)p.insts[i] : p.lo + i;
   const bool done = p.complete[i] != 0;
   auto rb = [&](int32_t idx) { return p.snap_nod[rec_word(p.stride, p.n_nodes, p.rw, p.sid, inst, p.rec_slot, idx)]; };
   long long m = p.count[i];

@@ -7,6 +7,7 @@ snapshot_test.go:20).  After the timed region the ranks all-reduce a handful of 
 checksums and take the max of their elapsed times -- RCCL over xGMI when the tensors
 live on the GPU (backend "nccl"), gloo on CPU in tests.
 """
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -50,6 +51,35 @@ def reduce_stats(stats, device):
             dist.all_reduce(part, op=op)
             t[lo:hi] = part
     return type(stats)(L, t.cpu().numpy())
+
+
+def gather_census(census, first_instance, device):
+    """A rank's SnapshotCensus (ChandyLamportSim.snapshot_census of its shard, whose instance 0 is
+    global instance `first_instance`) combined over all ranks: one all_gather of the (class
+    count, first instance) pairs sizes one all_gather of the class rows padded to the longest,
+    and the parts merge with each rank's first instance as offset (SnapshotCensus.merge; a
+    truncated census raises ValueError there).  Returns a new SnapshotCensus, the same on every
+    rank, with global instance indices; without an initialised group, a copy."""
+    cls = type(census)
+    mine = cls(census.snapshot_id, census.instances, census.ok, census.sample, census.n_classes, census.classes.copy())
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return mine
+    head = allgather_ints([mine.n_returned, first_instance, mine.instances, mine.ok, mine.sample, mine.n_classes],
+                          device)
+    words = mine.classes.dtype.itemsize // 8
+    rows = np.zeros((max(int(head[:, 0].max()), 1), words), dtype=np.int64)
+    rows[:mine.n_returned] = mine.classes.view(np.int64).reshape(-1, words)
+    t = torch.from_numpy(rows).to(device)
+    parts = [torch.empty_like(t) for _ in range(dist.get_world_size())]
+    dist.all_gather(parts, t)
+    out = None
+    for r, part in enumerate(parts):
+        k, first, instances, ok, sample, n_classes = (int(v) for v in head[r])
+        classes = part.cpu().numpy()[:k].reshape(-1).view(mine.classes.dtype)
+        c = cls(mine.snapshot_id, instances, ok, sample, n_classes, classes)
+        empty = cls(mine.snapshot_id, 0, 0, 0, 0, classes[:0])
+        out = empty.merge(c, offset=first) if out is None else out.merge(c, offset=first)
+    return out
 
 
 # ---- exchange layer of the graph-partitioned mode (DESIGN.md §11) ---------------------

@@ -260,6 +260,13 @@ int cl_collect_snapshot_range(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t
 int cl_collect_snapshot_packed(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, int32_t* tokens,
                                int32_t* complete, int64_t* msg_offsets, int32_t* msg_tokens, int64_t msg_cap,
                                int64_t* n_msgs);
+/* cl_collect_snapshot_packed over an instance list: row r is instance insts[r], r < n, in any
+ * order, duplicates allowed (msg_offsets has n * C + 1 entries).  An index outside
+ * [0, n_instances) gives CL_E_INVALID before any device work; otherwise the same outputs, NULL-able
+ * pointers and CL_E_LIMIT behaviour.  E.g. the representatives of cl_snapshot_census's classes. */
+int cl_collect_snapshot_list(cl_sim* sim, int32_t sid, const int64_t* insts, int64_t n, int32_t* tokens,
+                             int32_t* complete, int64_t* msg_offsets, int32_t* msg_tokens, int64_t msg_cap,
+                             int64_t* n_msgs);
 /* Device time of the latest packed collect's kernels (HIP events). */
 int cl_collect_time(cl_sim* sim, double* device_ms);
 /* Counters over instances (only_ok: restrict to CL_INST_OK instances). */
@@ -320,6 +327,45 @@ int cl_snapshot_stats(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi
                       int64_t* out, int64_t out_words);
 /* Device time of the latest cl_snapshot_stats kernel(s) (HIP events), like cl_collect_time. */
 int cl_stats_time(cl_sim* sim, double* device_ms);
+
+/* ---- snapshot outcome census: the distinct global snapshots of a batch -----------------------
+ * cl_snapshot_stats gives the marginal distributions; this is the joint one.  Over the same
+ * sample (instances of [inst_lo, inst_hi) with status CL_INST_OK in which snapshot sid has
+ * completed) the GPU groups the instances by the 64-bit snapshot content hash -- the value of
+ * orc_snapshot_hash, the per-snapshot term of CL_SUM_SNAPSHOT_HASH -- and returns one
+ * cl_census_class per distinct value.  Equality of snapshots here MEANS equality of that hash:
+ * contents are not compared (the engine's parity checks rest on the same hash).  Every key value,
+ * 0 and UINT64_MAX included, is a class.
+ *   classes    ordered by count descending, then key ascending (unsigned); the first
+ *              n_returned = min(n_classes, max_classes) are written
+ *   class_of   (may be NULL) class_of[i - inst_lo] = index of instance i's class in that full
+ *              order (not clamped to n_returned), -1 for instances outside the sample
+ *   info       instances, ok, sample as in cl_snapshot_stats; n_classes = distinct keys
+ * The result is a pure function of the records: it does not depend on the grid, on lds_slots, on
+ * the record layout or on the exec kernel.  Only n_classes * 32 bytes cross PCIe (plus class_of
+ * when asked for).  Like the other result queries the call executes pending events and never
+ * adds a tick, holds the sim's lock and waits for a split replay's second half.  Arguments are
+ * checked before any device work: CL_E_INVALID (bad spec, NULL info, NULL classes with
+ * max_classes > 0, sid or range out of bounds), CL_E_STATE (no event was ever issued).
+ * inst_lo == inst_hi is valid and gives an all-zero info. */
+typedef struct {
+  int64_t max_classes; /* entries of `classes` the caller provides, >= 0 */
+  int32_t lds_slots;   /* per-workgroup LDS table: 0 = engine's choice; -1 = none (every sample instance
+                          inserts into the global table); else a power of two in [16, 4096] */
+} cl_census_spec;
+typedef struct {       /* 32 bytes */
+  uint64_t key;        /* the snapshot content hash: orc_snapshot_hash, the per-snapshot term of
+                          CL_SUM_SNAPSHOT_HASH */
+  int64_t count;       /* sample instances with this content */
+  int64_t first_inst;  /* smallest instance index of the class (its representative) */
+  int32_t min_tick, max_tick; /* completion ticks over the class */
+} cl_census_class;
+typedef struct { int64_t instances, ok, sample, n_classes, n_returned; } cl_census_info;
+int cl_snapshot_census(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_census_spec* spec,
+                       cl_census_class* classes /* [max_classes], NULL iff max_classes == 0 */,
+                       int32_t* class_of /* [inst_hi - inst_lo] or NULL */, cl_census_info* info);
+/* Device time of the latest cl_snapshot_census kernels (HIP events), like cl_stats_time. */
+int cl_census_time(cl_sim* sim, double* device_ms);
 
 /* ---- device event trace: the reference's debug Logger (logger.go:12-76) ---- */
 /* One LogEvent (logger.go:18-23) per record, in the Logger's order.  Node ranks refer

@@ -1,0 +1,299 @@
+"""ChandyLamportSim.snapshot_census (cl_snapshot_census, cl_census.hip) and collect_snapshot_list
+against the oracle.
+
+Expected values: censuscheck.expected over one OracleSim per instance; every field of every class,
+the info and class_of must be equal exactly.  Each scenario runs on the library's choice of exec
+kernel (AUTO) and with the instance-per-lane kernel forced where the topology fits it, in both
+record layouts (instance-major after flush(), block-major by slot after rerun() of a mapped plan).
+"""
+import importlib
+
+import numpy as np
+import pytest
+
+import oracle as O
+from censuscheck import CensusRows, assert_census_equal, expected, global_snapshot_key, scenario_rows
+from snapcheck import read_text
+
+cl = importlib.import_module("chandy-lamport-distributed-snapshot-algorithm_amd")
+pytestmark = pytest.mark.gpu
+
+AUTO, LANES = cl.ChandyLamportSim.ENGINE_AUTO, cl.ChandyLamportSim.ENGINE_LANES
+ENGINES = pytest.mark.parametrize("engine", [AUTO, LANES], ids=["auto", "lanes"])
+
+C3_TOP, C3_EVENTS = "8nodes.top", "8nodes-concurrent-snapshots.events"
+
+# (the scenarios of test_stats_gpu.py) every node can pay for every send; N1->N2 carries up to 12
+# recorded messages
+TOP3 = "3\nN1 30\nN2 30\nN3 30\nN1 N2\nN2 N1\nN1 N3\nN3 N1\nN2 N3\nN3 N2\n"
+_ROUND = "send N1 N2 1\nsend N1 N2 2\nsend N2 N3 1\nsend N1 N3 1\nsend N3 N1 1\nsend N1 N2 1\ntick 1\n"
+EVENTS3 = (_ROUND * 3 + "snapshot N3\n" + "send N1 N2 1\nsend N2 N1 1\ntick 1\n" * 2
+           + "snapshot N1\nsend N1 N2 1\ntick 2\n")
+
+# a hub with 4 snapshots: degree bound 16, max in-degree 2, so a node record has 3 words -- not a
+# power of two -- and an instance's 33 record words are not staged in LDS
+_LEAVES = [f"L{k}" for k in range(10)]
+HUB_TOP = (f"{len(_LEAVES) + 1}\nH 40\n" + "".join(f"{x} 5\n" for x in _LEAVES)
+           + "".join(f"H {x}\n" for x in _LEAVES)
+           + "".join(f"{_LEAVES[k]} {_LEAVES[(k + 1) % 10]}\n" for k in range(10)) + "L0 H\n")
+HUB_EVENTS = "".join(f"send H {_LEAVES[(3 * r) % 10]} 2\nsnapshot {'H' if r % 2 == 0 else _LEAVES[r]}\n"
+                     f"send L{r} L{r + 1} 1\ntick 2\n" for r in range(4))
+
+
+def text(x):
+    return x if "\n" in x else read_text(x)
+
+
+def make_sim(top, events, n, engine):
+    sim = cl.ChandyLamportSim(n)
+    sim.set_exec_engine(engine)
+    sim.read_topology_text(text(top))
+    if events is not None:
+        sim.read_events_text(text(events))
+    return sim
+
+
+def flush_on(sim, engine):
+    """flush(); a forced engine must be the one the launch used."""
+    sim.flush()
+    if engine != AUTO:
+        assert sim.exec_engine() == engine
+
+
+def replay_blocked(sim):
+    """rerun() of the flushed program with poisoned outputs: the records come from the replay,
+    block-major by slot."""
+    sim.poison_outputs()
+    sim.rerun()
+    sim.synchronize()
+    assert sim.records_blocked()
+
+
+def check(sim, rows, ranges, what, sids=None, **kw):
+    for sid in range(rows.n_sids) if sids is None else sids:
+        for lo, hi in ranges:
+            got = sim.snapshot_census(sid, lo, hi, class_of=True, **kw)
+            assert_census_equal(got, expected(rows, sid, lo, hi), f"{what} sid {sid} [{lo}, {hi})")
+
+
+def both_layouts(sim, engine, body):
+    flush_on(sim, engine)
+    assert not sim.records_blocked()
+    body("instance-major")
+    replay_blocked(sim)
+    body("block-major")
+
+
+# ---- 1: mixed statuses and one class with most of the sample --------------------------------------
+@ENGINES
+def test_c3_mixed_statuses_and_contended_class(engine):
+    n = 4096
+    rows = scenario_rows(C3_TOP, C3_EVENTS, n)
+    assert rows.n_sids == 5
+    assert int((rows.status == O.FATAL_INSUFFICIENT_TOKENS).sum()) == 117   # the exclusion is exercised
+    whole = [expected(rows, sid, 0, n) for sid in range(5)]
+    assert [w[0][3] for w in whole] == [11, 15, 4, 2, 3]
+    # one class holds over half the sample (sids 2, 3, 4: 2330, 2719, 3458 of 3979): the contended slot
+    assert [2 * int(w[1]["count"][0]) > w[0][2] for w in whole] == [False, False, True, True, True]
+    sim = make_sim(C3_TOP, C3_EVENTS, n, engine)
+    ranges = [(0, n), (37, 3001)]
+    both_layouts(sim, engine, lambda what: check(sim, rows, ranges, what))
+    assert sim.census_time() > 0                                            # (10: the timing call)
+    # without class_of nothing per-instance is kept or returned
+    got = sim.snapshot_census(0)
+    assert got.class_of is None
+    assert_census_equal(got, whole[0], "no class_of")
+
+
+# ---- 2: many classes, truncation, and the workgroup table's overflow ---------------------------
+@ENGINES
+def test_many_classes_truncation_and_lds_overflow(engine):
+    n = 4096
+    rows = scenario_rows(TOP3, EVENTS3, n)
+    want = expected(rows, 0, 0, n)
+    counts = want[1]["count"]
+    assert want[0][3] == 413 and int((counts == 1).sum()) > 0              # singletons
+    assert (np.diff(counts[counts > 1]) == 0).any()                        # two classes of equal count
+    sim = make_sim(TOP3, EVENTS3, n, engine)
+
+    def body(what):
+        check(sim, rows, [(0, n)], what)
+        cut = [sim.snapshot_census(0, max_classes=16, class_of=True, lds_slots=s) for s in (0, 16, -1)]
+        for c in cut:
+            assert (c.n_returned, c.n_classes) == (16, 413) and int(c.class_of.max()) > 15
+            assert_census_equal(c, want, what + " cut", max_classes=16)
+            # 16 slots overflow in every workgroup: the fallback insert must give the same bytes
+            assert c.classes.tobytes() == cut[0].classes.tobytes()
+            assert c.class_of.tobytes() == cut[0].class_of.tobytes()
+        none = sim.snapshot_census(0, max_classes=0, class_of=True)
+        assert none.n_returned == 0 and none.n_classes == 413
+        assert np.array_equal(none.class_of, want[2])
+        for s in (64, 4096):
+            check(sim, rows, [(5, 3000)], f"{what} lds_slots {s}", lds_slots=s)
+
+    both_layouts(sim, engine, body)
+
+
+# ---- 3: node records of 3 words (not a power of two) --------------------------------------------
+def test_hub_three_word_records_instance_major():
+    n = 512
+    rows = scenario_rows(HUB_TOP, HUB_EVENTS, 4096)   # (instance i is seeded by i alone)
+    assert (rows.status == O.OK).all() and rows.n_sids == 4
+    sim = make_sim(HUB_TOP, HUB_EVENTS, n, AUTO)
+    sim.flush()
+    assert not sim.records_blocked()
+    check(sim, rows, [(0, n), (5, 300)], "hub after flush")
+
+
+def test_hub_three_word_records_block_major():
+    n = 4096
+    rows = scenario_rows(HUB_TOP, HUB_EVENTS, n)
+    assert [expected(rows, sid, 0, n)[0][3] for sid in range(4)] == [63, 51, 32, 16]
+    sim = make_sim(HUB_TOP, HUB_EVENTS, n, AUTO)
+    sim.flush()
+    replay_blocked(sim)
+    check(sim, rows, [(0, n), (37, 3001)], "hub after rerun")
+
+
+# ---- 4: incomplete but OK, and the state-image path -------------------------------------------
+@ENGINES
+def test_incomplete_ok_instances_and_resumed_program(engine):
+    n = 512
+    refs = []
+    for i in range(n):
+        r = O.OracleSim()
+        r.seed_go(O.REFERENCE_SEED + i)
+        assert r.read_topology_text(read_text("3nodes.top")) == 0
+        assert r.send_tokens("N1", "N2", 1) == 0 and r.send_tokens("N2", "N3", 2) == 0
+        assert r.start_snapshot("N1")[0] == 0
+        for _ in range(8):
+            r.tick()
+        refs.append(r)
+    rows = CensusRows(refs)
+    sample = expected(rows, 0, 0, n)[0][2]
+    assert (rows.status == O.OK).all() and 0 < sample < n
+    sim = make_sim("3nodes.top", None, n, engine)
+    sim.ProcessEvent(cl.PassTokenEvent("N1", "N2", 1))
+    sim.ProcessEvent(cl.PassTokenEvent("N2", "N3", 2))
+    assert sim.StartSnapshot("N1") == 0
+    sim.Tick(8)
+    got = sim.snapshot_census(0)        # executes the pending events, adds no tick
+    assert (got.instances, got.ok, got.sample) == (n, n, sample)
+    check(sim, rows, [(0, n), (3, 401)], "mid-program")
+    for r in refs:
+        for _ in range(8):
+            r.tick()
+    rows2 = CensusRows(refs)
+    sim.Tick(8)                         # resumes from the saved state image
+    check(sim, rows2, [(0, n)], "resumed")
+
+
+# ---- 5: empty samples --------------------------------------------------------------------------
+@ENGINES
+def test_empty_samples(engine):
+    n = 64
+    rows = scenario_rows("3nodes.top", EVENTS3, n)
+    assert (rows.status == O.FATAL_INSUFFICIENT_TOKENS).all()   # N3 starts with 0 tokens
+    sim = make_sim("3nodes.top", EVENTS3, n, engine)
+    flush_on(sim, engine)
+    for sid in range(2):
+        got = sim.snapshot_census(sid, class_of=True)
+        assert (got.instances, got.ok, got.sample, got.n_classes, got.n_returned) == (n, 0, 0, 0, 0)
+        assert (got.class_of == -1).all()
+    healthy = make_sim(TOP3, EVENTS3, n, engine)
+    flush_on(healthy, engine)
+    got = healthy.snapshot_census(0, 17, 17, class_of=True)
+    assert (got.instances, got.ok, got.sample, got.n_classes, got.n_returned) == (0, 0, 0, 0, 0)
+    assert got.class_of.size == 0
+    assert healthy.snapshot_census(0).sample == n
+
+
+# ---- 6: ragged sizes ------------------------------------------------------------------------------
+@ENGINES
+@pytest.mark.parametrize("n", [1, 63, 65, 257])
+def test_ragged_batch_sizes(n, engine):
+    rows = scenario_rows(TOP3, EVENTS3, 4096)   # (instance i is seeded by i alone)
+    sim = make_sim(TOP3, EVENTS3, n, engine)
+    flush_on(sim, engine)
+    for lds in (0, -1):
+        check(sim, rows, [(0, n)], f"n = {n} lds_slots {lds}", lds_slots=lds)
+
+
+# ---- 7: the hash-sum invariant; 8: merging sub-ranges ------------------------------------------
+@ENGINES
+def test_hash_sum_invariant_and_merge_of_sub_ranges(engine):
+    n = 4096
+    sim = make_sim(C3_TOP, C3_EVENTS, n, engine)
+
+    def body(what):
+        total = 0
+        for sid in range(5):
+            whole = sim.snapshot_census(sid)
+            assert whole.n_returned == whole.n_classes
+            total += sum(int(c) * int(k) for c, k in zip(whole.classes["count"], whole.classes["key"]))
+            for a in (1, 64, 1000):
+                parts = sim.snapshot_census(sid, 0, a).merge(sim.snapshot_census(sid, a, n))
+                assert parts == whole, f"{what}: merge at {a}"
+                # a census of [a, n) counts from 0 when it is another sim's shard: the offset
+                shifted = sim.snapshot_census(sid, a, n)
+                shifted.classes["first_inst"] -= a
+                assert sim.snapshot_census(sid, 0, a).merge(shifted, offset=a) == whole
+        hash_sum = int(sim.checksums()[cl.SUM_NAMES.index("snapshot_hash")])   # CL_SUM_SNAPSHOT_HASH
+        assert total % (1 << 64) == hash_sum % (1 << 64), what
+
+    both_layouts(sim, engine, body)
+
+
+# ---- 9: the representatives' contents ------------------------------------------------------------
+@ENGINES
+def test_representatives_contents(engine):
+    n = 4096
+    rows = scenario_rows(C3_TOP, C3_EVENTS, n)
+    sim = make_sim(C3_TOP, C3_EVENTS, n, engine)
+
+    def body(what):
+        for sid in (0, 1, 4):
+            census = sim.snapshot_census(sid)
+            reps = census.classes["first_inst"]
+            # a duplicate, descending order, and an instance outside the sample (a fatal one)
+            fatal = int(np.flatnonzero(rows.status != O.OK)[0])
+            insts = np.concatenate([reps[::-1], reps[:1], [fatal]])
+            tok, done, off, msg = sim.collect_snapshot_list(sid, insts)
+            ptok, pdone, poff, pmsg = sim.collect_snapshot_packed(sid)
+            ch = sim.num_channels
+            assert off.shape == (insts.size * ch + 1,) and off[0] == 0 and off[-1] == msg.size
+            for r, i in enumerate(insts):
+                i = int(i)
+                assert done[r] == pdone[i] and np.array_equal(tok[r], ptok[i]), f"{what} row {r}"
+                mine = [msg[off[r * ch + c]:off[r * ch + c + 1]].tolist() for c in range(ch)]
+                packed = [pmsg[poff[i * ch + c]:poff[i * ch + c + 1]].tolist() for c in range(ch)]
+                assert mine == packed, f"{what} row {r}: messages differ from the packed collect"
+                if i == fatal:
+                    continue
+                otok, ooff, ovals = rows.refs[i].collect_channels(sid)
+                assert done[r] and np.array_equal(tok[r], otok)
+                assert mine == [ovals[ooff[c]:ooff[c + 1]].tolist() for c in range(ch)], f"{what} row {r}: oracle"
+            snaps = census.snapshots(sim)
+            assert len(snaps) == census.n_returned
+            for k, snap in enumerate(snaps):
+                assert snap.id == sid and global_snapshot_key(sim, snap) == int(census.classes["key"][k])
+        empty = sim.collect_snapshot_list(0, [])
+        assert empty[0].shape == (0, sim.num_nodes) and empty[2].tolist() == [0] and empty[3].size == 0
+
+    both_layouts(sim, engine, body)
+
+
+# ---- the table's empty marker is a class like any other ----------------------------------------
+def test_key_equal_to_the_empty_marker(monkeypatch):
+    """Every key value is a legal class: with the table's empty marker moved onto the most frequent
+    key (and onto a singleton's), that class goes through the extra entry and nothing changes."""
+    n = 4096
+    rows = scenario_rows(TOP3, EVENTS3, n)
+    want = expected(rows, 0, 0, n)
+    sim = make_sim(TOP3, EVENTS3, n, AUTO)
+    sim.flush()
+    for marker in (int(want[1]["key"][0]), int(want[1]["key"][-1]), 0):
+        monkeypatch.setenv("CLSNAP_CENSUS_EMPTY_KEY", str(marker))
+        for lds in (0, 16, -1):
+            got = sim.snapshot_census(0, class_of=True, lds_slots=lds)
+            assert_census_equal(got, want, f"marker {marker:#x} lds_slots {lds}")
