@@ -1,5 +1,5 @@
 // cg_engine.h -- data layout shared by the graph engine's host runtime (cg_host.cpp)
-// and its gfx950 kernels (cg_kernels.hip).  DESIGN.md §10 draws the same layout.
+// and its gfx950 kernels (cg_kernels.hip, cg_table.hip).  DESIGN.md §10 draws the same layout.
 //
 // The graph engine runs ONE reference simulation over a large topology (BASELINE
 // configs 4 and 5: 2^20-node regular digraph, 100k-node power-law graph with 4,096
@@ -267,5 +267,11 @@ int cg_launch_finish(const GParams& p, int32_t n_sids, unsigned long long* out, 
 // out[1] in-flight token payloads, out[2] digest over completed snapshots,
 // out[3 + sid] = snapshot tokens + recorded token payloads of completed snapshot sid.
 int cg_launch_checks(const GParams& p, int32_t n_sids, unsigned long long* out, void* stream);
+// Per-snapshot summary table (cg_table.hip): rows[i] = the 16 int64 of cl_graph_snap_row
+// (clgraph.h) of snapshot sid_lo + i, i < n_sids, reduced over the owned nodes and the
+// in-positions [k_lo, k_hi) of the channels into them; in_ch[k] = channel of in-position k.
+// An init kernel and one grid-stride pass sized to n_cus compute units.
+int cg_launch_table(const GParams& p, const int32_t* in_ch, int32_t k_lo, int32_t k_hi, int32_t sid_lo,
+                    int32_t n_sids, long long* rows, int32_t n_cus, void* stream);
 
 }  // namespace clsnap

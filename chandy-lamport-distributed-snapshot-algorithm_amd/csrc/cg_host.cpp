@@ -181,6 +181,13 @@ struct cl_graph {
   GBuf<GOp> d_ops;
   GBuf<uint8_t> d_sched;
   GBuf<unsigned long long> d_scratch;
+  // per-snapshot summary table (cl_graph_snapshot_table): channel of every in-position, the
+  // device rows, the events around the latest call's kernels
+  GBuf<int32_t> d_in_ch;
+  GBuf<long long> d_table;
+  hipEvent_t tb_ev[2] = {nullptr, nullptr};
+  bool tb_timed = false;
+  int32_t n_cus = 0;
   size_t ops_uploaded = 0;
   // device event trace (cl_graph_trace_enable)
   int32_t trace_cap = 0;
@@ -220,6 +227,9 @@ struct cl_graph {
     d_outbox.release(); d_inbox.release(); d_out_n.release(); d_rmlist.release(); d_reports.release();
     d_rep_in.release(); d_trigv.release(); d_s0.release(); d_rdraw.release(); d_draw0.release();
     d_replies.release(); d_pop.release(); d_bk_cnt.release();
+    d_in_ch.release(); d_table.release();
+    for (auto& e : tb_ev)
+      if (e) (void)hipEventDestroy(e);
     for (auto& ev : ev_pool) {
       (void)hipEventDestroy(ev.first);
       (void)hipEventDestroy(ev.second);
@@ -419,6 +429,7 @@ struct cl_graph {
     GHIP(hipGetDeviceProperties(&prop, device));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
       return gerr(CL_E_DEVICE, "device %d is %s, the engine is built for gfx950", device, prop.gcnArchName);
+    n_cus = prop.multiProcessorCount;
     GHIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     own_stream = stream;
     dev_ready = true;
@@ -429,6 +440,11 @@ struct cl_graph {
     // sender's delivery word; out-degrees are below 256: kGMaxOutDegree)
     std::vector<uint8_t> in_oj((size_t)e);
     for (int64_t c = 0; c < e; ++c) in_oj[(size_t)ch_inpos[c]] = (uint8_t)(c - out_off[ch_src[c]]);
+    // channel of every in-position (the inverse of ch_inpos): the summary table walks the
+    // in-positions and needs the channel for the digest
+    std::vector<int32_t> in_ch((size_t)e);
+    for (int64_t c = 0; c < e; ++c) in_ch[(size_t)ch_inpos[c]] = (int32_t)c;
+    if ((rc = d_in_ch.upload(in_ch))) return rc;
     if ((rc = d_out_off.upload(out_off)) || (rc = d_route.upload(route)) || (rc = d_in_off.upload(in_off)) ||
         (rc = d_in_src.upload(in_src)) || (rc = d_in_oj.upload(in_oj)) || (rc = d_init_tok.upload(init_tok)))
       return rc;
@@ -1486,6 +1502,42 @@ int cl_graph_get_checksums(cl_graph* g, int64_t* out) {
   out[CL_GSUM_FINAL_RESIDUAL] = fin < 0 ? -fin : fin;
   out[CL_GSUM_DIGEST] = (int64_t)r[2];
   out[CL_GSUM_IN_FLIGHT] = (int64_t)r[1];
+  return CL_OK;
+}
+
+int cl_graph_snapshot_table(cl_graph* g, int32_t sid_lo, int32_t sid_hi, cl_graph_snap_row* rows) {
+  G_CHECK(g);
+  static_assert(sizeof(cl_graph_snap_row) == 16 * sizeof(int64_t), "cl_graph_snap_row is 16 x int64");
+  if (sid_lo < 0 || sid_lo > sid_hi || sid_hi > g->n_sids)
+    return gerr(CL_E_INVALID, "snapshot range [%d, %d) outside [0, %d]", sid_lo, sid_hi, g->n_sids);
+  const int32_t ns = sid_hi - sid_lo;
+  if (ns == 0) return CL_OK;
+  if (!rows) return gerr(CL_E_INVALID, "null output");
+  int rc = g->flush();
+  if (rc) return rc;
+  if ((rc = g->d_table.ensure((size_t)ns * 16))) return rc;
+  for (auto& e : g->tb_ev)
+    if (!e) GHIP(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+  g->tb_timed = false;
+  GHIP(hipEventRecord(g->tb_ev[0], g->stream));
+  // the in-CSR range of the owned nodes (all of them outside the partitioned mode)
+  const int32_t k_lo = g->in_off[(size_t)g->P.part_lo], k_hi = g->in_off[(size_t)g->P.part_hi];
+  if ((rc = g->k_err(cg_launch_table(g->P, g->d_in_ch.p, k_lo, k_hi, sid_lo, ns, g->d_table.p, g->n_cus, g->stream))))
+    return rc;
+  GHIP(hipEventRecord(g->tb_ev[1], g->stream));
+  GHIP(hipMemcpyAsync(rows, g->d_table.p, (size_t)ns * sizeof(cl_graph_snap_row), hipMemcpyDeviceToHost, g->stream));
+  GHIP(hipStreamSynchronize(g->stream));
+  g->tb_timed = true;
+  return CL_OK;
+}
+
+int cl_graph_table_time(cl_graph* g, double* ms) {
+  G_CHECK(g);
+  if (!ms) return gerr(CL_E_INVALID, "null output");
+  if (!g->tb_timed) return gerr(CL_E_STATE, "no snapshot table has been computed");
+  float f = 0.f;
+  GHIP(hipEventElapsedTime(&f, g->tb_ev[0], g->tb_ev[1]));
+  *ms = f;
   return CL_OK;
 }
 

@@ -17,6 +17,12 @@ from . import (ClSnapError, GlobalSnapshot, MsgSnapshot, PassTokenEvent, Snapsho
 
 GSUM_NAMES = ("ok", "delivered", "completed", "cut_residual", "final_residual", "digest", "in_flight")
 
+# cl_graph_snap_row (include/clgraph.h): one 128-byte row per snapshot id.
+SNAP_ROW_FIELDS = ("sid", "initiator", "start_tick", "complete_tick", "nodes_created", "last_create_tick",
+                   "node_tokens", "min_node_tokens", "max_node_tokens", "rec_msgs", "rec_tokens", "rec_channels",
+                   "max_ch_msgs", "digest")
+SNAP_ROW_DTYPE = np.dtype([(f, np.int64) for f in SNAP_ROW_FIELDS] + [("reserved", np.int64, (2,))])
+
 _SIGS = None
 
 
@@ -73,6 +79,8 @@ def glib():
             "cl_graph_collect_snapshot": [vp, i32, vp, vp, vp, i64],
             "cl_graph_get_counters": [vp, vp],
             "cl_graph_get_checksums": [vp, vp],
+            "cl_graph_snapshot_table": [vp, i32, i32, vp],
+            "cl_graph_table_time": [vp, vp],
             "cl_graph_part_begin": [vp, i32, i32],
             "cl_graph_part_snapshot": [vp, i32, vp],
             "cl_graph_part_pick": [vp, vp, i64, vp],
@@ -101,6 +109,76 @@ def glib():
 def counter_hash(seed, a, b):
     """The synthetic workloads' counter hash (cg_hash, cg_engine.h)."""
     return glib().cl_counter_hash(seed, a, b)
+
+
+class SnapshotTable:
+    """Per-snapshot summary rows (SNAP_ROW_DTYPE) of GraphSim.snapshot_table, reduced on the
+    device: when each snapshot started and completed, how far its marker wave got, what it
+    recorded, and its term of the content digest."""
+
+    _SUMS = ("nodes_created", "node_tokens", "rec_msgs", "rec_tokens", "rec_channels", "digest")
+    _CHANNEL = ("rec_msgs", "rec_tokens", "rec_channels", "max_ch_msgs", "digest")
+
+    def __init__(self, rows):
+        self.rows = np.ascontiguousarray(rows, dtype=SNAP_ROW_DTYPE).reshape(-1)
+
+    def __len__(self):
+        return self.rows.size
+
+    def __eq__(self, other):
+        return isinstance(other, SnapshotTable) and np.array_equal(self.rows, other.rows)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"SnapshotTable({self.rows!r})"
+
+    def _since_start(self, field):
+        a, b = self.rows[field], self.rows["start_tick"]
+        return np.where((a < 0) | (b < 0), np.int64(-1), a - b)
+
+    @property
+    def latency(self):
+        """complete_tick - start_tick per row; -1 where either is -1."""
+        return self._since_start("complete_tick")
+
+    @property
+    def spread(self):
+        """last_create_tick - start_tick per row (how long the marker wave has run); -1 where
+        either is -1."""
+        return self._since_start("last_create_tick")
+
+    def cut_residual(self, total_tokens):
+        """|node_tokens + rec_tokens - total| per row (the consistency of its cut); 0 where the
+        snapshot is not complete.  Its sum is the run's CL_GSUM_CUT_RESIDUAL."""
+        r = self.rows
+        d = np.abs(r["node_tokens"] + r["rec_tokens"] - np.int64(total_tokens))
+        return np.where(r["complete_tick"] >= 0, d, np.int64(0))
+
+    def digest_sum(self):
+        """The rows' digests summed modulo 2^64, as an int64: CL_GSUM_DIGEST over all sids."""
+        return int(self.rows["digest"].astype(np.uint64).sum(dtype=np.uint64).astype(np.int64))
+
+    def merge(self, other):
+        """The table of two parts of one partitioned run (the same sids in the same order):
+        sums add, extremes combine, the one part that owns the initiator reports it and the
+        start; a snapshot some part has not completed is incomplete, and its channel fields
+        and digest are 0."""
+        a, b = self.rows, other.rows
+        if a.shape != b.shape or not np.array_equal(a["sid"], b["sid"]):
+            raise ValueError("merge needs tables of the same snapshot ids in the same order")
+        out = a.copy()
+        with np.errstate(over="ignore"):
+            for f in self._SUMS:
+                out[f] = (a[f].astype(np.uint64) + b[f].astype(np.uint64)).astype(np.int64)
+        for f in ("initiator", "start_tick", "last_create_tick", "max_node_tokens", "max_ch_msgs"):
+            out[f] = np.maximum(a[f], b[f])
+        out["min_node_tokens"] = np.minimum(a["min_node_tokens"], b["min_node_tokens"])
+        done = (a["complete_tick"] >= 0) & (b["complete_tick"] >= 0)
+        out["complete_tick"] = np.where(done, np.maximum(a["complete_tick"], b["complete_tick"]), np.int64(-1))
+        for f in self._CHANNEL:
+            out[f] = np.where(done, out[f], np.int64(0))
+        return SnapshotTable(out)
 
 
 class GraphSim:
@@ -332,6 +410,19 @@ class GraphSim:
         out = np.zeros(len(GSUM_NAMES), dtype=np.int64)
         _check(self._L.cl_graph_get_checksums(self._h, _p(out)))
         return dict(zip(GSUM_NAMES, out.tolist()))
+
+    def snapshot_table(self, sid_lo=0, sid_hi=None):
+        """SnapshotTable of the snapshots [sid_lo, sid_hi) (default: all), reduced on the
+        device in one pass (cl_graph_snapshot_table): 128 bytes per snapshot reach the host."""
+        if sid_hi is None:
+            sid_hi = self.num_snapshots
+        rows = np.zeros(max(sid_hi - sid_lo, 0), dtype=SNAP_ROW_DTYPE)
+        _check(self._L.cl_graph_snapshot_table(self._h, sid_lo, sid_hi, _p(rows) if rows.size else None))
+        return SnapshotTable(rows)
+
+    def table_time(self):
+        """Device ms of the latest snapshot_table call's kernels (HIP events)."""
+        return self._get(self._L.cl_graph_table_time, C.c_double)
 
     # ---- device event trace: the reference's debug Logger (logger.go:12-76) ------------
     def trace_enable(self, capacity=1 << 16):
@@ -573,6 +664,18 @@ class PartitionedGraphSim:
                 return True
             self.tick()
         return False
+
+    def snapshot_table(self):
+        """The whole run's SnapshotTable on every rank: the parts' tables (each rank's nodes and
+        the channels into them), all-gathered and merged."""
+        mine = self.g.snapshot_table(0, self.n_sids)
+        words = mine.rows.view(np.int64).ravel()
+        allw = self.D.allgather_ints(words.tolist() or [0], self.dev)[:, :words.size]
+        parts = [SnapshotTable(np.ascontiguousarray(w).view(SNAP_ROW_DTYPE)) for w in allw]
+        out = parts[0]
+        for t in parts[1:]:
+            out = out.merge(t)
+        return out
 
     def results(self):
         """(status, final tokens[n], completion ticks, counters, {sid: (tokens[n], offsets,

@@ -152,6 +152,40 @@ int cl_graph_collect_snapshot(cl_graph* g, int32_t sid, int64_t* tokens, int64_t
 int cl_graph_get_counters(cl_graph* g, int64_t* out /* [CL_NUM_COUNTERS] */);
 int cl_graph_get_checksums(cl_graph* g, int64_t* out /* [CL_NUM_GSUMS] */);
 
+/* ---- per-snapshot summary table, reduced on the device ---------------------------
+ * One row per snapshot id of [sid_lo, sid_hi): one pass over the snapshot planes, and
+ * (sid_hi - sid_lo) x 128 B cross to the host -- against one cl_graph_collect_snapshot
+ * (N token words, E cursors and the payload history) per snapshot.  Epochs are the
+ * reference Logger's (logger.go:12-76): start_tick is the epoch of the snapshot's
+ * CL_LOG_START_SNAPSHOT record, a node's creation epoch that of the first
+ * CL_LOG_RECV_MARKER of the snapshot delivered to it (the initiator's: start_tick).
+ * The node fields cover the local snapshots created so far; the channel fields and the
+ * digest are taken from completed snapshots only.  The digests of all rows sum (mod 2^64)
+ * to CL_GSUM_DIGEST.  Partitioned runs: this device's part -- its nodes, the channels
+ * into them, completion over its nodes. */
+typedef struct cl_graph_snap_row {   /* 16 x int64 = 128 B */
+  int64_t sid;
+  int64_t initiator;        /* rank of the StartSnapshot node; -1 if this device does not own it (partitioned) */
+  int64_t start_tick;       /* Logger epoch of its StartSnapshot record; -1 likewise */
+  int64_t complete_tick;    /* cl_graph_snapshot_tick; -1 = not complete */
+  int64_t nodes_created;    /* local snapshots created so far (== N when complete, unpartitioned) */
+  int64_t last_create_tick; /* largest creation epoch over created nodes; -1 if none */
+  int64_t node_tokens;      /* sum of the recorded node tokens over created nodes */
+  int64_t min_node_tokens;  /* INT64_MAX if no node created */
+  int64_t max_node_tokens;  /* INT64_MIN if no node created */
+  int64_t rec_msgs;         /* recorded messages over all channels   -- complete snapshots only, else 0 */
+  int64_t rec_tokens;       /* their token payloads                   -- " */
+  int64_t rec_channels;     /* channels with at least one recorded message -- " */
+  int64_t max_ch_msgs;      /* most messages recorded on one channel  -- " */
+  int64_t digest;           /* this snapshot's term of CL_GSUM_DIGEST -- ", else 0 */
+  int64_t reserved[2];      /* 0 */
+} cl_graph_snap_row;
+/* CL_E_INVALID unless 0 <= sid_lo <= sid_hi <= num_snapshots, or on a null `rows` with a
+ * non-empty range; an empty range returns CL_OK and launches nothing. */
+int cl_graph_snapshot_table(cl_graph* g, int32_t sid_lo, int32_t sid_hi, cl_graph_snap_row* rows /* [sid_hi - sid_lo] */);
+/* Device ms of the latest table call's kernels (HIP events on the engine's stream). */
+int cl_graph_table_time(cl_graph* g, double* ms);
+
 /* ---- device event trace: the reference's debug Logger (logger.go:12-76) ---------- */
 /* Record up to `capacity` LogEvents from the next run on (0 = off, the default); the next
  * flush replays the program with tracing.  A debugging aid: records go through one device
