@@ -18,7 +18,8 @@ import os
 
 import numpy as np
 
-__all__ = ["ChandyLamportSim", "SnapshotStats", "STATS_LAYOUT_FIELDS", "GlobalSnapshot", "MsgSnapshot", "PassTokenEvent", "SnapshotEvent",
+__all__ = ["ChandyLamportSim", "SnapshotStats", "STATS_LAYOUT_FIELDS", "SnapshotSelection", "SELECT_CLAUSE_DTYPE",
+"GlobalSnapshot", "MsgSnapshot", "PassTokenEvent", "SnapshotEvent",
            "ClSnapError", "lib", "go_delay_schedule", "go_int63", "go_intn", "REFERENCE_SEED",
            "INST_OK", "INST_FATAL_INSUFFICIENT_TOKENS", "INST_FATAL_UNKNOWN_DEST",
            "INST_FIFO_OVERFLOW", "INST_HANG", "INST_DELAY_EXHAUSTED", "COUNTER_NAMES",
@@ -128,6 +129,10 @@ def lib():
         "cl_snapshot_census": [vp, i32, i64, i64, vp, vp, vp, vp],
         "cl_census_time": [vp, vp],
         "cl_collect_snapshot_list": [vp, i32, vp, i64, vp, vp, vp, vp, i64, vp],
+        "cl_select_instances": [vp, i32, i64, i64, vp, i32, vp, vp, i64, vp],
+        "cl_select_time": [vp, vp],
+        "cl_select_stage_times": [vp, vp, vp],
+        "cl_snapshot_ticks": [vp, i32, i64, i64, vp],
     }
     for name, args in sig.items():
         if os.environ.get("CLSNAP_VARIANT") and not hasattr(L, name):
@@ -413,6 +418,109 @@ class SnapshotCensus:
     __hash__ = None
 
 
+# cl_select_clause (include/clsnap.h) and the CL_SEL_* field codes, by name
+SELECT_CLAUSE_DTYPE = np.dtype([("field", np.int32), ("index", np.int32), ("flags", np.int32),
+                                ("reserved", np.int32), ("lo", np.int64), ("hi", np.int64)])
+SELECT_FIELDS = ("tick", "msgs", "inflight", "node", "ch_msgs", "ch_tok", "key")
+SELECT_NOT = 1
+SELECT_MAX_CLAUSES = 8
+
+
+def _select_clauses(where, ids, chans):
+    """`where` of ChandyLamportSim.select_instances as a SELECT_CLAUSE_DTYPE array; ids = node ids
+    by rank, chans = (src rank, dest rank) per channel."""
+    where = list(where)
+    out = np.zeros(len(where), dtype=SELECT_CLAUSE_DTYPE)
+    i64 = np.iinfo(np.int64)
+    for q, clause in enumerate(where):
+        if len(clause) not in (4, 5) or (len(clause) == 5 and clause[4] != "not"):
+            raise ValueError(f"select clause {q}: (field, index, lo, hi) or (field, index, lo, hi, 'not')")
+        field, index, lo, hi = clause[:4]
+        if field not in SELECT_FIELDS:
+            raise ValueError(f"select clause {q}: field must be one of {SELECT_FIELDS}")
+        if field == "node":
+            if isinstance(index, str):
+                if index not in ids:
+                    raise ValueError(f"select clause {q}: no node {index!r}")
+                index = ids.index(index)
+        elif field in ("ch_msgs", "ch_tok"):
+            if isinstance(index, (tuple, list)):
+                pair = tuple(ids.index(x) if isinstance(x, str) and x in ids else x for x in index)
+                if pair not in chans:
+                    raise ValueError(f"select clause {q}: no channel {tuple(index)!r}")
+                index = chans.index(pair)
+        elif index is None:
+            index = 0
+        if index is None or isinstance(index, (str, tuple, list)):
+            raise ValueError(f"select clause {q}: {field!r} does not take index {index!r}")
+        if field == "key":
+            lo, hi = 0 if lo is None else int(lo), 2**64 - 1 if hi is None else int(hi)
+            if not (0 <= lo < 2**64 and 0 <= hi < 2**64):
+                raise ValueError(f"select clause {q}: key bounds are uint64 values")
+            lo, hi = (int(np.array(v, dtype=np.uint64).view(np.int64)) for v in (lo, hi))
+        else:
+            lo, hi = i64.min if lo is None else int(lo), i64.max if hi is None else int(hi)
+        out[q] = (SELECT_FIELDS.index(field), int(index), SELECT_NOT if len(clause) == 5 else 0, 0, lo, hi)
+    return out
+
+
+class SnapshotSelection:
+    """The result of ``ChandyLamportSim.select_instances``: the instances of the sample that
+    satisfy every clause.
+
+    ``instances``, ``ok`` and ``sample`` are those of snapshot_stats over the same range;
+    ``n_match`` counts all matches, ``insts`` (int64, ascending) holds the first ``n_returned`` of
+    them, ``ticks`` (int32, or None) their completion ticks; ``truncated`` says whether matches
+    were left out."""
+
+    def __init__(self, snapshot_id, instances, ok, sample, n_match, insts, ticks=None):
+        self.snapshot_id = int(snapshot_id)
+        self.instances, self.ok, self.sample, self.n_match = int(instances), int(ok), int(sample), int(n_match)
+        self.insts = np.ascontiguousarray(insts, dtype=np.int64).ravel()
+        self.ticks = None if ticks is None else np.ascontiguousarray(ticks, dtype=np.int32).ravel()
+        if self.ticks is not None and self.ticks.shape != self.insts.shape:
+            raise ValueError("SnapshotSelection: one tick per instance")
+
+    @property
+    def n_returned(self):
+        return int(self.insts.shape[0])
+
+    @property
+    def truncated(self):
+        return self.n_returned < self.n_match
+
+    def collect(self, sim):
+        """The contents of the selected instances: sim.collect_snapshot_list(snapshot_id, insts)."""
+        return sim.collect_snapshot_list(self.snapshot_id, self.insts)
+
+    def merge(self, other, offset=0):
+        """The selection over the union of two disjoint instance sets (other ranks, other ranges);
+        ``offset`` is added to ``other``'s instance indices.  The indices are concatenated and
+        sorted, the counts add; ticks are kept when both sides have them.  Raises ValueError when
+        either side is truncated or the snapshot ids differ."""
+        if not isinstance(other, SnapshotSelection) or other.snapshot_id != self.snapshot_id:
+            raise ValueError("SnapshotSelection.merge: not a selection of the same snapshot id")
+        if self.truncated or other.truncated:
+            raise ValueError("SnapshotSelection.merge: a truncated selection (n_returned < n_match) cannot be merged")
+        insts = np.concatenate([self.insts, other.insts + offset])
+        order = np.argsort(insts, kind="stable")
+        ticks = None
+        if self.ticks is not None and other.ticks is not None:
+            ticks = np.concatenate([self.ticks, other.ticks])[order]
+        return SnapshotSelection(self.snapshot_id, self.instances + other.instances, self.ok + other.ok,
+                                 self.sample + other.sample, self.n_match + other.n_match, insts[order], ticks)
+
+    def __eq__(self, other):
+        return (isinstance(other, SnapshotSelection) and self.snapshot_id == other.snapshot_id
+                and (self.instances, self.ok, self.sample, self.n_match)
+                == (other.instances, other.ok, other.sample, other.n_match)
+                and bool(np.array_equal(self.insts, other.insts))
+                and (self.ticks is None) == (other.ticks is None)
+                and (self.ticks is None or bool(np.array_equal(self.ticks, other.ticks))))
+
+    __hash__ = None
+
+
 class ChandyLamportSim:
     """A batch of ``n_instances`` reference simulators (sim.go ChandyLamportSim).
 
@@ -612,6 +720,61 @@ class ChandyLamportSim:
         ms = C.c_double(0)
         _check(self._L.cl_census_time(self._h, C.byref(ms)))
         return ms.value
+
+    def select_clauses(self, where):
+        """`where` of select_instances as a SELECT_CLAUSE_DTYPE array (host only): node ids and
+        (src_id, dest_id) pairs mapped to ranks and channel numbers, None bounds opened, keys as
+        uint64 bit patterns."""
+        return _select_clauses(where, self.node_ids(), self.channels())
+
+    def select_instances(self, snapshot_id, where=(), inst_lo=0, inst_hi=None, max_out=None, ticks=False):
+        """The OK instances of [inst_lo, inst_hi) in which snapshot `snapshot_id` completed and that
+        satisfy every clause of `where`, found on the GPU (cl_select_instances): a
+        SnapshotSelection with the ascending instance indices.  A clause is (field, index, lo, hi)
+        or (field, index, lo, hi, "not"): field one of SELECT_FIELDS; index None, a node id or
+        rank ("node"), a channel number or (src_id, dest_id) pair ("ch_msgs", "ch_tok"); lo and
+        hi inclusive, None for an open end.  max_out=None counts first and fetches every match;
+        else at most max_out indices are returned (the smallest).  ticks=True also returns the
+        completion ticks."""
+        hi = self.n_instances if inst_hi is None else inst_hi
+        clauses = self.select_clauses(where)
+        info = np.zeros(5, dtype=np.int64)
+
+        def call(cap):
+            insts = np.zeros(max(cap, 0), dtype=np.int64)
+            tk = np.zeros(max(cap, 0), dtype=np.int32) if ticks else None
+            _check(self._L.cl_select_instances(self._h, snapshot_id, inst_lo, hi, _p(clauses) if clauses.size else None,
+                                               clauses.size, _p(insts) if cap > 0 else None,
+                                               _p(tk) if ticks and cap > 0 else None, cap, _p(info)))
+            k = int(info[4])
+            return insts[:k].copy(), None if tk is None else tk[:k].copy()
+
+        if max_out is None:
+            call(0)
+            insts, tk = call(int(info[3]))
+        else:
+            insts, tk = call(max_out)
+        instances, ok, sample, n_match, _ = info.tolist()
+        return SnapshotSelection(snapshot_id, instances, ok, sample, n_match, insts, tk)
+
+    def select_time(self, stages=False):
+        """Device ms of the latest select_instances kernels, both stages; stages=True: the pair
+        (evaluate ms, compact ms)."""
+        if stages:
+            a, b = C.c_double(0), C.c_double(0)
+            _check(self._L.cl_select_stage_times(self._h, C.byref(a), C.byref(b)))
+            return a.value, b.value
+        ms = C.c_double(0)
+        _check(self._L.cl_select_time(self._h, C.byref(ms)))
+        return ms.value
+
+    def snapshot_ticks(self, snapshot_id, inst_lo=0, inst_hi=None):
+        """Completion tick of snapshot `snapshot_id` in every instance of [inst_lo, inst_hi)
+        (int32, -1 = not complete): the bulk form of snapshot_tick (cl_snapshot_ticks)."""
+        hi = self.n_instances if inst_hi is None else inst_hi
+        out = np.full(max(hi - inst_lo, 0), -1, dtype=np.int32)
+        _check(self._L.cl_snapshot_ticks(self._h, snapshot_id, inst_lo, hi, _p(out)))
+        return out
 
     def collect_snapshot_list(self, snapshot_id, insts):
         """collect_snapshot_packed over an instance list (cl_collect_snapshot_list): row r is

@@ -175,16 +175,7 @@ __global__ __launch_bounds__(kCensusThreads) void cl_census_keys(CensusParams p)
       const int32_t v = idx / rw;
       return src[((size_t)v * 64 + lane) * rw + (idx - v * rw)];
     };
-    uint64_t h = 0x9E3779B97F4A7C15ULL ^ (uint64_t)p.sid;
-    for (int32_t v = 0; v < N; ++v) h = mix64(h ^ (uint64_t)(int64_t)(int32_t)rb(v * rw));
-    for (int32_t c = 0; c < p.n_ch; ++c) {
-      const uint32_t rec = rb(p.ch_slot[c]);
-      const uint32_t b = rec & 0xffffu, e = rec >> 16;
-      h = mix64(h ^ ((uint64_t)c << 32) ^ (uint64_t)(e - b));
-      const int32_t* hv = p.hist_val + p.hist_off[c];
-      for (uint32_t k = b; k < e; ++k) h = mix64(h ^ (uint64_t)(int64_t)hv[k]);
-    }
-    const unsigned long long key = h;
+    const unsigned long long key = snapshot_key(p.sid, N, rw, p.n_ch, p.ch_slot, p.hist_off, p.hist_val, rb);
     if (p.keys) {
       p.keys[inst - p.lo] = key;
       p.class_of[inst - p.lo] = 0;

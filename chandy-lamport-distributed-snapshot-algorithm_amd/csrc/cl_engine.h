@@ -577,5 +577,79 @@ inline uint64_t mix64(uint64_t z) {
   z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
   return z ^ (z >> 31);
 }
+// The content hash of snapshot `sid` of one instance -- the census key, cl_checksum_kernel's
+// per-snapshot term: the N token words, then per channel (channel order) its message count and
+// recorded tokens.  word(idx) reads word idx of the instance's N * rw record words.
+template <class Word>
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint64_t snapshot_key(int32_t sid, int32_t n_nodes, int32_t rw, int32_t n_ch, const int32_t* ch_slot,
+                             const int32_t* hist_off, const int32_t* hist_val, Word word) {
+  uint64_t h = 0x9E3779B97F4A7C15ULL ^ (uint64_t)sid;
+  for (int32_t v = 0; v < n_nodes; ++v) h = mix64(h ^ (uint64_t)(int64_t)(int32_t)word(v * rw));
+  for (int32_t c = 0; c < n_ch; ++c) {
+    const uint32_t rec = word(ch_slot[c]);
+    const uint32_t b = rec & 0xffffu, e = rec >> 16;
+    h = mix64(h ^ ((uint64_t)c << 32) ^ (uint64_t)(e - b));
+    const int32_t* hv = hist_val + hist_off[c];
+    for (uint32_t k = b; k < e; ++k) h = mix64(h ^ (uint64_t)(int64_t)hv[k]);
+  }
+  return h;
+}
+
+// ---- instance selection by snapshot predicate (cl_select.hip; include/clsnap.h cl_select_instances) ----
+// A conjunction of range clauses over the per-instance quantities the statistics reduce, evaluated
+// over the sample of cl_snapshot_stats; the matches come back as ascending instance indices.
+enum : int32_t {
+  SEL_TICK = 0, SEL_MSGS = 1, SEL_INFLIGHT = 2, SEL_NODE = 3, SEL_CH_MSGS = 4, SEL_CH_TOK = 5, SEL_KEY = 6,
+  SEL_NUM_FIELDS = 7,
+};
+constexpr int32_t kSelNot = 1;
+constexpr int32_t kSelMaxClauses = 8;
+constexpr int32_t kSelThreads = 256;
+// Words (64 verdict bits each) one workgroup of the compaction counts and fills: one per thread.
+constexpr int32_t kSelBlockWords = kSelThreads;
+struct SelectClause {  // the layout of cl_select_clause
+  int32_t field, index, flags, reserved;
+  int64_t lo, hi;
+};
+struct SelectParams {
+  int32_t n_nodes, n_ch, s_cap, rw, sid;
+  int64_t n_inst, stride;
+  int64_t lo, hi;            // the sample's instance range
+  int64_t tile_lo, tile_hi;  // 64-slot tiles to walk (as StatsParams)
+  const int32_t* regs;
+  const int32_t* snap_tick;
+  const uint32_t* snap_nod;
+  int32_t blocked;           // records block-major by slot (rec_word)
+  const int32_t* inst_map;   // slot -> instance of a block-major replay (nullptr: identity)
+  const int32_t* ch_slot;    // [C] record word of channel c
+  const int32_t* hist_off;   // [C + 1]
+  const int32_t* hist_val;
+  const long long* hist_pre; // as StatsParams::hist_pre
+  int32_t staged;            // N * rw <= kCensusStageWords: records staged in LDS
+  int32_t n_clauses;
+  int32_t need_records;      // a clause reads the records (any field but SEL_TICK)
+  int32_t need_totals;       // a clause names SEL_MSGS or SEL_INFLIGHT
+  int32_t need_key;          // a clause names SEL_KEY
+  SelectClause clause[kSelMaxClauses];
+  // Verdict bitmap: bit (inst - base) & 63 of word (inst - base) >> 6, base = lo rounded down to a
+  // multiple of 64 (so an instance-major tile is one word).  Block-major: zeroed before the pass.
+  int64_t base, words;
+  unsigned long long* bitmap;  // [words]
+  unsigned long long* info;    // instances, ok, sample, n_match
+  // compaction: block b counts / fills words [b * kSelBlockWords, ...)
+  long long* bsum;             // [ceil(words / kSelBlockWords)] block totals -> exclusive prefix
+  int64_t cap;                 // entries of out (and ticks) the fill may write
+  long long* out;              // [cap] matching instances, ascending
+  int32_t* ticks;              // [cap] their completion ticks, or nullptr
+};
+inline int32_t select_lds_bytes(bool staged) {
+  return 4 * 8 + (staged ? kWavesPerBlock * kStatsStageWords * 4 : 0);
+}
+int launch_select_eval(const SelectParams& p, int32_t blocks, void* stream);
+// count + scan (n_match left in p.info[3]), then the fill of the first p.cap matches
+int launch_select_compact(const SelectParams& p, void* stream);
 
 }  // namespace clsnap

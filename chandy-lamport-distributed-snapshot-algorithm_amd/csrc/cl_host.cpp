@@ -390,6 +390,12 @@ struct cl_sim {
   DevBuf<long long> d_pk_list;  // instance list of cl_collect_snapshot_list
   hipEvent_t cs_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int32_t cs_timed = 0;  // event pairs of the latest census (0: none has run)
+  // instance selection (cl_select_instances, cl_select.hip): verdict bitmap, block sums, output
+  DevBuf<unsigned long long> d_sel_bits, d_sel_info;
+  DevBuf<long long> d_sel_bsum, d_sel_out;
+  DevBuf<int32_t> d_sel_ticks;
+  hipEvent_t sel_ev[3] = {nullptr, nullptr, nullptr};  // start, evaluated, compacted
+  bool sel_timed = false;
   size_t hist_uploaded = (size_t)-1;  // history entries on the device
 
   ~cl_sim() {
@@ -407,6 +413,9 @@ struct cl_sim {
       d_word_ch.release(); d_hist_pre.release(); d_stats.release();
       d_cs_table.release(); d_cs_out.release(); d_cs_list.release(); d_cs_info.release(); d_cs_keys.release();
       d_cs_class.release(); d_cs_rank.release(); d_pk_list.release();
+      d_sel_bits.release(); d_sel_info.release(); d_sel_bsum.release(); d_sel_out.release(); d_sel_ticks.release();
+      for (auto& e : sel_ev)
+        if (e) (void)hipEventDestroy(e);
       for (auto& e : cs_ev)
         if (e) (void)hipEventDestroy(e);
       for (auto& e : pk_ev)
@@ -1365,6 +1374,111 @@ struct cl_sim {
     return CL_OK;
   }
 
+  // cl_select_instances (arguments checked by the caller): the instances of the sample of
+  // snapshot sid over [lo, hi) that satisfy every clause, ascending, the first `cap` of them into
+  // insts (and their completion ticks into ticks).  Both stages are enqueued back to back; the
+  // host waits once, for the info, then copies the n_returned entries.
+  int select(int32_t sid, int64_t lo, int64_t hi, const cl_select_clause* clauses, int32_t n_clauses, int64_t* insts,
+             int32_t* ticks, int64_t cap, cl_select_info* info) {
+    int rc = flush();
+    if (rc) return rc;
+    if (!dev_ready) return set_err(CL_E_STATE, "nothing has run on the device yet");
+    HIP_TRY(hipSetDevice(device));
+    if ((rc = upload_hist())) return rc;
+    if (!n_cus) HIP_TRY(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device));
+    for (auto& e : sel_ev)
+      if (!e) HIP_TRY(hipEventCreate(&e));
+    *info = cl_select_info{};
+    const int64_t n = hi - lo;
+    if (n == 0) return CL_OK;
+    SelectParams p{};
+    p.n_nodes = (int32_t)ids.size();
+    p.n_ch = (int32_t)ch_dst.size();
+    p.s_cap = s_cap;
+    p.rw = lay.rw;
+    p.sid = sid;
+    p.n_inst = n_inst;
+    p.stride = stride;
+    p.lo = lo;
+    p.hi = hi;
+    p.regs = d_regs.p;
+    p.snap_tick = d_snap_tick.p;
+    p.snap_nod = d_snap_nod.p;
+    p.blocked = rec_blocked ? 1 : 0;
+    p.inst_map = rec_blocked && rec_slot_gen != -2 ? d_map.p : nullptr;  // (as stats())
+    p.ch_slot = d_ch_slot.p;
+    p.hist_off = d_hist.p;
+    p.hist_val = d_hist.p + hist.size() + 1;
+    p.hist_pre = d_hist_pre.p;
+    p.staged = p.n_nodes * p.rw <= kCensusStageWords ? 1 : 0;
+    p.n_clauses = n_clauses;
+    for (int32_t q = 0; q < n_clauses; ++q) {
+      std::memcpy(&p.clause[q], &clauses[q], sizeof(SelectClause));
+      const int32_t f = clauses[q].field;
+      p.need_records |= f != SEL_TICK;
+      p.need_totals |= f == SEL_MSGS || f == SEL_INFLIGHT;
+      p.need_key |= f == SEL_KEY;
+    }
+    p.tile_lo = rec_blocked ? 0 : lo / kWave;
+    p.tile_hi = rec_blocked ? stride / kWave : (hi + kWave - 1) / kWave;
+    p.base = lo / kWave * kWave;
+    p.words = (hi - p.base + kWave - 1) / kWave;
+    p.cap = std::min(cap, n);
+    const int64_t n_blocks = (p.words + kSelBlockWords - 1) / kSelBlockWords;
+    if ((rc = d_sel_bits.ensure((size_t)p.words)) || (rc = d_sel_bsum.ensure((size_t)n_blocks)) ||
+        (rc = d_sel_info.ensure(4)) || (rc = d_sel_out.ensure((size_t)std::max<int64_t>(p.cap, 1))))
+      return rc;
+    if (ticks && (rc = d_sel_ticks.ensure((size_t)std::max<int64_t>(p.cap, 1)))) return rc;
+    p.bitmap = d_sel_bits.p;
+    p.info = d_sel_info.p;
+    p.bsum = d_sel_bsum.p;
+    p.out = d_sel_out.p;
+    p.ticks = ticks ? d_sel_ticks.p : nullptr;
+    const int64_t tiles = p.tile_hi - p.tile_lo;
+    const int32_t per_cu = stats_blocks_per_cu(select_lds_bytes(p.staged && p.need_records));
+    const int32_t blocks = (int32_t)std::min<int64_t>((tiles + kWavesPerBlock - 1) / kWavesPerBlock,
+                                                      (int64_t)per_cu * std::max(n_cus, 1));
+    HIP_TRY(hipEventRecord(sel_ev[0], stream));
+    HIP_TRY(hipMemsetAsync(d_sel_info.p, 0, 4 * sizeof(unsigned long long), stream));
+    // block-major: the lanes OR their bits in; instance-major: every word is stored
+    if (rec_blocked) HIP_TRY(hipMemsetAsync(d_sel_bits.p, 0, (size_t)p.words * sizeof(unsigned long long), stream));
+    int e = launch_select_eval(p, blocks, stream);
+    if (e) return set_err(CL_E_DEVICE, "select kernels: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipEventRecord(sel_ev[1], stream));
+    if ((e = launch_select_compact(p, stream)))
+      return set_err(CL_E_DEVICE, "select kernels: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipEventRecord(sel_ev[2], stream));
+    unsigned long long h[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, d_sel_info.p, sizeof h, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    sel_timed = true;
+    if ((int64_t)h[3] > n)
+      return set_err(CL_E_DEVICE, "select: %lld matches of %lld instances", (long long)h[3], (long long)n);
+    info->instances = (int64_t)h[0], info->ok = (int64_t)h[1], info->sample = (int64_t)h[2];
+    info->n_match = (int64_t)h[3];
+    info->n_returned = std::min<int64_t>(info->n_match, cap);
+    if (info->n_returned > 0) {
+      const size_t k = (size_t)info->n_returned;
+      HIP_TRY(hipMemcpyAsync(insts, d_sel_out.p, k * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+      if (ticks) HIP_TRY(hipMemcpyAsync(ticks, d_sel_ticks.p, k * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+    }
+    return CL_OK;
+  }
+
+  // cl_snapshot_ticks: the snap_tick column of snapshot sid over [lo, hi), one strided copy.
+  int ticks_of(int32_t sid, int64_t lo, int64_t hi, int32_t* out) {
+    int rc = flush();
+    if (rc) return rc;
+    if (!dev_ready) return set_err(CL_E_STATE, "nothing has run on the device yet");
+    if (hi == lo) return CL_OK;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpy2D(out, sizeof(int32_t), d_snap_tick.p + (size_t)lo * s_cap + sid, s_cap * sizeof(int32_t),
+                        sizeof(int32_t), (size_t)(hi - lo), hipMemcpyDeviceToHost));
+    return CL_OK;
+  }
+
   int append(Op op) {
     int rc = freeze();
     if (rc) return rc;
@@ -1842,6 +1956,8 @@ int cl_device_bytes(const cl_sim* sim, int64_t* bytes) {
   b += sim->d_ops.n * sizeof(Op) + sim->d_topo.n * 4 + sim->d_sched.n + sim->d_state.n * 4 + sim->d_regs.n * 4;
   b += sim->d_snap_nod.n * 4 + sim->d_snap_tick.n * 4 + sim->d_ovf.n * 4;
   b += sim->d_ovh.n * 4 + sim->d_hist.n * 4 + sim->d_sums.n * 8 + sim->d_fin_tok.n * 4;
+  b += sim->d_sel_bits.n * 8 + sim->d_sel_info.n * 8 + sim->d_sel_bsum.n * 8 + sim->d_sel_out.n * 8 +
+       sim->d_sel_ticks.n * 4;  // (the selection's scratch, once a selection has run)
   *bytes = b;
   return CL_OK;
 }
@@ -2136,6 +2252,65 @@ int cl_census_time(cl_sim* sim, double* device_ms) {
   }
   *device_ms = ms;
   return CL_OK;
+}
+
+static_assert(sizeof(cl_select_clause) == sizeof(SelectClause) && sizeof(SelectClause) == 32,
+              "cl_select_clause mirrors SelectClause");
+static_assert(CL_SELECT_MAX_CLAUSES == kSelMaxClauses && CL_SEL_KEY == SEL_KEY && CL_SEL_NOT == kSelNot,
+              "CL_SEL_* mirror cl_engine.h");
+
+int cl_select_instances(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_select_clause* clauses,
+                        int32_t n_clauses, int64_t* insts, int32_t* ticks, int64_t cap, cl_select_info* info) {
+  SIM_CHECK(sim);
+  // every argument is checked before any device work
+  if (!info) return set_err(CL_E_INVALID, "null select info");
+  if (n_clauses < 0 || n_clauses > CL_SELECT_MAX_CLAUSES || (n_clauses > 0 && !clauses))
+    return set_err(CL_E_INVALID, "select: 0 <= n_clauses <= %d, with a clause array", CL_SELECT_MAX_CLAUSES);
+  const int64_t N = (int64_t)sim->ids.size(), Cn = (int64_t)sim->links.size();
+  for (int32_t q = 0; q < n_clauses; ++q) {
+    const cl_select_clause& z = clauses[q];
+    if (z.field < 0 || z.field >= SEL_NUM_FIELDS || (z.flags & ~CL_SEL_NOT) || z.reserved)
+      return set_err(CL_E_INVALID, "select clause %d: unknown field or flag bits, or non-zero reserved", q);
+    const int64_t bound = z.field == CL_SEL_NODE ? N : z.field == CL_SEL_CH_MSGS || z.field == CL_SEL_CH_TOK ? Cn : 1;
+    if (z.index < 0 || z.index >= bound) return set_err(CL_E_INVALID, "select clause %d: index %d out of range", q, z.index);
+  }
+  if (cap < 0 || (cap > 0 && !insts)) return set_err(CL_E_INVALID, "select: cap >= 0, with an index array when cap > 0");
+  if (inst_lo < 0 || inst_hi > sim->n_inst || inst_lo > inst_hi)
+    return set_err(CL_E_INVALID, "instance range out of range");
+  if (sim->ops.empty() && !sim->dev_ready) return set_err(CL_E_STATE, "nothing has run yet: no event was issued");
+  if (sid < 0 || sid >= sim->n_sids) return set_err(CL_E_INVALID, "snapshot id out of range");
+  return sim->select(sid, inst_lo, inst_hi, clauses, n_clauses, insts, ticks, cap, info);
+}
+
+int cl_select_stage_times(cl_sim* sim, double* evaluate_ms, double* compact_ms) {
+  SIM_CHECK(sim);
+  if (!sim->sel_timed) return set_err(CL_E_STATE, "no select call has run");
+  HIP_TRY(hipStreamSynchronize(sim->stream));
+  float a = 0.f, b = 0.f;
+  HIP_TRY(hipEventElapsedTime(&a, sim->sel_ev[0], sim->sel_ev[1]));
+  HIP_TRY(hipEventElapsedTime(&b, sim->sel_ev[1], sim->sel_ev[2]));
+  if (evaluate_ms) *evaluate_ms = a;
+  if (compact_ms) *compact_ms = b;
+  return CL_OK;
+}
+
+int cl_select_time(cl_sim* sim, double* device_ms) {
+  if (!device_ms) return set_err(CL_E_INVALID, "null output");
+  double a = 0, b = 0;
+  const int rc = cl_select_stage_times(sim, &a, &b);
+  if (rc) return rc;
+  *device_ms = a + b;
+  return CL_OK;
+}
+
+int cl_snapshot_ticks(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, int32_t* out) {
+  SIM_CHECK(sim);
+  if (inst_lo < 0 || inst_hi > sim->n_inst || inst_lo > inst_hi)
+    return set_err(CL_E_INVALID, "instance range out of range");
+  if (!out && inst_hi > inst_lo) return set_err(CL_E_INVALID, "null output");
+  if (sim->ops.empty() && !sim->dev_ready) return set_err(CL_E_STATE, "nothing has run yet: no event was issued");
+  if (sid < 0 || sid >= sim->n_sids) return set_err(CL_E_INVALID, "snapshot id out of range");
+  return sim->ticks_of(sid, inst_lo, inst_hi, out);
 }
 
 int cl_get_counters(cl_sim* sim, int32_t only_ok, int64_t* out) {

@@ -82,6 +82,38 @@ def gather_census(census, first_instance, device):
     return out
 
 
+def gather_selection(sel, first_instance, device):
+    """A rank's SnapshotSelection (ChandyLamportSim.select_instances of its shard, whose instance 0
+    is global instance `first_instance`) combined over all ranks, in the manner of gather_census:
+    one all_gather of the heads sizes one all_gather of the (instance, tick) rows padded to the
+    longest, and the parts merge with each rank's first instance as offset
+    (SnapshotSelection.merge; a truncated selection raises ValueError there).  Returns a new
+    SnapshotSelection, the same on every rank, with global instance indices; without an
+    initialised group, a copy."""
+    cls = type(sel)
+    mine = cls(sel.snapshot_id, sel.instances, sel.ok, sel.sample, sel.n_match, sel.insts.copy(),
+               None if sel.ticks is None else sel.ticks.copy())
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return mine
+    head = allgather_ints([mine.n_returned, first_instance, mine.instances, mine.ok, mine.sample, mine.n_match,
+                           mine.ticks is not None], device)
+    rows = np.zeros((max(int(head[:, 0].max()), 1), 2), dtype=np.int64)
+    rows[:mine.n_returned, 0] = mine.insts
+    if mine.ticks is not None:
+        rows[:mine.n_returned, 1] = mine.ticks
+    t = torch.from_numpy(rows).to(device)
+    parts = [torch.empty_like(t) for _ in range(dist.get_world_size())]
+    dist.all_gather(parts, t)
+    out = None
+    for r, part in enumerate(parts):
+        k, first, instances, ok, sample, n_match, has_ticks = (int(v) for v in head[r])
+        got = part.cpu().numpy()[:k]
+        c = cls(mine.snapshot_id, instances, ok, sample, n_match, got[:, 0], got[:, 1] if has_ticks else None)
+        empty = cls(mine.snapshot_id, 0, 0, 0, 0, got[:0, 0], got[:0, 1] if has_ticks else None)
+        out = empty.merge(c, offset=first) if out is None else out.merge(c, offset=first)
+    return out
+
+
 # ---- exchange layer of the graph-partitioned mode (DESIGN.md §11) ---------------------
 # One simulation whose nodes are split into rank ranges exchanges, every tick, records
 # addressed to the owners of other nodes (deliveries, broadcast-trigger reports, draw

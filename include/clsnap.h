@@ -367,6 +367,55 @@ int cl_snapshot_census(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_h
 /* Device time of the latest cl_snapshot_census kernels (HIP events), like cl_stats_time. */
 int cl_census_time(cl_sim* sim, double* device_ms);
 
+/* ---- instance selection by snapshot predicate: which instances are those? --------------------
+ * cl_snapshot_stats and cl_snapshot_census describe a batch; this call names the instances behind
+ * a histogram bin, a tail or a class.  The query is a conjunction of at most CL_SELECT_MAX_CLAUSES
+ * range clauses over the per-instance quantities the statistics reduce, evaluated on the GPU over
+ * the record planes.  The universe is the sample of those two calls: the instances of
+ * [inst_lo, inst_hi) with status CL_INST_OK in which snapshot sid has completed; instances, ok and
+ * sample in `info` mean what they mean there.  An instance matches when every clause holds
+ * (n_clauses == 0: the whole sample).  A clause holds when its field's value lies in [lo, hi], both
+ * inclusive -- with CL_SEL_NOT, when it lies outside; lo > hi is the empty interval (with
+ * CL_SEL_NOT it then matches everything).
+ *   insts   the matches in ascending instance order, as absolute indices (not relative to
+ *           inst_lo); with n_match > cap the first cap of them.  n_returned = min(n_match, cap);
+ *           truncation is reported, not an error.  cap == 0 with insts == NULL only counts.
+ *   ticks   (may be NULL) ticks[k] = completion tick of insts[k]
+ * The result is a pure function of the records: it does not depend on the grid, the record layout
+ * or the exec kernel.  Only info and n_returned * 8 bytes (12 with ticks) cross PCIe; the result
+ * feeds cl_collect_snapshot_list.  Like the other result queries the call executes pending events
+ * and never adds a tick, holds the sim's lock and waits for a split replay's second half.
+ * Arguments are checked before any device work: CL_E_INVALID (NULL info; NULL clauses with
+ * n_clauses > 0; n_clauses outside [0, CL_SELECT_MAX_CLAUSES]; an unknown field or flag bits;
+ * non-zero reserved; index outside [0, N) for CL_SEL_NODE, outside [0, C) for CL_SEL_CH_*,
+ * non-zero for the other fields; sid or the range out of bounds; cap < 0; NULL insts with
+ * cap > 0), CL_E_STATE (no event was ever issued).  inst_lo == inst_hi is valid and gives an
+ * all-zero info. */
+#define CL_SEL_TICK      0  /* completion tick of sid */
+#define CL_SEL_MSGS      1  /* recorded messages of the instance over all channels (stats "msgs") */
+#define CL_SEL_INFLIGHT  2  /* recorded tokens of the instance over all channels (stats "inflight") */
+#define CL_SEL_NODE      3  /* tokenMap entry of node rank `index` */
+#define CL_SEL_CH_MSGS   4  /* recorded messages on channel `index` (cl_channel order) */
+#define CL_SEL_CH_TOK    5  /* recorded tokens on channel `index` */
+#define CL_SEL_KEY       6  /* snapshot content hash (the census key); lo/hi are uint64 bit patterns, compared unsigned */
+#define CL_SEL_NOT       1  /* clause flag: the clause holds when the value is OUTSIDE [lo, hi] */
+#define CL_SELECT_MAX_CLAUSES 8
+typedef struct { int32_t field, index, flags, reserved; int64_t lo, hi; } cl_select_clause; /* 32 B */
+typedef struct { int64_t instances, ok, sample, n_match, n_returned; } cl_select_info;
+int cl_select_instances(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi,
+                        const cl_select_clause* clauses, int32_t n_clauses,
+                        int64_t* insts /* [cap] or NULL iff cap == 0 */, int32_t* ticks /* [cap] or NULL */,
+                        int64_t cap, cl_select_info* info);
+/* Device time of the latest cl_select_instances kernels, both stages (HIP events), like
+ * cl_census_time.  cl_select_stage_times splits it: the evaluation of the clauses into the
+ * verdict bitmap, and the bitmap's compaction (either pointer may be NULL). */
+int cl_select_time(cl_sim* sim, double* device_ms);
+int cl_select_stage_times(cl_sim* sim, double* evaluate_ms, double* compact_ms);
+/* The bulk form of cl_snapshot_tick: out[i - inst_lo] = completion tick of snapshot sid in
+ * instance i of [inst_lo, inst_hi), -1 = not complete.  One strided device-to-host copy; the same
+ * flush and lock behaviour and argument checks as the result queries above. */
+int cl_snapshot_ticks(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, int32_t* out /* [hi-lo], -1 = not complete */);
+
 /* ---- device event trace: the reference's debug Logger (logger.go:12-76) ---- */
 /* One LogEvent (logger.go:18-23) per record, in the Logger's order.  Node ranks refer
  * to cl_node_id; `other` is the peer of a Sent/Received record (-1 for Start/End and
