@@ -1,5 +1,5 @@
 // cg_engine.h -- data layout shared by the graph engine's host runtime (cg_host.cpp)
-// and its gfx950 kernels (cg_kernels.hip, cg_table.hip).  DESIGN.md §10 draws the same layout.
+// and its gfx950 kernels (cg_kernels.hip, cg_table.hip, cg_sparse.hip).  DESIGN.md §10 draws the same layout.
 //
 // The graph engine runs ONE reference simulation over a large topology (BASELINE
 // configs 4 and 5: 2^20-node regular digraph, 100k-node power-law graph with 4,096
@@ -273,5 +273,21 @@ int cg_launch_checks(const GParams& p, int32_t n_sids, unsigned long long* out, 
 // An init kernel and one grid-stride pass sized to n_cus compute units.
 int cg_launch_table(const GParams& p, const int32_t* in_ch, int32_t k_lo, int32_t k_hi, int32_t sid_lo,
                     int32_t n_sids, long long* rows, int32_t n_cus, void* stream);
+// Sparse packed collect (cg_sparse.hip) of the snapshots sid_lo + [0, n_sids): one entry per
+// channel into an owned node with at least one recorded message of a completed snapshot, in
+// (sid, channel) order.  cg_sparse_tiles(e) = channel tiles of a graph of e channels; the scan
+// leaves in tb[n_sids * tiles] every tile's (entry, message) offset within its sid's row, in
+// rtot[n_sids] the rows' totals, in row_off / row_moff[n_sids + 1] the rows' entry and message
+// offsets (the last: the totals) and in complete[n_sids] whether each sid completed.  The write
+// recomputes the tiles and stores channel and count of every entry, and, with msg != nullptr,
+// the payloads from the history p.histv (p.hist > 0).  The token plane is out[n_sids][part_hi -
+// part_lo]: recorded node tokens, a row of -1 for an incomplete sid.
+int32_t cg_sparse_tiles(int64_t e);
+int cg_launch_sparse_scan(const GParams& p, int32_t sid_lo, int32_t n_sids, ulonglong2* tb, ulonglong2* rtot,
+                          long long* row_off, long long* row_moff, int32_t* complete, void* stream);
+int cg_launch_sparse_write(const GParams& p, int32_t sid_lo, int32_t n_sids, const ulonglong2* tb,
+                           const ulonglong2* rtot, const long long* row_off, const long long* row_moff,
+                           int32_t* ent_channel, int32_t* ent_count, int32_t* msg, void* stream);
+int cg_launch_sparse_tokens(const GParams& p, int32_t sid_lo, int32_t n_sids, int32_t* out, void* stream);
 
 }  // namespace clsnap

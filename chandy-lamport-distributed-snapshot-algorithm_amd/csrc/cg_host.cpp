@@ -188,6 +188,14 @@ struct cl_graph {
   hipEvent_t tb_ev[2] = {nullptr, nullptr};
   bool tb_timed = false;
   int32_t n_cus = 0;
+  // sparse packed collect (cl_graph_collect_sparse): per-(sid, tile) offsets, per-sid totals,
+  // the head the host reads between scan and write (row_offsets, message offsets, complete),
+  // the packed outputs, and the events around the scan ([0], [1]) and the write ([2], [3])
+  GBuf<ulonglong2> d_sp_tiles, d_sp_rows;
+  GBuf<long long> d_sp_head;
+  GBuf<int32_t> d_sp_chan, d_sp_cnt, d_sp_msg, d_sp_tok;
+  hipEvent_t sp_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool sp_timed = false, sp_wrote = false;
   size_t ops_uploaded = 0;
   // device event trace (cl_graph_trace_enable)
   int32_t trace_cap = 0;
@@ -228,7 +236,11 @@ struct cl_graph {
     d_rep_in.release(); d_trigv.release(); d_s0.release(); d_rdraw.release(); d_draw0.release();
     d_replies.release(); d_pop.release(); d_bk_cnt.release();
     d_in_ch.release(); d_table.release();
+    d_sp_tiles.release(); d_sp_rows.release(); d_sp_head.release();
+    d_sp_chan.release(); d_sp_cnt.release(); d_sp_msg.release(); d_sp_tok.release();
     for (auto& e : tb_ev)
+      if (e) (void)hipEventDestroy(e);
+    for (auto& e : sp_ev)
       if (e) (void)hipEventDestroy(e);
     for (auto& ev : ev_pool) {
       (void)hipEventDestroy(ev.first);
@@ -1541,8 +1553,106 @@ int cl_graph_table_time(cl_graph* g, double* ms) {
   return CL_OK;
 }
 
+int cl_graph_collect_sparse(cl_graph* g, int32_t sid_lo, int32_t sid_hi, int32_t* complete, int64_t* row_offsets,
+                            int32_t* ent_channel, int32_t* ent_count, int64_t ent_cap, int32_t* msg_tokens,
+                            int64_t msg_cap, int32_t* tokens, cl_graph_sparse_info* info) {
+  G_CHECK(g);
+  static_assert(sizeof(cl_graph_sparse_info) == 8 * sizeof(int64_t), "cl_graph_sparse_info is 8 x int64");
+  if (!info) return gerr(CL_E_INVALID, "null info");
+  if (sid_lo < 0 || sid_lo > sid_hi || sid_hi > g->n_sids)
+    return gerr(CL_E_INVALID, "snapshot range [%d, %d) outside [0, %d]", sid_lo, sid_hi, g->n_sids);
+  if (ent_cap < 0 || msg_cap < 0) return gerr(CL_E_INVALID, "negative capacity");
+  if (ent_cap > 0 && (!ent_channel || !ent_count)) return gerr(CL_E_INVALID, "null entry arrays with ent_cap > 0");
+  const int32_t ns = sid_hi - sid_lo;
+  *info = cl_graph_sparse_info{};
+  info->node_lo = g->part ? g->part_lo : 0;
+  info->node_hi = g->part ? g->part_hi : (g->frozen ? g->n : 0);
+  if (ns == 0) {
+    if (row_offsets) row_offsets[0] = 0;
+    return CL_OK;
+  }
+  int rc = g->flush();
+  if (rc) return rc;
+  const GParams& P = g->P;
+  const size_t tiles = (size_t)cg_sparse_tiles(P.e), nsz = (size_t)ns;
+  // head: row_offsets[ns + 1], message offsets[ns + 1], then complete[ns] as int32
+  const size_t head_words = 2 * (nsz + 1) + (nsz + 1) / 2;
+  if ((rc = g->d_sp_tiles.ensure(nsz * tiles)) || (rc = g->d_sp_rows.ensure(nsz)) ||
+      (rc = g->d_sp_head.ensure(head_words)))
+    return rc;
+  long long* d_off = g->d_sp_head.p;
+  long long* d_moff = d_off + (nsz + 1);
+  int32_t* d_complete = reinterpret_cast<int32_t*>(d_moff + (nsz + 1));
+  for (auto& e : g->sp_ev)
+    if (!e) GHIP(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
+  g->sp_timed = g->sp_wrote = false;
+  GHIP(hipEventRecord(g->sp_ev[0], g->stream));
+  if ((rc = g->k_err(cg_launch_sparse_scan(P, sid_lo, ns, g->d_sp_tiles.p, g->d_sp_rows.p, d_off, d_moff, d_complete,
+                                           g->stream))))
+    return rc;
+  GHIP(hipEventRecord(g->sp_ev[1], g->stream));
+  // the totals decide the sizes: the host reads the head between scan and write
+  std::vector<long long> head(head_words);
+  GHIP(hipMemcpyAsync(head.data(), d_off, head_words * sizeof(long long), hipMemcpyDeviceToHost, g->stream));
+  GHIP(hipStreamSynchronize(g->stream));
+  g->sp_timed = true;
+  const int32_t* h_complete = reinterpret_cast<const int32_t*>(head.data() + 2 * (nsz + 1));
+  const int64_t n_entries = head[nsz], n_msgs = head[2 * nsz + 1];
+  info->n_sids = ns;
+  for (int32_t r = 0; r < ns; ++r) info->n_complete += h_complete[r] != 0;
+  info->n_entries = n_entries;
+  info->n_msgs = n_msgs;
+  info->unit_payloads = g->hist == 0 ? 1 : 0;
+  if (complete) std::copy(h_complete, h_complete + ns, complete);
+  if (row_offsets) std::copy(head.begin(), head.begin() + (ns + 1), row_offsets);
+  if (n_entries > ent_cap)
+    return gerr(CL_E_LIMIT, "%lld entries exceed ent_cap %lld", (long long)n_entries, (long long)ent_cap);
+  if (msg_tokens && n_msgs > msg_cap)
+    return gerr(CL_E_LIMIT, "%lld messages exceed msg_cap %lld", (long long)n_msgs, (long long)msg_cap);
+  // unit payloads are all 1: no history on the device, nothing to pack or copy
+  const bool dev_msgs = msg_tokens && g->hist > 0 && n_msgs > 0;
+  const int64_t width = info->node_hi - info->node_lo;
+  if ((rc = g->d_sp_chan.ensure((size_t)n_entries)) || (rc = g->d_sp_cnt.ensure((size_t)n_entries))) return rc;
+  if (dev_msgs && (rc = g->d_sp_msg.ensure((size_t)n_msgs))) return rc;
+  if (tokens && (rc = g->d_sp_tok.ensure(nsz * (size_t)width))) return rc;
+  GHIP(hipEventRecord(g->sp_ev[2], g->stream));
+  if (n_entries > 0 &&
+      (rc = g->k_err(cg_launch_sparse_write(P, sid_lo, ns, g->d_sp_tiles.p, g->d_sp_rows.p, d_off, d_moff,
+                                            g->d_sp_chan.p, g->d_sp_cnt.p, dev_msgs ? g->d_sp_msg.p : nullptr,
+                                            g->stream))))
+    return rc;
+  if (tokens && (rc = g->k_err(cg_launch_sparse_tokens(P, sid_lo, ns, g->d_sp_tok.p, g->stream)))) return rc;
+  GHIP(hipEventRecord(g->sp_ev[3], g->stream));
+  if (n_entries > 0) {
+    GHIP(hipMemcpyAsync(ent_channel, g->d_sp_chan.p, (size_t)n_entries * sizeof(int32_t), hipMemcpyDeviceToHost,
+                        g->stream));
+    GHIP(hipMemcpyAsync(ent_count, g->d_sp_cnt.p, (size_t)n_entries * sizeof(int32_t), hipMemcpyDeviceToHost,
+                        g->stream));
+  }
+  if (dev_msgs)
+    GHIP(hipMemcpyAsync(msg_tokens, g->d_sp_msg.p, (size_t)n_msgs * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+  if (tokens && width > 0)
+    GHIP(hipMemcpyAsync(tokens, g->d_sp_tok.p, nsz * (size_t)width * sizeof(int32_t), hipMemcpyDeviceToHost,
+                        g->stream));
+  GHIP(hipStreamSynchronize(g->stream));
+  g->sp_wrote = true;
+  if (msg_tokens && !dev_msgs) std::fill(msg_tokens, msg_tokens + n_msgs, 1);
+  return CL_OK;
+}
+
+int cl_graph_sparse_time(cl_graph* g, double* ms) {
+  G_CHECK(g);
+  if (!ms) return gerr(CL_E_INVALID, "null output");
+  if (!g->sp_timed) return gerr(CL_E_STATE, "no sparse collect has run");
+  float a = 0.f, b = 0.f;
+  GHIP(hipEventElapsedTime(&a, g->sp_ev[0], g->sp_ev[1]));
+  if (g->sp_wrote) GHIP(hipEventElapsedTime(&b, g->sp_ev[2], g->sp_ev[3]));
+  *ms = (double)a + (double)b;
+  return CL_OK;
+}
+
 // ---- graph-partitioned mode ---------------------------------------------
-#define G_PART(g)                                                                            \
+#define G_PART(g)                                                                           \
   do {                                                                                       \
     if (!(g)->part) return gerr(CL_E_STATE, "not a partitioned run (cl_graph_part_begin)");  \
   } while (0)

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import (ClSnapError, GlobalSnapshot, MsgSnapshot, PassTokenEvent, SnapshotEvent, _check, _p, format_log,
-               COUNTER_NAMES, lib)
+               COUNTER_NAMES, E_LIMIT, lib)
 
 GSUM_NAMES = ("ok", "delivered", "completed", "cut_residual", "final_residual", "digest", "in_flight")
 
@@ -81,6 +81,8 @@ def glib():
             "cl_graph_get_checksums": [vp, vp],
             "cl_graph_snapshot_table": [vp, i32, i32, vp],
             "cl_graph_table_time": [vp, vp],
+            "cl_graph_collect_sparse": [vp, i32, i32, vp, vp, vp, vp, i64, vp, i64, vp, vp],
+            "cl_graph_sparse_time": [vp, vp],
             "cl_graph_part_begin": [vp, i32, i32],
             "cl_graph_part_snapshot": [vp, i32, vp],
             "cl_graph_part_pick": [vp, vp, i64, vp],
@@ -179,6 +181,222 @@ class SnapshotTable:
         for f in self._CHANNEL:
             out[f] = np.where(done, out[f], np.int64(0))
         return SnapshotTable(out)
+
+
+# cl_graph_sparse_info (include/clgraph.h): 8 x int64.
+SPARSE_INFO_FIELDS = ("n_sids", "n_complete", "n_entries", "n_msgs", "unit_payloads", "node_lo", "node_hi",
+                      "reserved")
+SPARSE_INFO_DTYPE = np.dtype([(f, np.int64) for f in SPARSE_INFO_FIELDS])
+
+_U64 = np.uint64
+
+
+def _mix64(z):
+    """mix64 (cl_engine.h) on uint64 arrays."""
+    with np.errstate(over="ignore"):
+        z = (z ^ (z >> _U64(30))) * _U64(0xbf58476d1ce4e5b9)
+        z = (z ^ (z >> _U64(27))) * _U64(0x94d049bb133111eb)
+    return z ^ (z >> _U64(31))
+
+
+def _cg_hash(seed, a, b):
+    """cg_hash (cg_engine.h) of a scalar a and a uint64 array b."""
+    with np.errstate(over="ignore"):
+        h = _mix64(np.asarray(_U64(seed) ^ (_U64(a) * _U64(0x9E3779B97F4A7C15))))
+        return _mix64(h ^ (b * _U64(0xD6E8FEB86659FD93)))
+
+
+class SparseSnapshots:
+    """The recorded channel state of the snapshots [sid_lo, sid_lo + len(complete)), compacted
+    on the device (GraphSim.collect_sparse, cl_graph_collect_sparse): one entry per channel
+    with at least one recorded message of a completed snapshot, ordered by snapshot id, then
+    channel index.
+
+      complete[r]     1 iff snapshot sid_lo + r completed (an incomplete one has no entries)
+      row_offsets     int64[len + 1]: the entries of snapshot sid_lo + r are [row_offsets[r],
+                      row_offsets[r + 1])
+      channel, count  int32 per entry: the channel (index into GraphSim.channels()) and its
+                      recorded messages
+      msg_offsets     int64[entries + 1]: entry i's payloads are msg_tokens[msg_offsets[i] :
+                      msg_offsets[i + 1]], in delivery order
+      msg_tokens      int32 payloads, or None when they were not asked for
+      tokens          int32[len, node_hi - node_lo] recorded node tokens (a row of -1 for an
+                      incomplete snapshot), or None
+      node_lo/hi      the node ranks the object covers (a part of a partitioned run, else all)"""
+
+    def __init__(self, sid_lo, complete, row_offsets, channel, count, msg_tokens=None, tokens=None, node_lo=0,
+                 node_hi=0):
+        self.sid_lo = int(sid_lo)
+        self.complete = np.ascontiguousarray(complete, dtype=np.int32).reshape(-1)
+        self.row_offsets = np.ascontiguousarray(row_offsets, dtype=np.int64).reshape(-1)
+        self.channel = np.ascontiguousarray(channel, dtype=np.int32).reshape(-1)
+        self.count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+        self.msg_offsets = np.zeros(self.count.size + 1, dtype=np.int64)
+        np.cumsum(self.count, dtype=np.int64, out=self.msg_offsets[1:])
+        self.msg_tokens = None if msg_tokens is None else np.ascontiguousarray(msg_tokens, dtype=np.int32).reshape(-1)
+        self.node_lo, self.node_hi = int(node_lo), int(node_hi)
+        self.tokens = None if tokens is None else \
+            np.ascontiguousarray(tokens, dtype=np.int32).reshape(self.complete.size, self.node_hi - self.node_lo)
+        if self.row_offsets.size != self.complete.size + 1 or self.row_offsets[-1] != self.channel.size or \
+                self.channel.size != self.count.size:
+            raise ValueError("row_offsets, channel and count do not describe the same entries")
+        if self.msg_tokens is not None and self.msg_tokens.size != self.msg_offsets[-1]:
+            raise ValueError("msg_tokens does not hold the entries' messages")
+
+    def __len__(self):
+        return self.complete.size
+
+    @property
+    def sid_hi(self):
+        return self.sid_lo + self.complete.size
+
+    @property
+    def n_entries(self):
+        return self.channel.size
+
+    @property
+    def n_msgs(self):
+        return int(self.msg_offsets[-1])
+
+    def __eq__(self, other):
+        if not isinstance(other, SparseSnapshots):
+            return NotImplemented
+        same = lambda a, b: (a is None) == (b is None) and (a is None or np.array_equal(a, b))  # noqa: E731
+        return (self.sid_lo, self.node_lo, self.node_hi) == (other.sid_lo, other.node_lo, other.node_hi) and \
+            all(same(getattr(self, f), getattr(other, f))
+                for f in ("complete", "row_offsets", "channel", "count", "msg_tokens", "tokens"))
+
+    __hash__ = None
+
+    def __repr__(self):
+        return (f"SparseSnapshots(sids [{self.sid_lo}, {self.sid_hi}), {int(self.complete.sum())} complete, "
+                f"{self.n_entries} entries, {self.n_msgs} messages, nodes [{self.node_lo}, {self.node_hi}))")
+
+    def _row(self, sid):
+        r = sid - self.sid_lo
+        if not 0 <= r < self.complete.size:
+            raise IndexError(f"snapshot {sid} outside [{self.sid_lo}, {self.sid_hi})")
+        return r
+
+    def _need_complete(self, sid):
+        r = self._row(sid)
+        if not self.complete[r]:
+            raise ClSnapError(-9, f"snapshot {sid} has not completed")
+        return r
+
+    def entries(self, sid):
+        """(channel, count, payloads) of snapshot sid: its entries' channels and message counts,
+        and one payload slice per entry (None without payloads)."""
+        r = self._row(sid)
+        a, b = int(self.row_offsets[r]), int(self.row_offsets[r + 1])
+        pay = None
+        if self.msg_tokens is not None:
+            pay = [self.msg_tokens[self.msg_offsets[i]:self.msg_offsets[i + 1]] for i in range(a, b)]
+        return self.channel[a:b], self.count[a:b], pay
+
+    def dense(self, sid, n_channels):
+        """(tokens, offsets[n_channels + 1], messages) as int64: what GraphSim.collect_arrays
+        returns (tokens None when the object holds none); ClSnapError(-9) if sid has not
+        completed."""
+        r = self._need_complete(sid)
+        if self.msg_tokens is None:
+            raise ValueError("dense needs the payloads (collect_sparse(payloads=True))")
+        a, b = int(self.row_offsets[r]), int(self.row_offsets[r + 1])
+        cnt = np.zeros(n_channels, dtype=np.int64)
+        cnt[self.channel[a:b]] = self.count[a:b]
+        off = np.zeros(n_channels + 1, dtype=np.int64)
+        np.cumsum(cnt, out=off[1:])
+        msg = self.msg_tokens[self.msg_offsets[a]:self.msg_offsets[b]].astype(np.int64)   # (channel order already)
+        tok = None if self.tokens is None else self.tokens[r].astype(np.int64)
+        return tok, off, msg
+
+    def digest(self, sid, n_nodes, n_channels):
+        """Snapshot sid's term of CL_GSUM_DIGEST (cg_kernels.hip k_checks_snap; the `digest` of
+        its SnapshotTable row), as an int64, from the sparse contents: the recorded tokens of
+        every node, and of every channel its message count and payload sum -- (0, 0) for the
+        channels without an entry.  Needs the token plane of all n_nodes nodes and the payloads."""
+        r = self._need_complete(sid)
+        if self.tokens is None or (self.node_lo, self.node_hi) != (0, n_nodes):
+            raise ValueError("digest needs the token plane of every node (collect_sparse(tokens=True))")
+        if self.msg_tokens is None:
+            raise ValueError("digest needs the payloads (collect_sparse(payloads=True))")
+        a, b = int(self.row_offsets[r]), int(self.row_offsets[r + 1])
+        with np.errstate(over="ignore"):
+            h = _cg_hash(0x5107, sid, np.arange(n_nodes, dtype=_U64))
+            total = _mix64(h ^ self.tokens[r].astype(np.uint32).astype(_U64)).sum(dtype=_U64)
+            word = np.zeros(n_channels, dtype=_U64)                  # (count << 32) | payload sum (low 32 bits)
+            cs = np.concatenate([[0], np.cumsum(self.msg_tokens, dtype=np.int64)])
+            sums = cs[self.msg_offsets[a + 1:b + 1]] - cs[self.msg_offsets[a:b]]
+            word[self.channel[a:b]] = (self.count[a:b].astype(_U64) << _U64(32)) | \
+                sums.astype(np.uint32).astype(_U64)
+            hc = _cg_hash(0xC4A1, sid, np.arange(n_channels, dtype=_U64))
+            total = total + _mix64(hc ^ word).sum(dtype=_U64)
+        return int(np.asarray(total, dtype=_U64).astype(np.int64))
+
+    def snapshot(self, sid, sim):
+        """GlobalSnapshot of sid like sim.CollectSnapshot(sid): messages in (dest, src,
+        delivery) order.  sim supplies the node ids and the channel list."""
+        r = self._need_complete(sid)
+        ids = sim.node_ids()
+        if self.tokens is None or (self.node_lo, self.node_hi) != (0, len(ids)):
+            raise ValueError("snapshot needs the token plane of every node (collect_sparse(tokens=True))")
+        ch, cnt, pay = self.entries(sid)
+        if pay is None:
+            raise ValueError("snapshot needs the payloads (collect_sparse(payloads=True))")
+        src, dst = sim.channels()
+        order = np.lexsort((src[ch], dst[ch]))
+        msgs = [MsgSnapshot(ids[src[ch[i]]], ids[dst[ch[i]]], int(t)) for i in order for t in pay[i]]
+        return GlobalSnapshot(sid, dict(zip(ids, self.tokens[r].tolist())), msgs)
+
+    @staticmethod
+    def merge(parts):
+        """The SparseSnapshots of a partitioned run from its parts' (the same sids; disjoint
+        node ranges, so disjoint channels): per sid the entries of all parts sorted by channel;
+        complete is the AND over the parts, and a sid some part has not completed has no
+        entries and a token row of -1; token rows are concatenated in node_lo order.  Payloads
+        and tokens are kept when every part holds them.  A pure host function."""
+        parts = sorted(parts, key=lambda p: p.node_lo)
+        if not parts:
+            raise ValueError("merge needs at least one part")
+        first = parts[0]
+        ns = len(first)
+        for a, b in zip(parts, parts[1:]):
+            if b.sid_lo != first.sid_lo or len(b) != ns:
+                raise ValueError("merge needs parts of the same snapshot ids")
+            if b.node_lo != a.node_hi:
+                raise ValueError("merge needs parts of adjacent node ranges")
+        complete = np.ones(ns, dtype=np.int32)
+        for p in parts:
+            complete &= (p.complete != 0).astype(np.int32)
+        with_msgs = all(p.msg_tokens is not None for p in parts)
+        with_tokens = all(p.tokens is not None for p in parts)
+        # every part's entries of the complete sids, keyed by (row, channel)
+        row, chan, cnt, msgs = [], [], [], []
+        for p in parts:
+            prow = np.repeat(np.arange(ns, dtype=np.int64), np.diff(p.row_offsets))
+            keep = complete[prow] != 0
+            row.append(prow[keep]), chan.append(p.channel[keep]), cnt.append(p.count[keep])
+            if with_msgs:
+                msgs.append(p.msg_tokens[np.repeat(keep, p.count)])
+        row, chan, cnt = np.concatenate(row), np.concatenate(chan), np.concatenate(cnt)
+        order = np.lexsort((chan, row))
+        msg_tokens = None
+        if with_msgs:
+            allm = np.concatenate(msgs)
+            start = np.zeros(cnt.size + 1, dtype=np.int64)
+            np.cumsum(cnt, dtype=np.int64, out=start[1:])
+            c = cnt[order].astype(np.int64)
+            # message j of the merged entry i sits at start[order[i]] + j of the concatenation
+            within = np.arange(int(c.sum()), dtype=np.int64) - np.repeat(np.cumsum(c) - c, c)
+            msg_tokens = allm[np.repeat(start[:-1][order], c) + within]
+        row_offsets = np.zeros(ns + 1, dtype=np.int64)
+        np.cumsum(np.bincount(row, minlength=ns), out=row_offsets[1:])
+        tokens = None
+        if with_tokens:
+            tokens = np.concatenate([p.tokens for p in parts], axis=1)
+            tokens[complete == 0] = -1
+        return SparseSnapshots(first.sid_lo, complete, row_offsets, chan[order], cnt[order], msg_tokens, tokens,
+                               parts[0].node_lo, parts[-1].node_hi)
 
 
 class GraphSim:
@@ -423,6 +641,45 @@ class GraphSim:
     def table_time(self):
         """Device ms of the latest snapshot_table call's kernels (HIP events)."""
         return self._get(self._L.cl_graph_table_time, C.c_double)
+
+    def _collect_sparse(self, sid_lo, sid_hi, complete=None, row_offsets=None, channel=None, count=None, ent_cap=0,
+                        msg_tokens=None, msg_cap=0, tokens=None):
+        """One cl_graph_collect_sparse call: (return code, info record)."""
+        ptr = lambda a: None if a is None else _p(a)  # noqa: E731
+        info = np.zeros(1, dtype=SPARSE_INFO_DTYPE)
+        rc = self._L.cl_graph_collect_sparse(self._h, sid_lo, sid_hi, ptr(complete), ptr(row_offsets), ptr(channel),
+                                             ptr(count), ent_cap, ptr(msg_tokens), msg_cap, ptr(tokens), _p(info))
+        return rc, info[0]
+
+    def collect_sparse(self, sid_lo=0, sid_hi=None, tokens=False, payloads=True):
+        """SparseSnapshots of the snapshots [sid_lo, sid_hi) (default: all): the entries
+        (channel, count) of the completed ones, compacted on the device, with their payloads
+        (payloads=True) and the plane of recorded node tokens (tokens=True).  One sizing call
+        and one fetch (cl_graph_collect_sparse); nothing sized by the channel count reaches
+        the host."""
+        if sid_hi is None:
+            sid_hi = self.num_snapshots
+        ns = max(sid_hi - sid_lo, 0)
+        complete = np.zeros(ns, dtype=np.int32)
+        row_offsets = np.zeros(ns + 1, dtype=np.int64)
+        rc, info = self._collect_sparse(sid_lo, sid_hi, complete, row_offsets)      # the sizing call
+        if rc != E_LIMIT:
+            _check(rc)
+        ne, nm = int(info["n_entries"]), int(info["n_msgs"])
+        lo, hi = int(info["node_lo"]), int(info["node_hi"])
+        channel, count = np.zeros(ne, dtype=np.int32), np.zeros(ne, dtype=np.int32)
+        msg = np.zeros(nm, dtype=np.int32) if payloads else None
+        tok = np.zeros((ns, hi - lo), dtype=np.int32) if tokens else None
+        if ns and (rc == E_LIMIT or payloads or tokens):
+            rc, info = self._collect_sparse(sid_lo, sid_hi, complete, row_offsets, channel, count, ne, msg, nm, tok)
+            _check(rc)
+        if msg is None and info["unit_payloads"]:
+            msg = np.ones(nm, dtype=np.int32)          # (no history: every payload is 1)
+        return SparseSnapshots(sid_lo, complete, row_offsets, channel, count, msg, tok, lo, hi)
+
+    def sparse_time(self):
+        """Device ms of the latest collect_sparse call's kernels (HIP events)."""
+        return self._get(self._L.cl_graph_sparse_time, C.c_double)
 
     # ---- device event trace: the reference's debug Logger (logger.go:12-76) ------------
     def trace_enable(self, capacity=1 << 16):
@@ -676,6 +933,17 @@ class PartitionedGraphSim:
         for t in parts[1:]:
             out = out.merge(t)
         return out
+
+    def collect_sparse(self, sid_lo=0, sid_hi=None, tokens=False, payloads=True):
+        """The whole run's SparseSnapshots on every rank: the parts' sparse collects (each
+        rank's nodes and the channels into them), gathered and merged (SparseSnapshots.merge)."""
+        import torch.distributed as dist
+        mine = self.g.collect_sparse(sid_lo, self.n_sids if sid_hi is None else sid_hi, tokens, payloads)
+        fields = ("sid_lo", "complete", "row_offsets", "channel", "count", "msg_tokens", "tokens", "node_lo",
+                  "node_hi")
+        allp = [None] * self.world
+        dist.all_gather_object(allp, tuple(getattr(mine, f) for f in fields))
+        return SparseSnapshots.merge([SparseSnapshots(*p) for p in allp])
 
     def results(self):
         """(status, final tokens[n], completion ticks, counters, {sid: (tokens[n], offsets,

@@ -186,6 +186,48 @@ int cl_graph_snapshot_table(cl_graph* g, int32_t sid_lo, int32_t sid_hi, cl_grap
 /* Device ms of the latest table call's kernels (HIP events on the engine's stream). */
 int cl_graph_table_time(cl_graph* g, double* ms);
 
+/* ---- sparse packed collect of snapshot contents, compacted on the device -----------
+ * The recorded channel state of the COMPLETED snapshots of [sid_lo, sid_hi), one entry per
+ * channel with at least one recorded message: entry i is channel ent_channel[i] (the channel
+ * index of cl_graph_channels) with ent_count[i] messages; entries are ordered by snapshot id,
+ * then ascending channel; the entries of snapshot sid_lo + r are [row_offsets[r],
+ * row_offsets[r + 1]).  msg_tokens holds the token payloads of all entries back to back in
+ * entry order, delivery order within a channel: entry i's start at the exclusive prefix sum of
+ * ent_count.  complete[r] = 1 iff snapshot sid_lo + r has completed; an incomplete snapshot has
+ * no entries.  tokens (optional) is the plane [n_sids][node_hi - node_lo] of recorded node
+ * tokens, a row of -1 for an incomplete snapshot.  Partitioned runs: this device's part -- its
+ * nodes [node_lo, node_hi), the channels into them, completion over its nodes.
+ *
+ * Only info, complete, row_offsets, the entries, the payloads and the token plane cross to the
+ * host: nothing sized by the number of channels -- against N token words, E cursors and the
+ * whole payload history per snapshot of cl_graph_collect_snapshot.
+ *
+ * Sizing: info, complete and row_offsets are written whenever the device scan has run.  If
+ * n_entries > ent_cap, or msg_tokens != NULL and n_msgs > msg_cap, the call returns CL_E_LIMIT
+ * and leaves the entry, payload and token arrays untouched: size them from info and call
+ * again (ent_cap == 0 with NULL arrays is the sizing call).  msg_tokens == NULL skips the
+ * payloads.  unit_payloads = 1: the run keeps no payload history, every payload is 1.
+ * CL_E_INVALID (before any device work) on a NULL info, a range outside 0 <= sid_lo <= sid_hi
+ * <= num_snapshots, a negative capacity, or NULL entry arrays with ent_cap > 0.  An empty range
+ * returns CL_OK with info zeroed but for node_lo / node_hi and launches nothing. */
+typedef struct cl_graph_sparse_info {   /* 8 x int64 = 64 B */
+  int64_t n_sids;          /* sid_hi - sid_lo */
+  int64_t n_complete;      /* completed snapshots among them */
+  int64_t n_entries;       /* entries of all of them */
+  int64_t n_msgs;          /* recorded messages of all entries */
+  int64_t unit_payloads;   /* 1: no payload history, every payload is 1 */
+  int64_t node_lo, node_hi; /* the owned node ranks (the token plane's columns) */
+  int64_t reserved;        /* 0 */
+} cl_graph_sparse_info;
+int cl_graph_collect_sparse(cl_graph* g, int32_t sid_lo, int32_t sid_hi,
+                            int32_t* complete /* [ns] or NULL */, int64_t* row_offsets /* [ns+1] or NULL */,
+                            int32_t* ent_channel, int32_t* ent_count, int64_t ent_cap,
+                            int32_t* msg_tokens /* [msg_cap] or NULL */, int64_t msg_cap,
+                            int32_t* tokens /* [ns * (node_hi - node_lo)] or NULL */,
+                            cl_graph_sparse_info* info);
+/* Device ms of the latest sparse collect's kernels (HIP events on the engine's stream). */
+int cl_graph_sparse_time(cl_graph* g, double* ms);
+
 /* ---- device event trace: the reference's debug Logger (logger.go:12-76) ---------- */
 /* Record up to `capacity` LogEvents from the next run on (0 = off, the default); the next
  * flush replays the program with tracing.  A debugging aid: records go through one device
