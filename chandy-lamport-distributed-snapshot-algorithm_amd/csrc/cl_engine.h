@@ -491,7 +491,11 @@ inline int32_t stats_blocks_per_cu(int32_t lds_bytes) {
   return b < 1 ? 1 : b > 8 ? 8 : b;
 }
 
-struct StatsParams {
+// The sample of the analytics calls (statistics, census, select) and the planes their kernels walk
+// for it: the instances of [lo, hi) with status OK in which snapshot `sid` completed.  The walk
+// itself is cl_sample.h's (device code; this header is also compiled into the run-time lanes kernel
+// and holds declarations only).
+struct SampleParams {
   int32_t n_nodes, n_ch, s_cap, rw, sid;
   int64_t n_inst, stride;
   int64_t lo, hi;            // the sample's instance range
@@ -501,6 +505,10 @@ struct StatsParams {
   const uint32_t* snap_nod;
   int32_t blocked;           // records block-major by slot (rec_word)
   const int32_t* inst_map;   // slot -> instance of a block-major replay (nullptr: identity)
+};
+
+struct StatsParams {
+  SampleParams s;
   const int32_t* word_ch;    // [N * rw] record word -> channel, -2 token word, -1 padding
   const int32_t* hist_off;   // [C + 1]
   const long long* hist_pre; // prefix sums of the token histories: channel c at hist_off[c] + c
@@ -539,15 +547,7 @@ inline int32_t census_lds_bytes(int32_t lds_slots, bool staged) {
   return lds_slots * kCensusLdsEntryBytes + 4 * 8 + (staged ? kWavesPerBlock * kStatsStageWords * 4 : 0);
 }
 struct CensusParams {
-  int32_t n_nodes, n_ch, s_cap, rw, sid;
-  int64_t n_inst, stride;
-  int64_t lo, hi;            // the sample's instance range
-  int64_t tile_lo, tile_hi;  // 64-slot tiles to walk (as StatsParams)
-  const int32_t* regs;
-  const int32_t* snap_tick;
-  const uint32_t* snap_nod;
-  int32_t blocked;           // records block-major by slot (rec_word)
-  const int32_t* inst_map;   // slot -> instance of a block-major replay (nullptr: identity)
+  SampleParams s;
   const int32_t* ch_slot;    // [C] record word of channel c
   const int32_t* hist_off;   // [C + 1]
   const int32_t* hist_val;
@@ -615,15 +615,7 @@ struct SelectClause {  // the layout of cl_select_clause
   int64_t lo, hi;
 };
 struct SelectParams {
-  int32_t n_nodes, n_ch, s_cap, rw, sid;
-  int64_t n_inst, stride;
-  int64_t lo, hi;            // the sample's instance range
-  int64_t tile_lo, tile_hi;  // 64-slot tiles to walk (as StatsParams)
-  const int32_t* regs;
-  const int32_t* snap_tick;
-  const uint32_t* snap_nod;
-  int32_t blocked;           // records block-major by slot (rec_word)
-  const int32_t* inst_map;   // slot -> instance of a block-major replay (nullptr: identity)
+  SampleParams s;
   const int32_t* ch_slot;    // [C] record word of channel c
   const int32_t* hist_off;   // [C + 1]
   const int32_t* hist_val;

@@ -1186,17 +1186,55 @@ struct cl_sim {
     return CL_OK;
   }
 
-  // cl_snapshot_stats: the statistics of snapshot sid over [lo, hi) into out[L.total_words]
-  // (arguments checked by the caller).  One kernel pass when the topology's N * rw record
-  // words fit the LDS accumulator budget (stats_pass_words), else one pass per range of chunks;
-  // the first pass also takes the per-instance totals.
-  int stats(int32_t sid, int64_t lo, int64_t hi, const StatsLayout& L, int64_t* out) {
+  // The opening of the analytics calls (stats, census, select): executes what is pending, makes the
+  // token histories resident, and describes the sample of snapshot sid over [lo, hi) and the planes
+  // its kernels walk (cl_sample.h).
+  int sample_begin(int32_t sid, int64_t lo, int64_t hi, SampleParams* s) {
     int rc = flush();
     if (rc) return rc;
     if (!dev_ready) return set_err(CL_E_STATE, "nothing has run on the device yet");
     HIP_TRY(hipSetDevice(device));
     if ((rc = upload_hist())) return rc;
     if (!n_cus) HIP_TRY(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device));
+    *s = SampleParams{};
+    s->n_nodes = (int32_t)ids.size();
+    s->n_ch = (int32_t)ch_dst.size();
+    s->s_cap = s_cap;
+    s->rw = lay.rw;
+    s->sid = sid;
+    s->n_inst = n_inst;
+    s->stride = stride;
+    s->lo = lo;
+    s->hi = hi;
+    s->regs = d_regs.p;
+    s->snap_tick = d_snap_tick.p;
+    s->snap_nod = d_snap_nod.p;
+    s->blocked = rec_blocked ? 1 : 0;
+    // (the slot order of the replay that wrote the records; the dbg A/B's is the identity)
+    s->inst_map = rec_blocked && rec_slot_gen != -2 ? d_map.p : nullptr;
+    // block-major records are in slot order: a sub-range's instances may sit in any tile
+    s->tile_lo = rec_blocked ? 0 : lo / kWave;
+    s->tile_hi = hi <= lo ? s->tile_lo : rec_blocked ? stride / kWave : (hi + kWave - 1) / kWave;
+    return CL_OK;
+  }
+
+  // Workgroups of a sample walk over `tiles` tiles whose workgroups need lds_bytes of LDS: a
+  // grid-stride grid sized to the chip, as many workgroups per CU as its LDS holds (up to 8).
+  // (one tile per wave where the batch is small: at 2^17 instances of C3, 4 tiles per wave --
+  // a quarter of the workgroups and of their closing atomics -- measured 0.117 against 0.069 ms)
+  int32_t sample_grid(int64_t tiles, int32_t lds_bytes) const {
+    return (int32_t)std::min<int64_t>((tiles + kWavesPerBlock - 1) / kWavesPerBlock,
+                                      (int64_t)stats_blocks_per_cu(lds_bytes) * std::max(n_cus, 1));
+  }
+
+  // cl_snapshot_stats: the statistics of snapshot sid over [lo, hi) into out[L.total_words]
+  // (arguments checked by the caller).  One kernel pass when the topology's N * rw record
+  // words fit the LDS accumulator budget (stats_pass_words), else one pass per range of chunks;
+  // the first pass also takes the per-instance totals.
+  int stats(int32_t sid, int64_t lo, int64_t hi, const StatsLayout& L, int64_t* out) {
+    StatsParams p{};
+    int rc = sample_begin(sid, lo, hi, &p.s);
+    if (rc) return rc;
     for (auto& e : st_ev)
       if (!e) HIP_TRY(hipEventCreate(&e));
     std::vector<long long> h((size_t)L.total_words, 0);
@@ -1204,46 +1242,23 @@ struct cl_sim {
     std::fill(h.begin() + L.max_begin, h.begin() + L.max_end, INT64_MIN);
     if ((rc = d_stats.ensure(h.size()))) return rc;
     HIP_TRY(hipMemcpyAsync(d_stats.p, h.data(), h.size() * sizeof(long long), hipMemcpyHostToDevice, stream));
-    StatsParams p{};
-    p.n_nodes = (int32_t)ids.size();
-    p.n_ch = (int32_t)ch_dst.size();
-    p.s_cap = s_cap;
-    p.rw = lay.rw;
-    p.sid = sid;
-    p.n_inst = n_inst;
-    p.stride = stride;
-    p.lo = lo;
-    p.hi = hi;
-    p.regs = d_regs.p;
-    p.snap_tick = d_snap_tick.p;
-    p.snap_nod = d_snap_nod.p;
-    p.blocked = rec_blocked ? 1 : 0;
-    // (the slot order of the replay that wrote the records; the dbg A/B's is the identity)
-    p.inst_map = rec_blocked && rec_slot_gen != -2 ? d_map.p : nullptr;
     p.word_ch = d_word_ch.p;
     p.hist_off = d_hist.p;
     p.hist_pre = d_hist_pre.p;
     p.lay = L;
     p.out = d_stats.p;
-    // block-major records are in slot order: a sub-range's instances may sit in any tile
-    p.tile_lo = rec_blocked ? 0 : lo / kWave;
-    p.tile_hi = hi <= lo ? p.tile_lo : rec_blocked ? stride / kWave : (hi + kWave - 1) / kWave;
-    const int64_t tiles = p.tile_hi - p.tile_lo;
+    const int64_t tiles = p.s.tile_hi - p.s.tile_lo;
     const int32_t budget = stats_pass_words((int32_t)L.tick_bins, (int32_t)L.msg_bins);
-    const int32_t n_chunks = stats_chunks(p.n_nodes, p.rw);
-    // a grid-stride grid sized to the chip: as many workgroups per CU as its LDS holds of the
-    // largest pass (two at the full budget, up to 8)
-    const int32_t pass_words = std::min(budget, p.n_nodes * p.rw);
-    const int32_t per_cu = stats_blocks_per_cu(stats_lds_bytes(pass_words, (int32_t)L.tick_bins, (int32_t)L.msg_bins));
-    // (one tile per wave where the batch is small: at 2^17 instances of C3, 4 tiles per wave --
-    // a quarter of the workgroups and of their closing atomics -- measured 0.117 against 0.069 ms)
-    const int32_t blocks = (int32_t)std::min<int64_t>((tiles + kWavesPerBlock - 1) / kWavesPerBlock,
-                                                      (int64_t)per_cu * std::max(n_cus, 1));
+    const int32_t n_chunks = stats_chunks(p.s.n_nodes, p.s.rw);
+    // the grid for the LDS of the largest pass (two workgroups per CU at the full budget)
+    const int32_t pass_words = std::min(budget, p.s.n_nodes * p.s.rw);
+    const int32_t blocks =
+        sample_grid(tiles, stats_lds_bytes(pass_words, (int32_t)L.tick_bins, (int32_t)L.msg_bins));
     HIP_TRY(hipEventRecord(st_ev[0], stream));
     for (int32_t c0 = 0; c0 < n_chunks && tiles > 0;) {
       int32_t c1 = c0, words = 0;
       while (c1 < n_chunks) {
-        const StatsChunk ch = stats_chunk(p.n_nodes, p.rw, c1);
+        const StatsChunk ch = stats_chunk(p.s.n_nodes, p.s.rw, c1);
         if (words + ch.nv * ch.kw > budget) break;
         words += ch.nv * ch.kw;
         ++c1;
@@ -1269,12 +1284,9 @@ struct cl_sim {
   // table's entries, 0 for none.
   int census(int32_t sid, int64_t lo, int64_t hi, int32_t lds_slots, std::vector<CensusEntry>* out,
              int32_t* class_of, cl_census_info* info) {
-    int rc = flush();
+    CensusParams p{};
+    int rc = sample_begin(sid, lo, hi, &p.s);
     if (rc) return rc;
-    if (!dev_ready) return set_err(CL_E_STATE, "nothing has run on the device yet");
-    HIP_TRY(hipSetDevice(device));
-    if ((rc = upload_hist())) return rc;
-    if (!n_cus) HIP_TRY(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device));
     for (auto& e : cs_ev)
       if (!e) HIP_TRY(hipEventCreate(&e));
     const int64_t n = hi - lo;
@@ -1285,32 +1297,17 @@ struct cl_sim {
       return CL_OK;
     }
     if (n > ((int64_t)1 << 29)) return set_err(CL_E_LIMIT, "census of more than 2^29 instances");
-    CensusParams p{};
     p.slots = 16;
     while (p.slots < 2 * n) p.slots <<= 1;
     if ((rc = d_cs_table.ensure((size_t)p.slots + 1)) || (rc = d_cs_list.ensure((size_t)n)) ||
         (rc = d_cs_info.ensure(4)))
       return rc;
     if (class_of && ((rc = d_cs_keys.ensure((size_t)n)) || (rc = d_cs_class.ensure((size_t)n)))) return rc;
-    p.n_nodes = (int32_t)ids.size();
-    p.n_ch = (int32_t)ch_dst.size();
-    p.s_cap = s_cap;
-    p.rw = lay.rw;
-    p.sid = sid;
-    p.n_inst = n_inst;
-    p.stride = stride;
-    p.lo = lo;
-    p.hi = hi;
-    p.regs = d_regs.p;
-    p.snap_tick = d_snap_tick.p;
-    p.snap_nod = d_snap_nod.p;
-    p.blocked = rec_blocked ? 1 : 0;
-    p.inst_map = rec_blocked && rec_slot_gen != -2 ? d_map.p : nullptr;  // (as stats())
     p.ch_slot = d_ch_slot.p;
     p.hist_off = d_hist.p;
     p.hist_val = d_hist.p + hist.size() + 1;
     p.lds_slots = lds_slots;
-    p.staged = p.n_nodes * p.rw <= kCensusStageWords ? 1 : 0;
+    p.staged = p.s.n_nodes * p.s.rw <= kCensusStageWords ? 1 : 0;
     p.empty_key = kCensusEmptyKey;
     // (tests move the marker onto a key that occurs, to run the extra entry's path)
     if (const char* v = std::getenv("CLSNAP_CENSUS_EMPTY_KEY")) p.empty_key = std::strtoull(v, nullptr, 0);
@@ -1319,12 +1316,7 @@ struct cl_sim {
     p.info = d_cs_info.p;
     p.keys = class_of ? d_cs_keys.p : nullptr;
     p.class_of = class_of ? d_cs_class.p : nullptr;
-    p.tile_lo = rec_blocked ? 0 : lo / kWave;
-    p.tile_hi = rec_blocked ? stride / kWave : (hi + kWave - 1) / kWave;
-    const int64_t tiles = p.tile_hi - p.tile_lo;
-    const int32_t per_cu = stats_blocks_per_cu(census_lds_bytes(lds_slots, p.staged != 0));
-    const int32_t blocks = (int32_t)std::min<int64_t>((tiles + kWavesPerBlock - 1) / kWavesPerBlock,
-                                                      (int64_t)per_cu * std::max(n_cus, 1));
+    const int32_t blocks = sample_grid(p.s.tile_hi - p.s.tile_lo, census_lds_bytes(lds_slots, p.staged != 0));
     HIP_TRY(hipEventRecord(cs_ev[0], stream));
     HIP_TRY(hipMemsetAsync(d_cs_info.p, 0, 4 * sizeof(unsigned long long), stream));
     int e = launch_census_init(p, stream);
@@ -1380,37 +1372,19 @@ struct cl_sim {
   // host waits once, for the info, then copies the n_returned entries.
   int select(int32_t sid, int64_t lo, int64_t hi, const cl_select_clause* clauses, int32_t n_clauses, int64_t* insts,
              int32_t* ticks, int64_t cap, cl_select_info* info) {
-    int rc = flush();
+    SelectParams p{};
+    int rc = sample_begin(sid, lo, hi, &p.s);
     if (rc) return rc;
-    if (!dev_ready) return set_err(CL_E_STATE, "nothing has run on the device yet");
-    HIP_TRY(hipSetDevice(device));
-    if ((rc = upload_hist())) return rc;
-    if (!n_cus) HIP_TRY(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device));
     for (auto& e : sel_ev)
       if (!e) HIP_TRY(hipEventCreate(&e));
     *info = cl_select_info{};
     const int64_t n = hi - lo;
     if (n == 0) return CL_OK;
-    SelectParams p{};
-    p.n_nodes = (int32_t)ids.size();
-    p.n_ch = (int32_t)ch_dst.size();
-    p.s_cap = s_cap;
-    p.rw = lay.rw;
-    p.sid = sid;
-    p.n_inst = n_inst;
-    p.stride = stride;
-    p.lo = lo;
-    p.hi = hi;
-    p.regs = d_regs.p;
-    p.snap_tick = d_snap_tick.p;
-    p.snap_nod = d_snap_nod.p;
-    p.blocked = rec_blocked ? 1 : 0;
-    p.inst_map = rec_blocked && rec_slot_gen != -2 ? d_map.p : nullptr;  // (as stats())
     p.ch_slot = d_ch_slot.p;
     p.hist_off = d_hist.p;
     p.hist_val = d_hist.p + hist.size() + 1;
     p.hist_pre = d_hist_pre.p;
-    p.staged = p.n_nodes * p.rw <= kCensusStageWords ? 1 : 0;
+    p.staged = p.s.n_nodes * p.s.rw <= kCensusStageWords ? 1 : 0;
     p.n_clauses = n_clauses;
     for (int32_t q = 0; q < n_clauses; ++q) {
       std::memcpy(&p.clause[q], &clauses[q], sizeof(SelectClause));
@@ -1419,8 +1393,6 @@ struct cl_sim {
       p.need_totals |= f == SEL_MSGS || f == SEL_INFLIGHT;
       p.need_key |= f == SEL_KEY;
     }
-    p.tile_lo = rec_blocked ? 0 : lo / kWave;
-    p.tile_hi = rec_blocked ? stride / kWave : (hi + kWave - 1) / kWave;
     p.base = lo / kWave * kWave;
     p.words = (hi - p.base + kWave - 1) / kWave;
     p.cap = std::min(cap, n);
@@ -1434,10 +1406,7 @@ struct cl_sim {
     p.bsum = d_sel_bsum.p;
     p.out = d_sel_out.p;
     p.ticks = ticks ? d_sel_ticks.p : nullptr;
-    const int64_t tiles = p.tile_hi - p.tile_lo;
-    const int32_t per_cu = stats_blocks_per_cu(select_lds_bytes(p.staged && p.need_records));
-    const int32_t blocks = (int32_t)std::min<int64_t>((tiles + kWavesPerBlock - 1) / kWavesPerBlock,
-                                                      (int64_t)per_cu * std::max(n_cus, 1));
+    const int32_t blocks = sample_grid(p.s.tile_hi - p.s.tile_lo, select_lds_bytes(p.staged && p.need_records));
     HIP_TRY(hipEventRecord(sel_ev[0], stream));
     HIP_TRY(hipMemsetAsync(d_sel_info.p, 0, 4 * sizeof(unsigned long long), stream));
     // block-major: the lanes OR their bits in; instance-major: every word is stored
@@ -2160,6 +2129,16 @@ int cl_collect_time(cl_sim* sim, double* device_ms) {
   return CL_OK;
 }
 
+// The arguments every call over a sample shares (after the call's own): the instance range, a sim
+// that has run something, the snapshot id.
+static int sample_args_ok(const cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi) {
+  if (inst_lo < 0 || inst_hi > sim->n_inst || inst_lo > inst_hi)
+    return set_err(CL_E_INVALID, "instance range out of range");
+  if (sim->ops.empty() && !sim->dev_ready) return set_err(CL_E_STATE, "nothing has run yet: no event was issued");
+  if (sid < 0 || sid >= sim->n_sids) return set_err(CL_E_INVALID, "snapshot id out of range");
+  return CL_OK;
+}
+
 static_assert(sizeof(cl_stats_layout) == sizeof(StatsLayout), "cl_stats_layout mirrors StatsLayout");
 
 static int stats_spec_ok(const cl_stats_spec* spec) {
@@ -2189,10 +2168,7 @@ int cl_snapshot_stats(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi
   int rc = stats_spec_ok(spec);
   if (rc) return rc;
   if (!out) return set_err(CL_E_INVALID, "null output");
-  if (inst_lo < 0 || inst_hi > sim->n_inst || inst_lo > inst_hi)
-    return set_err(CL_E_INVALID, "instance range out of range");
-  if (sim->ops.empty() && !sim->dev_ready) return set_err(CL_E_STATE, "nothing has run yet: no event was issued");
-  if (sid < 0 || sid >= sim->n_sids) return set_err(CL_E_INVALID, "snapshot id out of range");
+  if ((rc = sample_args_ok(sim, sid, inst_lo, inst_hi))) return rc;
   const StatsLayout L = stats_layout((int64_t)sim->ids.size(), (int64_t)sim->links.size(), spec->tick_lo,
                                      spec->tick_bins, spec->msg_bins);
   if (out_words < L.total_words)
@@ -2226,10 +2202,7 @@ int cl_snapshot_census(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_h
     return set_err(CL_E_INVALID, "census spec: max_classes >= 0; lds_slots 0, -1 or a power of two in [%d, %d]",
                    kCensusMinLdsSlots, kCensusMaxLdsSlots);
   if (spec->max_classes > 0 && !classes) return set_err(CL_E_INVALID, "null classes with max_classes > 0");
-  if (inst_lo < 0 || inst_hi > sim->n_inst || inst_lo > inst_hi)
-    return set_err(CL_E_INVALID, "instance range out of range");
-  if (sim->ops.empty() && !sim->dev_ready) return set_err(CL_E_STATE, "nothing has run yet: no event was issued");
-  if (sid < 0 || sid >= sim->n_sids) return set_err(CL_E_INVALID, "snapshot id out of range");
+  if (const int rc = sample_args_ok(sim, sid, inst_lo, inst_hi)) return rc;
   std::vector<CensusEntry> got;
   const int32_t lds_slots = ls == 0 ? kCensusAutoLdsSlots : ls < 0 ? 0 : ls;
   const int rc = sim->census(sid, inst_lo, inst_hi, lds_slots, &got, class_of, info);
@@ -2275,10 +2248,7 @@ int cl_select_instances(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_
     if (z.index < 0 || z.index >= bound) return set_err(CL_E_INVALID, "select clause %d: index %d out of range", q, z.index);
   }
   if (cap < 0 || (cap > 0 && !insts)) return set_err(CL_E_INVALID, "select: cap >= 0, with an index array when cap > 0");
-  if (inst_lo < 0 || inst_hi > sim->n_inst || inst_lo > inst_hi)
-    return set_err(CL_E_INVALID, "instance range out of range");
-  if (sim->ops.empty() && !sim->dev_ready) return set_err(CL_E_STATE, "nothing has run yet: no event was issued");
-  if (sid < 0 || sid >= sim->n_sids) return set_err(CL_E_INVALID, "snapshot id out of range");
+  if (const int rc = sample_args_ok(sim, sid, inst_lo, inst_hi)) return rc;
   return sim->select(sid, inst_lo, inst_hi, clauses, n_clauses, insts, ticks, cap, info);
 }
 
@@ -2305,11 +2275,8 @@ int cl_select_time(cl_sim* sim, double* device_ms) {
 
 int cl_snapshot_ticks(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, int32_t* out) {
   SIM_CHECK(sim);
-  if (inst_lo < 0 || inst_hi > sim->n_inst || inst_lo > inst_hi)
-    return set_err(CL_E_INVALID, "instance range out of range");
   if (!out && inst_hi > inst_lo) return set_err(CL_E_INVALID, "null output");
-  if (sim->ops.empty() && !sim->dev_ready) return set_err(CL_E_STATE, "nothing has run yet: no event was issued");
-  if (sid < 0 || sid >= sim->n_sids) return set_err(CL_E_INVALID, "snapshot id out of range");
+  if (const int rc = sample_args_ok(sim, sid, inst_lo, inst_hi)) return rc;
   return sim->ticks_of(sid, inst_lo, inst_hi, out);
 }
 

@@ -3,15 +3,14 @@
 // Which instances of a batch have a snapshot with given properties: a conjunction of at most
 // kSelMaxClauses range clauses over the quantities cl_snapshot_stats reduces (completion tick, a
 // node's tokenMap entry, a channel's recorded messages and tokens, the instance's totals) and the
-// census key, evaluated over the sample of those calls -- the instances of [lo, hi) with status OK
-// in which snapshot `sid` completed.  The answer is the ascending list of matching instance
+// census key, evaluated over the sample of those calls (cl_sample.h) -- the instances of [lo, hi)
+// with status OK in which snapshot `sid` completed.  The answer is the ascending list of matching instance
 // indices.  All integer and order-preserving, so it does not depend on the grid, the record layout
 // or the exec kernel.
 //
-// Evaluate (cl_select_eval).  A wave walks tiles of 64 record slots, grid-stride, lane = slot, like
-// the statistics and census kernels.  When a clause reads the records, those of at most
-// kCensusStageWords words per instance are staged in LDS with address-ordered loads (the census's
-// pattern); longer ones are read word by word by their lane.  A sample lane computes only what the
+// Evaluate (cl_select_eval).  The sample walk of cl_sample.h, lane = slot.  When a clause reads the
+// records, those of at most kCensusStageWords words per instance are staged in LDS as one chunk
+// (stage_tile); longer ones are read word by word by their lane (RecordRow).  A sample lane computes only what the
 // clauses name: the totals in one pass over the channels' cursor words, a channel's recorded tokens
 // from the int64 prefix of its token history, the key with the census's hash (snapshot_key).  The
 // verdict goes into a bitmap indexed by instance - base, base = lo rounded down to a multiple of 64:
@@ -30,102 +29,39 @@
 #include <hip/hip_runtime.h>
 
 #include "cl_engine.h"
+#include "cl_sample.h"
 
 namespace clsnap {
 namespace {
-
-__device__ __forceinline__ void select_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ __launch_bounds__(kSelThreads) void cl_select_eval(SelectParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char select_lds[];
   const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned long long* scal = reinterpret_cast<unsigned long long*>(select_lds);               // [4] (3 used)
-  uint32_t* tile = reinterpret_cast<uint32_t*>(scal + 4) + (size_t)wave * kStatsStageWords;  // [64][NW | 1]
+  uint32_t* tile = reinterpret_cast<uint32_t*>(scal + 4) + (size_t)wave * kStatsStageWords;  // [64][N * rw | 1]
   if (threadIdx.x < 4) scal[threadIdx.x] = 0;
   __syncthreads();
 
-  const int32_t N = p.n_nodes, rw = p.rw, NW = N * rw, pitch = NW | 1;
-  const size_t plane = (size_t)p.sid * (size_t)p.stride * (size_t)NW;
-  const bool vec = (rw & 3) == 0;
-  unsigned long long n_all = 0, n_ok = 0, n_sample = 0;
-
-  const int64_t wave_stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t t = p.tile_lo + (int64_t)blockIdx.x * kWavesPerBlock + wave; t < p.tile_hi; t += wave_stride) {
-    const int64_t slot = t * 64 + lane;
-    int64_t inst = -1;
-    if (slot < p.n_inst) inst = p.blocked && p.inst_map ? (int64_t)p.inst_map[slot] : slot;
-    const bool in = inst >= p.lo && inst < p.hi;
-    bool ok = false, sample = false;
-    int32_t tick = -1;
-    if (in) {
-      ok = p.regs[inst * R_NUM + R_STATUS] == ST_OK;
-      tick = p.snap_tick[inst * p.s_cap + p.sid];
-      sample = ok && tick >= 0;
-    }
-    n_all += in, n_ok += ok, n_sample += sample;
+  SampleCounts counts;
+  for (int64_t t = sample_first_tile(p.s, wave); t < p.s.tile_hi; t += sample_tile_stride()) {
+    const SampleLane l = sample_lane(p.s, t, lane);
+    counts.add(l);
     bool hit = false;
-    if (__ballot(sample) != 0) {  // (wave-uniform)
-      // the tile's 64 * NW record words, contiguous in both layouts
-      const uint32_t* src = p.snap_nod + plane + (size_t)t * 64 * (size_t)NW;
-      if (p.need_records && p.staged) {
-        select_wave_sync();  // (the previous tile's readers are done)
-        if (vec) {
-          const int32_t rq = rw >> 2;
-          for (int32_t f = lane; f < 16 * NW; f += 64) {
-            const uint4 x = reinterpret_cast<const uint4*>(src)[f];
-            // instance-major: word 4 f of row r = 4 f / NW; block-major [N][64][rw]: record
-            // g = f / rq of node v = g / 64, row r = g % 64
-            int32_t r, k;
-            if (p.blocked) {
-              const int32_t g = f / rq, q = f - g * rq, v = g >> 6;
-              r = g & 63, k = v * rw + 4 * q;
-            } else {
-              r = (4 * f) / NW, k = 4 * f - r * NW;
-            }
-            uint32_t* d = tile + r * pitch + k;
-            d[0] = x.x, d[1] = x.y, d[2] = x.z, d[3] = x.w;
-          }
-        } else {
-          for (int32_t f = lane; f < 64 * NW; f += 64) {
-            int32_t r, k;
-            if (p.blocked) {
-              const int32_t g = f / rw, w = f - g * rw, v = g >> 6;
-              r = g & 63, k = v * rw + w;
-            } else {
-              r = f / NW, k = f - r * NW;
-            }
-            tile[r * pitch + k] = src[f];
-          }
-        }
-        select_wave_sync();
-      }
-      if (sample) {
-        auto rb = [&](int32_t idx) -> uint32_t {
-          if (p.staged) return tile[lane * pitch + idx];
-          if (!p.blocked) return src[(size_t)lane * NW + idx];
-          const int32_t v = idx / rw;
-          return src[((size_t)v * 64 + lane) * rw + (idx - v * rw)];
-        };
+    if (__ballot(l.sample) != 0) {  // (wave-uniform)
+      if (p.need_records && p.staged) stage_tile(p.s, t, whole_record_chunk(p.s), tile, lane);
+      if (l.sample) {
+        const RecordRow rb(p.s, t, lane, tile, p.staged);
         // a channel's recorded messages and tokens from its cursor word
-        auto ch_msgs = [&](int32_t c) -> long long {
-          const uint32_t rec = rb(p.ch_slot[c]);
-          return (long long)((rec >> 16) - (rec & 0xffffu));
-        };
+        auto ch_msgs = [&](int32_t c) -> long long { return (long long)rec_msgs(rb(p.ch_slot[c])); };
         auto ch_tok = [&](int32_t c) -> long long {
-          const uint32_t rec = rb(p.ch_slot[c]), b = rec & 0xffffu, e = rec >> 16;
-          if (e == b) return 0;
-          const long long* pre = p.hist_pre + p.hist_off[c] + c;
-          return pre[e] - pre[b];
+          return rec_tokens(rb(p.ch_slot[c]), token_prefix(p.hist_pre, p.hist_off, c));
         };
         long long msgs = 0, infl = 0;
         if (p.need_totals)
-          for (int32_t c = 0; c < p.n_ch; ++c) msgs += ch_msgs(c), infl += ch_tok(c);
+          for (int32_t c = 0; c < p.s.n_ch; ++c) msgs += ch_msgs(c), infl += ch_tok(c);
         unsigned long long key = 0;
-        if (p.need_key) key = snapshot_key(p.sid, N, rw, p.n_ch, p.ch_slot, p.hist_off, p.hist_val, rb);
+        if (p.need_key)
+          key = snapshot_key(p.s.sid, p.s.n_nodes, p.s.rw, p.s.n_ch, p.ch_slot, p.hist_off, p.hist_val, rb);
         hit = true;
         for (int32_t q = 0; q < p.n_clauses; ++q) {
           const SelectClause& z = p.clause[q];
@@ -133,11 +69,11 @@ __global__ __launch_bounds__(kSelThreads) void cl_select_eval(SelectParams p) {
           if (z.field == SEL_KEY) {
             inside = key >= (unsigned long long)z.lo && key <= (unsigned long long)z.hi;
           } else {
-            long long v = tick;
+            long long v = l.tick;
             switch (z.field) {
               case SEL_MSGS: v = msgs; break;
               case SEL_INFLIGHT: v = infl; break;
-              case SEL_NODE: v = (int32_t)rb(z.index * rw); break;
+              case SEL_NODE: v = (int32_t)rb(z.index * p.s.rw); break;
               case SEL_CH_MSGS: v = ch_msgs(z.index); break;
               case SEL_CH_TOK: v = ch_tok(z.index); break;
               default: break;
@@ -149,27 +85,18 @@ __global__ __launch_bounds__(kSelThreads) void cl_select_eval(SelectParams p) {
       }
     }
     // ---- the verdict
-    if (!p.blocked) {
+    if (!p.s.blocked) {
       const unsigned long long word = __ballot(hit);
-      if (lane == 0) p.bitmap[t - p.tile_lo] = word;
+      if (lane == 0) p.bitmap[t - p.s.tile_lo] = word;
     } else if (hit) {
-      const int64_t bit = inst - p.base;
+      const int64_t bit = l.inst - p.base;
       atomicOr(&p.bitmap[bit >> 6], 1ULL << (bit & 63));
     }
   }
 
-  for (int o = 32; o > 0; o >>= 1) {
-    n_all += __shfl_xor(n_all, o);
-    n_ok += __shfl_xor(n_ok, o);
-    n_sample += __shfl_xor(n_sample, o);
-  }
-  if (lane == 0) {
-    if (n_all) atomicAdd(&scal[0], n_all);
-    if (n_ok) atomicAdd(&scal[1], n_ok);
-    if (n_sample) atomicAdd(&scal[2], n_sample);
-  }
+  counts.fold_wave(scal, lane);
   __syncthreads();
-  if (threadIdx.x < 3 && scal[threadIdx.x]) atomicAdd(&p.info[threadIdx.x], scal[threadIdx.x]);
+  sample_counts_to_global(scal, &p.info[0], &p.info[1], &p.info[2]);
 }
 
 // Inclusive scan of x over the wave's lanes.
@@ -245,7 +172,7 @@ __global__ __launch_bounds__(kSelThreads) void cl_select_fill(SelectParams p) {
       if (pos < p.cap) {
         const int64_t inst = p.base + (w - lane + k) * 64 + lane;
         p.out[pos] = inst;
-        if (p.ticks) p.ticks[pos] = p.snap_tick[inst * p.s_cap + p.sid];
+        if (p.ticks) p.ticks[pos] = p.s.snap_tick[inst * p.s.s_cap + p.s.sid];
       }
     }
   }
@@ -256,7 +183,7 @@ __global__ __launch_bounds__(kSelThreads) void cl_select_fill(SelectParams p) {
 int launch_select_eval(const SelectParams& p, int32_t blocks, void* stream) {
   const size_t lds = (size_t)select_lds_bytes(p.staged != 0 && p.need_records != 0);
   if (blocks < 1 || p.n_clauses < 0 || p.n_clauses > kSelMaxClauses) return (int)hipErrorInvalidValue;
-  if (p.staged && p.n_nodes * p.rw > kCensusStageWords) return (int)hipErrorInvalidValue;
+  if (p.staged && p.s.n_nodes * p.s.rw > kCensusStageWords) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(cl_select_eval, dim3((unsigned)blocks), dim3(kSelThreads), lds, (hipStream_t)stream, p);
   return (int)hipGetLastError();
 }

@@ -1,22 +1,16 @@
 // cl_stats.hip -- per-snapshot batch statistics of the batch engine (cl_snapshot_stats).
 //
 // One pass over the result planes of a run: the status word of `regs`, the completion tick of
-// snapshot `sid` in `snap_tick`, and snapshot sid's slice of the node records `snap_nod`.  The
-// sample is every instance of [lo, hi) with status OK in which the snapshot completed; for it
+// snapshot `sid` in `snap_tick`, and snapshot sid's slice of the node records `snap_nod`.  For the
+// sample (cl_sample.h: the instances of [lo, hi) with status OK in which the snapshot completed)
 // the kernel reduces count / sum / sum of squares / min / max / histograms of the completion
 // tick, of every node's tokenMap entry, of every channel's recorded messages and tokens, and of
 // the per-instance totals, into one flat int64 array (StatsLayout).  All integer, so the result
 // does not depend on the grid, the record layout or the exec kernel that wrote the records.
 //
-// Read pattern.  A wave walks tiles of 64 record slots (grid-stride, the grid sized to the chip).
-// Per tile and chunk of record words (cl_engine.h stats_chunk) it stages 64 x K words in LDS:
-//   block-major records [S][I/64][N][64][rw]: the tile is one 64-slot block, a chunk of whole
-//     nodes is nv * 64 * rw contiguous words, read lane-linear (dwordx4 when rw % 4 == 0); the
-//     slot's instance comes from the replay's slot -> instance map, and a sub-range filters on it;
-//   instance-major records [S][I][N][rw]: the tile's 64 instances are 64 * N * rw contiguous
-//     words; a chunk takes K contiguous words of each (all of them when N * rw <= 32, e.g. the
-//     8-node degree-3 topology's 128 B), again lane-linear.
-// Rows are padded to an odd pitch, so both phases below read the tile without bank conflicts.
+// Read pattern.  The sample walk of cl_sample.h: per tile of 64 record slots and chunk of record
+// words (cl_engine.h stats_chunk) the wave stages 64 x K words in LDS (stage_tile), rows at an odd
+// pitch, so both views below read the tile without bank conflicts.
 //
 // Reduction.  Two views of the staged tile:
 //   lane = slot      the instance's totals (recorded messages, recorded tokens) over the chunk's
@@ -37,18 +31,10 @@
 #include <hip/hip_runtime.h>
 
 #include "cl_engine.h"
+#include "cl_sample.h"
 
 namespace clsnap {
 namespace {
-
-constexpr long long kI64Max = 0x7fffffffffffffffLL;
-constexpr long long kI64Min = -kI64Max - 1;
-
-__device__ __forceinline__ void stats_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 struct Stat4 {
   unsigned long long sum, sq;
@@ -113,38 +99,26 @@ __global__ __launch_bounds__(kStatsThreads) void cl_stats_kernel(StatsParams p) 
   for (int32_t i = threadIdx.x; i < AW * M + T; i += kStatsThreads) mh[i] = 0;  // (mh and th are adjacent)
   __syncthreads();
 
-  const int32_t N = p.n_nodes, rw = p.rw;
+  const int32_t N = p.s.n_nodes, rw = p.s.rw;
   const int32_t n_chunks = stats_chunks(N, rw);
   const int32_t word_lo = [&] {
     const StatsChunk c = stats_chunk(N, rw, p.chunk_lo);
     return c.v0 * rw + c.k0;
   }();
-  const size_t plane = (size_t)p.sid * (size_t)p.stride * (size_t)N * (size_t)rw;
-  const bool vec = (rw & 3) == 0;  // every chunk then starts and ends on 16 bytes
 
-  unsigned long long n_all = 0, n_ok = 0, n_sample = 0;
+  SampleCounts counts;
   Stat4 s_tick, s_msgs, s_infl;
   s_tick.init(), s_msgs.init(), s_infl.init();
 
-  const int64_t wave_stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t t = p.tile_lo + (int64_t)blockIdx.x * kWavesPerBlock + wave; t < p.tile_hi; t += wave_stride) {
-    const int64_t slot = t * 64 + lane;
-    int64_t inst = -1;
-    if (slot < p.n_inst) inst = p.blocked && p.inst_map ? (int64_t)p.inst_map[slot] : slot;
-    const bool in = inst >= p.lo && inst < p.hi;
-    bool ok = false, sample = false;
-    int32_t tick = -1;
-    if (in) {
-      ok = p.regs[inst * R_NUM + R_STATUS] == ST_OK;
-      tick = p.snap_tick[inst * p.s_cap + p.sid];
-      sample = ok && tick >= 0;
-    }
+  for (int64_t t = sample_first_tile(p.s, wave); t < p.s.tile_hi; t += sample_tile_stride()) {
+    const SampleLane l = sample_lane(p.s, t, lane);
+    const bool sample = l.sample;
     const unsigned long long mask = __ballot(sample);
     if (p.totals) {
-      n_all += in, n_ok += ok, n_sample += sample;
+      counts.add(l);
       if (sample) {
-        s_tick.add(tick);
-        long long bin = (long long)tick - p.lay.tick_lo;
+        s_tick.add(l.tick);
+        long long bin = (long long)l.tick - p.lay.tick_lo;
         bin = bin < 0 ? 0 : bin > T - 1 ? T - 1 : bin;
         atomicAdd(&th[bin], 1u);
       }
@@ -157,58 +131,16 @@ __global__ __launch_bounds__(kStatsThreads) void cl_stats_kernel(StatsParams p) 
     for (int32_t ci = c_begin; ci < c_end; ++ci) {
       const StatsChunk ch = stats_chunk(N, rw, ci);
       const int32_t K = ch.nv * ch.kw, pitch = K | 1, w0 = ch.v0 * rw + ch.k0;
-      // ---- stage 64 rows x K words, in memory order
-      stats_wave_sync();  // (the previous chunk's readers are done with the tile)
-      if (p.blocked) {
-        // rows of node v: 64 records at pitch rw, nodes at pitch 64 * rw
-        const uint32_t* src = p.snap_nod + plane + (size_t)t * 64 * (size_t)N * (size_t)rw;
-        if (vec) {
-          const int32_t kq = ch.kw >> 2, per_node = 64 * kq;
-          for (int32_t f = lane; f < ch.nv * per_node; f += 64) {
-            const int32_t vl = f / per_node, rem = f - vl * per_node, r = rem / kq, q = rem - r * kq;
-            const uint4 x = *reinterpret_cast<const uint4*>(src + ((size_t)(ch.v0 + vl) * 64 + r) * rw + ch.k0 + 4 * q);
-            uint32_t* d = tile + r * pitch + vl * ch.kw + 4 * q;
-            d[0] = x.x, d[1] = x.y, d[2] = x.z, d[3] = x.w;
-          }
-        } else {
-          const int32_t per_node = 64 * ch.kw;
-          for (int32_t f = lane; f < ch.nv * per_node; f += 64) {
-            const int32_t vl = f / per_node, rem = f - vl * per_node, r = rem / ch.kw, k = rem - r * ch.kw;
-            tile[r * pitch + vl * ch.kw + k] = src[((size_t)(ch.v0 + vl) * 64 + r) * rw + ch.k0 + k];
-          }
-        }
-      } else {
-        // row r = instance 64 t + r: its K words start at word w0 of its N * rw
-        const uint32_t* src = p.snap_nod + plane + (size_t)t * 64 * (size_t)N * (size_t)rw + w0;
-        const size_t row = (size_t)N * (size_t)rw;
-        if (vec) {
-          const int32_t kq = K >> 2;
-          for (int32_t f = lane; f < 64 * kq; f += 64) {
-            const int32_t r = f / kq, q = f - r * kq;
-            const uint4 x = *reinterpret_cast<const uint4*>(src + r * row + 4 * q);
-            uint32_t* d = tile + r * pitch + 4 * q;
-            d[0] = x.x, d[1] = x.y, d[2] = x.z, d[3] = x.w;
-          }
-        } else {
-          for (int32_t f = lane; f < 64 * K; f += 64) {
-            const int32_t r = f / K, k = f - r * K;
-            tile[r * pitch + k] = src[r * row + k];
-          }
-        }
-      }
-      stats_wave_sync();
+      stage_tile(p.s, t, ch, tile, lane);  // 64 rows x K words, in memory order
 
       // ---- lane = slot: the instance's totals over this chunk's channel words
       if (p.totals && sample) {
         for (int32_t k = 0; k < K; ++k) {
           const int32_t c = p.word_ch[w0 + k];
           if (c < 0) continue;
-          const uint32_t rec = tile[lane * pitch + k], b = rec & 0xffffu, e = rec >> 16;
-          tot_msgs += e - b;
-          if (e != b) {
-            const long long* pre = p.hist_pre + p.hist_off[c] + c;
-            tot_tok += (unsigned long long)(pre[e] - pre[b]);
-          }
+          const uint32_t rec = tile[lane * pitch + k], cnt = rec_msgs(rec);
+          tot_msgs += cnt;
+          if (cnt) tot_tok += (unsigned long long)rec_tokens(rec, token_prefix(p.hist_pre, p.hist_off, c));
         }
       }
 
@@ -228,15 +160,14 @@ __global__ __launch_bounds__(kStatsThreads) void cl_stats_kernel(StatsParams p) 
             }
             fold(acc, AW, row, 0, a);
           } else {
-            const long long* pre = p.hist_pre + p.hist_off[c] + c;
+            const long long* pre = token_prefix(p.hist_pre, p.hist_off, c);
             uint32_t* h = mh + (size_t)row * M;
             for (unsigned long long m = mask; m; m &= m - 1) {
               const int32_t i = __builtin_ctzll(m);
-              const uint32_t rec = tile[i * pitch + k], b = rec & 0xffffu, e = rec >> 16;
-              const uint32_t cnt = e - b;
+              const uint32_t rec = tile[i * pitch + k], cnt = rec_msgs(rec);
               a.add_u32(cnt);
               // (the full 64 bits, as the lane = slot side keeps for the instance's total)
-              b2.add(e != b ? pre[e] - pre[b] : 0);
+              b2.add(rec_tokens(rec, pre));
               atomicAdd(&h[cnt < (uint32_t)(M - 1) ? cnt : (uint32_t)(M - 1)], 1u);
             }
             fold(acc, AW, row, 0, a);
@@ -252,17 +183,10 @@ __global__ __launch_bounds__(kStatsThreads) void cl_stats_kernel(StatsParams p) 
   }
 
   if (p.totals) {
-    for (int o = 32; o > 0; o >>= 1) {
-      n_all += __shfl_xor(n_all, o);
-      n_ok += __shfl_xor(n_ok, o);
-      n_sample += __shfl_xor(n_sample, o);
-    }
+    unsigned long long* u = (unsigned long long*)scal;
+    counts.fold_wave(u, lane);
     s_tick.wave_reduce(), s_msgs.wave_reduce(), s_infl.wave_reduce();
     if (lane == 0) {
-      unsigned long long* u = (unsigned long long*)scal;
-      if (n_all) atomicAdd(&u[0], n_all);
-      if (n_ok) atomicAdd(&u[1], n_ok);
-      if (n_sample) atomicAdd(&u[2], n_sample);
       const Stat4* s3[3] = {&s_tick, &s_msgs, &s_infl};
       for (int q = 0; q < 3; ++q) {
         if (s3[q]->sum) atomicAdd(&u[3 + 4 * q], s3[q]->sum);
@@ -286,10 +210,9 @@ __global__ __launch_bounds__(kStatsThreads) void cl_stats_kernel(StatsParams p) 
     if (v != kI64Min) atomicMax(p.out + at, v);
   };
   if (p.totals) {
+    unsigned long long* o = (unsigned long long*)p.out;
+    sample_counts_to_global((const unsigned long long*)scal, o + L.instances, o + L.ok, o + L.sample);
     if (threadIdx.x == 0) {
-      g_add(L.instances, (unsigned long long)scal[0]);
-      g_add(L.ok, (unsigned long long)scal[1]);
-      g_add(L.sample, (unsigned long long)scal[2]);
       const int64_t sum_at[3] = {L.tick_sum, L.msgs_sum, L.inflight_sum};
       const int64_t sq_at[3] = {L.tick_sumsq, L.msgs_sumsq, L.inflight_sumsq};
       for (int q = 0; q < 3; ++q) {

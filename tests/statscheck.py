@@ -13,6 +13,14 @@ from enginecheck import oracle_run
 
 I64_MAX, I64_MIN = np.iinfo(np.int64).max, np.iinfo(np.int64).min
 
+# A 5-node ring, max in-degree 1: a node record has 2 words, an instance's 10 record words are
+# staged in LDS with scalar loads (rw % 4 != 0).  R2 starts with one token, so many instances
+# end with insufficient tokens.  Shared by the statistics, census and select tests.
+RING_TOP = "5\nR0 6\nR1 6\nR2 1\nR3 6\nR4 6\nR0 R1\nR1 R2\nR2 R3\nR3 R4\nR4 R0\n"
+_RND = "send R0 R1 1\nsend R1 R2 2\nsend R3 R4 1\nsend R0 R1 1\ntick 1\n"
+RING_EVENTS = (_RND * 2 + "snapshot R2\n" + "send R4 R0 1\nsend R2 R3 1\ntick 1\n" * 2
+               + "snapshot R0\nsend R0 R1 1\nsend R2 R3 1\ntick 2\n")
+
 
 class Rows:
     """Per-instance oracle results of one scenario: status[n], and per snapshot id the sample

@@ -14,6 +14,7 @@ import pytest
 
 import oracle as O
 from selectcheck import assert_selection_equal, expected, from_refs, scenario
+from statscheck import RING_EVENTS, RING_TOP
 from test_census_gpu import (AUTO, C3_EVENTS, C3_TOP, ENGINES, EVENTS3, HUB_EVENTS, HUB_TOP, TOP3, both_layouts,
                              flush_on, make_sim, replay_blocked)
 
@@ -183,6 +184,30 @@ def test_hub_three_word_records_block_major():
         wheres = hub_wheres(rows, keys, sid, N)
         assert 0 < n_match(rows, keys, sid, wheres[4]) < N
         check(sim, rows, keys, sid, RANGES, wheres, "hub after rerun")
+
+
+# ---- 4b: node records of 2 words, 10 record words: staged in LDS word by word ----------------------
+def test_ring_two_word_records_both_layouts():
+    rows, keys = scenario(RING_TOP, RING_EVENTS, N)
+    assert rows.n_sids == 2
+    assert int((rows.status == O.OK).sum()) == 2417
+    assert int((rows.status == O.FATAL_INSUFFICIENT_TOKENS).sum()) == 1679
+    wheres = [
+        [("msgs", None, 2, None)],
+        [("ch_tok", 1, 2, None)],
+        [("node", 2, 0, 1), ("tick", None, None, 12)],
+        [("inflight", None, 1, 2, "not")],
+    ]
+    assert [[n_match(rows, keys, sid, w) for sid in range(2)] for w in wheres] == [[813, 1403], [2238, 0], [13, 0],
+                                                                                  [992, 100]]
+    sim = make_sim(RING_TOP, RING_EVENTS, N, AUTO)
+    assert sim.num_nodes == 5 and sim.num_channels == 5     # max in-degree 1: rec_words gives rw = 2
+
+    def body(what):
+        for sid in range(2):
+            check(sim, rows, keys, sid, RANGES, wheres + [[]], "ring " + what)
+
+    both_layouts(sim, AUTO, body)
 
 
 # ---- 5: incomplete snapshots never match; the bulk ticks -------------------------------------------
