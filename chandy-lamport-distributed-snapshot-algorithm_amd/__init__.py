@@ -20,7 +20,8 @@ import numpy as np
 
 __all__ = ["ChandyLamportSim", "SnapshotStats", "STATS_LAYOUT_FIELDS", "SnapshotSelection", "SELECT_CLAUSE_DTYPE",
 "GlobalSnapshot", "MsgSnapshot", "PassTokenEvent", "SnapshotEvent",
-           "ClSnapError", "lib", "go_delay_schedule", "go_int63", "go_intn", "REFERENCE_SEED",
+           "ClSnapError", "lib", "go_delay_schedule", "go_delay_schedule_device", "go_delay_schedule_jump",
+           "DELAYGEN_MAX_DRAWS", "go_int63", "go_intn", "REFERENCE_SEED",
            "INST_OK", "INST_FATAL_INSUFFICIENT_TOKENS", "INST_FATAL_UNKNOWN_DEST",
            "INST_FIFO_OVERFLOW", "INST_HANG", "INST_DELAY_EXHAUSTED", "COUNTER_NAMES",
            "SUM_NAMES", "MAX_DELAY", "E_INVALID", "E_UNKNOWN_NODE", "E_DUPLICATE_NODE", "E_PARSE",
@@ -33,6 +34,7 @@ if os.environ.get("CLSNAP_VARIANT"):  # diagnostic ablation builds (Makefile `va
 
 REFERENCE_SEED = 8053172852482175523 + 1  # snapshot_test.go:9,20 rand.Seed(seed + 1)
 MAX_DELAY = 5                              # sim.go:10
+DELAYGEN_MAX_DRAWS = 4096                  # include/clsnap.h CL_DELAYGEN_MAX_DRAWS
 
 (INST_OK, INST_FATAL_INSUFFICIENT_TOKENS, INST_FATAL_UNKNOWN_DEST, INST_FIFO_OVERFLOW,
  INST_HANG, INST_DELAY_EXHAUSTED) = range(6)
@@ -133,6 +135,12 @@ def lib():
         "cl_select_time": [vp, vp],
         "cl_select_stage_times": [vp, vp, vp],
         "cl_snapshot_ticks": [vp, i32, i64, i64, vp],
+        "cl_set_delay_go_seed_list": [vp, vp, i64],
+        "cl_set_delay_generator": [vp, i32],
+        "cl_delay_generator": [vp, vp],
+        "cl_delay_gen_time": [vp, vp, vp, vp],
+        "cl_go_delay_schedule_jump": [i64, vp, i64, i64, vp, vp],
+        "cl_go_delay_schedule_device": [i32, i64, vp, i64, i64, vp, vp, vp],
     }
     for name, args in sig.items():
         if os.environ.get("CLSNAP_VARIANT") and not hasattr(L, name):
@@ -197,6 +205,40 @@ def go_delay_schedule(seed_base, n, draws):
     out = np.empty((n, draws), dtype=np.uint8)
     _check(lib().cl_go_delay_schedule(seed_base, n, draws, _p(out)))
     return out
+
+
+def _seed_rows(seed_base, n, seeds):
+    """(seed_base, seeds array or None, n) of the schedule utilities: ``seeds`` overrides both."""
+    if seeds is None:
+        if n is None:
+            raise ClSnapError(E_INVALID, "give n (rows of seed_base + i) or seeds")
+        return int(seed_base), None, int(n)
+    s = np.ascontiguousarray(seeds, dtype=np.int64)
+    if s.ndim != 1 or (n is not None and int(n) != s.size):
+        raise ClSnapError(E_INVALID, "seeds must be int64[n]")
+    return 0, s, int(s.size)
+
+
+def go_delay_schedule_jump(seed_base=0, n=None, draws=0, seeds=None, return_info=False):
+    """go_delay_schedule from the generator's closed form (csrc/cl_gorand.h), on the host: row i
+    from ``seeds[i]``, or from ``seed_base + i``.  With return_info: (schedule, rows that met an
+    Intn rejection and were regenerated sequentially)."""
+    base, s, n = _seed_rows(seed_base, n, seeds)
+    out = np.empty((n, draws), dtype=np.uint8)
+    rej = C.c_int64(0)
+    _check(lib().cl_go_delay_schedule_jump(base, None if s is None else _p(s), n, draws, _p(out), C.byref(rej)))
+    return (out, rej.value) if return_info else out
+
+
+def go_delay_schedule_device(seed_base=0, n=None, draws=0, seeds=None, device=0, return_info=False):
+    """go_delay_schedule generated by the gfx950 kernel (cl_go_delay_schedule_device) and copied
+    back.  With return_info: (schedule, rows patched on the host, kernel ms)."""
+    base, s, n = _seed_rows(seed_base, n, seeds)
+    out = np.empty((n, draws), dtype=np.uint8)
+    patched, ms = C.c_int64(0), C.c_double(0)
+    _check(lib().cl_go_delay_schedule_device(device, base, None if s is None else _p(s), n, draws, _p(out),
+                                             C.byref(patched), C.byref(ms)))
+    return (out, patched.value, ms.value) if return_info else out
 
 
 def go_int63(seed, n):
@@ -822,6 +864,36 @@ class ChandyLamportSim:
 
     def set_delay_go_seeds(self, seed_base):
         _check(self._L.cl_set_delay_go_seeds(self._h, seed_base))
+
+    def set_delay_go_seed_list(self, seeds):
+        """Instance i draws from rand.Seed(seeds[i]) (cl_set_delay_go_seed_list): e.g. the instances
+        a selection named, re-run as their own batch with ``seed_base + insts``."""
+        s = np.ascontiguousarray(seeds, dtype=np.int64)
+        if s.ndim != 1:
+            raise ClSnapError(E_INVALID, "seeds must be int64[n_instances]")
+        _check(self._L.cl_set_delay_go_seed_list(self._h, _p(s), s.size))
+
+    DELAY_GENERATORS = ("host", "device")
+
+    def set_delay_generator(self, generator):
+        """"host" (default) or "device": who makes the Go streams' delay rows (cl_set_delay_generator);
+        the rows are the same bytes either way."""
+        if generator not in self.DELAY_GENERATORS:
+            raise ClSnapError(E_INVALID, f"delay generator must be one of {self.DELAY_GENERATORS}")
+        _check(self._L.cl_set_delay_generator(self._h, self.DELAY_GENERATORS.index(generator)))
+
+    @property
+    def delay_generator(self):
+        """The generator that made the rows now on the device: "host", "device", or None before any
+        rows exist and for an explicit schedule."""
+        m = self._i32(self._L.cl_delay_generator)
+        return None if m < 0 else self.DELAY_GENERATORS[m]
+
+    def delay_gen_time(self):
+        """(kernel ms, host ms, rows patched on the host) of the latest delay generation."""
+        d, h, p = C.c_double(0), C.c_double(0), C.c_int64(0)
+        _check(self._L.cl_delay_gen_time(self._h, C.byref(d), C.byref(h), C.byref(p)))
+        return d.value, h.value, p.value
 
     def set_limits(self, fifo_lds_slots=0, max_drain_ticks=10000):
         _check(self._L.cl_set_limits(self._h, fifo_lds_slots, max_drain_ticks))

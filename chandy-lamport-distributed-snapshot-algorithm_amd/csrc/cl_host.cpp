@@ -30,6 +30,7 @@
 
 #include "../../include/clsnap.h"
 #include "cl_engine.h"
+#include "cl_gorand.h"
 #include "cl_text.h"
 
 using namespace clsnap;
@@ -73,11 +74,9 @@ int set_err(int code, const char* fmt, ...) {
 
 // ---------------------------------------------------------------------------
 // Go math/rand (Go 1.22, go.mod:3): rngSource seeded as in rng.go, Intn -> Int31n.
-// rngCooked is regenerated offline by oracle/gen_go_rng_cooked.py (KAT-pinned).
+// rngCooked (cl_gorand.h) is regenerated offline by oracle/gen_go_rng_cooked.py (KAT-pinned).
 // ---------------------------------------------------------------------------
-const int64_t kRngCooked[607] = {
-#include "go_rng_cooked.inc"
-};
+using gorand::kRngCooked;
 
 struct GoRand {
   int tap = 0, feed = 334;
@@ -129,19 +128,59 @@ int host_threads() {
   return (int)std::min(n, 16u);  // the GPU box grants 16 host cores per GPU
 }
 
-void go_schedule(int64_t seed_base, int64_t n, int64_t draws, uint8_t* out) {
+// seed of instance i: seeds[i], or seed_base + i (wrapping) without a list
+inline int64_t seed_of(int64_t seed_base, const int64_t* seeds, int64_t i) {
+  return seeds ? seeds[i] : (int64_t)((uint64_t)seed_base + (uint64_t)i);
+}
+
+void go_row(int64_t seed, int64_t draws, uint8_t* o) {
+  GoRand r(seed);
+  for (int64_t k = 0; k < draws; ++k) o[k] = (uint8_t)r.int31n(5);  // rand.Intn(maxDelay)
+}
+
+void go_schedule(int64_t seed_base, const int64_t* seeds, int64_t n, int64_t draws, uint8_t* out) {
   const int T = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), (n + 255) / 256));
   std::vector<std::thread> th;
   for (int t = 0; t < T; ++t) {
     th.emplace_back([=] {
+      for (int64_t i = n * t / T; i < n * (t + 1) / T; ++i) go_row(seed_of(seed_base, seeds, i), draws, out + i * draws);
+    });
+  }
+  for (auto& x : th) x.join();
+}
+
+// The same plane from the closed form of cl_gorand.h, row by row as the device generator computes
+// it; a row that met a rejection is regenerated sequentially.  Returns the number of such rows.
+int64_t go_schedule_jump(int64_t seed_base, const int64_t* seeds, int64_t n, int64_t draws, uint8_t* out) {
+  static const std::vector<uint32_t> pw = [] {
+    std::vector<uint32_t> t(gorand::kPowN);
+    gorand::build_pow_table(t.data());
+    return t;
+  }();
+  const int T = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), (n + 255) / 256));
+  std::atomic<int64_t> rejected{0};
+  std::vector<std::thread> th;
+  for (int t = 0; t < T; ++t) {
+    th.emplace_back([=, &rejected] {
+      std::vector<uint64_t> o((size_t)draws + 1);
       for (int64_t i = n * t / T; i < n * (t + 1) / T; ++i) {
-        GoRand r(seed_base + i);
-        uint8_t* o = out + i * draws;
-        for (int64_t k = 0; k < draws; ++k) o[k] = (uint8_t)r.int31n(5);  // rand.Intn(maxDelay)
+        const int64_t seed = seed_of(seed_base, seeds, i);
+        const uint32_t x0 = gorand::norm_seed(seed);
+        uint8_t* row = out + i * draws;
+        bool rej = false;
+        for (int64_t k = 1; k <= draws; ++k) {
+          o[(size_t)k] = gorand::output(x0, (int32_t)k, pw.data(), kRngCooked, o.data());
+          row[k - 1] = (uint8_t)gorand::intn5(o[(size_t)k], &rej);
+        }
+        if (rej) {
+          go_row(seed, draws, row);
+          ++rejected;
+        }
       }
     });
   }
   for (auto& x : th) x.join();
+  return rejected.load();
 }
 
 #define HIP_TRY(expr)                                                                     \
@@ -170,6 +209,72 @@ struct DevBuf {
     n = 0;
   }
 };
+
+// ---- the device generator (cl_gorand.hip) and its host-side patching ---------------------------
+// Shapes it takes: rows up to the documented cap, a plane of fewer than 2^31 dwords.
+bool delaygen_fits(int64_t n, int64_t row) {
+  return n >= 1 && row >= 4 && row <= CL_DELAYGEN_MAX_DRAWS && n * (row / 4) < (1ll << 31);
+}
+
+struct DeviceGen {
+  double device_ms = 0, host_ms = 0;
+  int64_t patched = 0;
+  bool overflow = false;  // more flagged rows than the list holds: nothing was patched
+};
+
+// Generate the [n][row] plane at d_plane on `stream` (seeds: d_seeds, a device array, or
+// seed_base + i), wait, and regenerate the rows that met a rejection among their first `draws`
+// outputs with the sequential generator.  d_flag has 1 + kDelayGenFlagCap words; ev two events.
+int device_generate(int device, hipStream_t stream, int32_t n_cus, int64_t seed_base, const long long* d_seeds,
+                    int64_t n, int64_t row, int64_t draws, uint8_t* d_plane, unsigned long long* d_flag,
+                    hipEvent_t* ev, DeviceGen* g) {
+  const void* tables = nullptr;
+  int e = gorand::delaygen_tables(device, &tables);
+  if (e) return set_err(CL_E_DEVICE, "delay generator tables: %s", hipGetErrorString((hipError_t)e));
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(unsigned long long), stream));
+  gorand::DelayGenParams p{};
+  p.plane = d_plane;
+  p.seeds = d_seeds;
+  p.seed_base = seed_base;
+  p.n_inst = n;
+  p.row = (int32_t)row;
+  p.draws = (int32_t)draws;
+  p.flagged = d_flag;
+  p.flag_cap = gorand::kDelayGenFlagCap;
+  p.tables = tables;
+  HIP_TRY(hipEventRecord(ev[0], stream));
+  e = gorand::launch_delaygen(p, n_cus, stream);
+  if (e) return set_err(CL_E_DEVICE, "delay generator launch failed: %s", hipGetErrorString((hipError_t)e));
+  HIP_TRY(hipEventRecord(ev[1], stream));
+  unsigned long long cnt = 0;
+  HIP_TRY(hipMemcpyAsync(&cnt, d_flag, sizeof cnt, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  const auto t0 = std::chrono::steady_clock::now();
+  *g = DeviceGen{};
+  if (cnt > (unsigned long long)gorand::kDelayGenFlagCap) {
+    g->overflow = true;
+  } else if (cnt) {
+    std::vector<unsigned long long> rows((size_t)cnt);
+    HIP_TRY(hipMemcpy(rows.data(), d_flag + 1, (size_t)cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    std::sort(rows.begin(), rows.end());
+    rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+    std::vector<uint8_t> buf((size_t)row);
+    for (unsigned long long i : rows) {
+      if (i >= (unsigned long long)n) return set_err(CL_E_DEVICE, "delay generator flagged row %llu of %lld", i, (long long)n);
+      long long seed = (long long)((uint64_t)seed_base + (uint64_t)i);
+      if (d_seeds) HIP_TRY(hipMemcpy(&seed, d_seeds + i, sizeof seed, hipMemcpyDeviceToHost));
+      go_row((int64_t)seed, row, buf.data());
+      HIP_TRY(hipMemcpy(d_plane + (size_t)i * (size_t)row, buf.data(), (size_t)row, hipMemcpyHostToDevice));
+    }
+    g->patched = (int64_t)rows.size();
+  }
+  g->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  g->device_ms = ms;
+  return CL_OK;
+}
 
 }  // namespace
 
@@ -241,6 +346,17 @@ struct cl_sim {
   int64_t user_draws = 0;
   int64_t dev_draws = -1;  // valid draws per instance of the schedule resident on the device
   int64_t dev_row = 0;     // its row stride (multiple of 16)
+  // Go streams: which generator makes the rows (cl_set_delay_generator) and which made the rows
+  // now on the device; per-instance seeds (cl_set_delay_go_seed_list) replace seed_base + i.  The
+  // list lives on the host until the device generator first needs it, then in d_seeds only (the
+  // host generator fetches it back).
+  int32_t delaygen = CL_DELAYGEN_HOST;
+  int32_t dev_gen = -1;
+  bool seed_list = false, seeds_on_dev = false;
+  std::vector<int64_t> h_seeds;
+  bool dg_timed = false;  // a generation has run: the three figures of cl_delay_gen_time
+  double dg_device_ms = 0, dg_host_ms = 0;
+  int64_t dg_patched = 0;
 
   // device
   bool dev_ready = false;
@@ -302,6 +418,9 @@ struct cl_sim {
   DevBuf<uint32_t> d_topo;
   DevBuf<int32_t> d_fin_tok;
   DevBuf<uint8_t> d_sched;
+  DevBuf<long long> d_seeds;              // [n_inst] the seed list, once the device generator ran with it
+  DevBuf<unsigned long long> d_dg_flag;   // device generator: count, then the rows that met a rejection
+  hipEvent_t dg_ev[2] = {nullptr, nullptr};
   DevBuf<uint32_t> d_state;
   DevBuf<int32_t> d_regs;
   DevBuf<uint32_t> d_snap_nod;  // [s_cap][stride][n][lay.rw] node snapshot records
@@ -414,6 +533,9 @@ struct cl_sim {
       d_cs_table.release(); d_cs_out.release(); d_cs_list.release(); d_cs_info.release(); d_cs_keys.release();
       d_cs_class.release(); d_cs_rank.release(); d_pk_list.release();
       d_sel_bits.release(); d_sel_info.release(); d_sel_bsum.release(); d_sel_out.release(); d_sel_ticks.release();
+      d_seeds.release(); d_dg_flag.release();
+      for (auto& e : dg_ev)
+        if (e) (void)hipEventDestroy(e);
       for (auto& e : sel_ev)
         if (e) (void)hipEventDestroy(e);
       for (auto& e : cs_ev)
@@ -547,17 +669,77 @@ struct cl_sim {
     return CL_OK;
   }
 
+  // (the generator's kernel has finished whenever an ABI call returns: nothing reads d_seeds then)
+  void drop_seed_list() {
+    seed_list = seeds_on_dev = false;
+    std::vector<int64_t>().swap(h_seeds);
+    if (dev_ready && d_seeds.p) {
+      (void)hipSetDevice(device);
+      d_seeds.release();
+    }
+  }
+
+  // Rows of D draws from the device generator, on the sim's stream, straight into d_sched.
+  // *done = false when more rows met a rejection than its list holds (the caller then takes the
+  // host generator).
+  int generate_on_device(int64_t D, bool* done) {
+    int rc;
+    HIP_TRY(hipStreamSynchronize(stream));  // (an async launch may read d_sched)
+    dev_draws = -1;                         // (the rows on the device are about to be overwritten)
+    if ((rc = d_sched.ensure((size_t)(D * n_inst)))) return rc;
+    if ((rc = d_dg_flag.ensure(1 + (size_t)gorand::kDelayGenFlagCap))) return rc;
+    if (seed_list && !seeds_on_dev) {
+      if ((rc = d_seeds.ensure((size_t)n_inst))) return rc;
+      HIP_TRY(hipMemcpy(d_seeds.p, h_seeds.data(), (size_t)n_inst * sizeof(int64_t), hipMemcpyHostToDevice));
+      std::vector<int64_t>().swap(h_seeds);
+      seeds_on_dev = true;
+    }
+    for (auto& e : dg_ev)
+      if (!e) HIP_TRY(hipEventCreate(&e));
+    if (!n_cus) HIP_TRY(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device));
+    DeviceGen g;
+    if ((rc = device_generate(device, stream, n_cus, seed_base, seed_list ? d_seeds.p : nullptr, n_inst, D, D,
+                              d_sched.p, d_dg_flag.p, dg_ev, &g)))
+      return rc;
+    *done = !g.overflow;
+    if (g.overflow) return CL_OK;
+    dg_device_ms = g.device_ms;
+    dg_host_ms = g.host_ms;
+    dg_patched = g.patched;
+    dg_timed = true;
+    dev_gen = CL_DELAYGEN_DEVICE;
+    return CL_OK;
+  }
+
   int ensure_delays() {
     int64_t need = draws_needed();
     if (go_seeds) {
       int64_t D = std::max<int64_t>(16, (need + 15) / 16 * 16);
       if (dev_draws >= D) return CL_OK;
-      std::vector<uint8_t> sched((size_t)(D * n_inst));
-      go_schedule(seed_base, n_inst, D, sched.data());
-      if (dev_ready) HIP_TRY(hipStreamSynchronize(stream));  // (an async launch may read d_sched)
-      int rc = d_sched.ensure(sched.size());
-      if (rc) return rc;
-      HIP_TRY(hipMemcpy(d_sched.p, sched.data(), sched.size(), hipMemcpyHostToDevice));
+      int rc;
+      bool on_device = delaygen == CL_DELAYGEN_DEVICE && delaygen_fits(n_inst, D);
+      if (on_device) {
+        if ((rc = generate_on_device(D, &on_device))) return rc;
+      }
+      if (!on_device) {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (seed_list && seeds_on_dev) {  // (the list goes back to the host generator's side)
+          h_seeds.resize((size_t)n_inst);
+          HIP_TRY(hipMemcpy(h_seeds.data(), d_seeds.p, (size_t)n_inst * sizeof(int64_t), hipMemcpyDeviceToHost));
+          d_seeds.release();
+          seeds_on_dev = false;
+        }
+        std::vector<uint8_t> sched((size_t)(D * n_inst));
+        go_schedule(seed_base, seed_list ? h_seeds.data() : nullptr, n_inst, D, sched.data());
+        if (dev_ready) HIP_TRY(hipStreamSynchronize(stream));  // (an async launch may read d_sched)
+        if ((rc = d_sched.ensure(sched.size()))) return rc;
+        HIP_TRY(hipMemcpy(d_sched.p, sched.data(), sched.size(), hipMemcpyHostToDevice));
+        dg_device_ms = 0;
+        dg_host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        dg_patched = 0;
+        dg_timed = true;
+        dev_gen = CL_DELAYGEN_HOST;
+      }
       dev_draws = D;  // longer rows of the same streams: saved draw cursors stay valid
       plan_ops = plan_tried = -1;
       dev_row = D;
@@ -1601,8 +1783,49 @@ int cl_set_delay_go_seeds(cl_sim* sim, int64_t seed_base) {
   sim->plan_ops = sim->plan_tried = -1;
   sim->go_seeds = true;
   sim->seed_base = seed_base;
+  sim->drop_seed_list();
   sim->dev_draws = -1;
   sim->need_fresh = true;
+  return CL_OK;
+}
+
+int cl_set_delay_go_seed_list(cl_sim* sim, const int64_t* seeds, int64_t n) {
+  SIM_CHECK(sim);
+  if (!seeds || n != sim->n_inst) return set_err(CL_E_INVALID, "the seed list must have one seed per instance");
+  sim->plan_ops = sim->plan_tried = -1;
+  sim->drop_seed_list();
+  sim->h_seeds.assign(seeds, seeds + n);
+  sim->seed_list = true;
+  sim->go_seeds = true;
+  sim->dev_draws = -1;
+  sim->need_fresh = true;
+  return CL_OK;
+}
+
+int cl_set_delay_generator(cl_sim* sim, int32_t mode) {
+  SIM_CHECK(sim);
+  if (mode != CL_DELAYGEN_HOST && mode != CL_DELAYGEN_DEVICE) return set_err(CL_E_INVALID, "unknown delay generator %d", mode);
+  if (mode == sim->delaygen) return CL_OK;
+  sim->delaygen = mode;
+  sim->plan_ops = sim->plan_tried = -1;
+  sim->dev_draws = -1;  // the next launch generates the rows again, with this generator
+  sim->need_fresh = true;
+  return CL_OK;
+}
+
+int cl_delay_generator(cl_sim* sim, int32_t* mode) {
+  SIM_CHECK(sim);
+  if (!mode) return set_err(CL_E_INVALID, "null output");
+  *mode = sim->go_seeds && sim->dev_draws >= 0 ? sim->dev_gen : -1;
+  return CL_OK;
+}
+
+int cl_delay_gen_time(cl_sim* sim, double* device_ms, double* host_ms, int64_t* patched_rows) {
+  SIM_CHECK(sim);
+  if (!sim->dg_timed) return set_err(CL_E_STATE, "no delay generation has run");
+  if (device_ms) *device_ms = sim->dg_device_ms;
+  if (host_ms) *host_ms = sim->dg_host_ms;
+  if (patched_rows) *patched_rows = sim->dg_patched;
   return CL_OK;
 }
 
@@ -1616,6 +1839,7 @@ int cl_set_delay_schedule(cl_sim* sim, const uint8_t* delays, int64_t draws_per_
   sim->user_sched.assign(delays, delays + n);
   sim->user_draws = draws_per_instance;
   sim->go_seeds = false;
+  sim->drop_seed_list();
   sim->dev_draws = -1;
   sim->need_fresh = true;
   return CL_OK;
@@ -1927,6 +2151,7 @@ int cl_device_bytes(const cl_sim* sim, int64_t* bytes) {
   b += sim->d_ovh.n * 4 + sim->d_hist.n * 4 + sim->d_sums.n * 8 + sim->d_fin_tok.n * 4;
   b += sim->d_sel_bits.n * 8 + sim->d_sel_info.n * 8 + sim->d_sel_bsum.n * 8 + sim->d_sel_out.n * 8 +
        sim->d_sel_ticks.n * 4;  // (the selection's scratch, once a selection has run)
+  b += sim->d_seeds.n * 8 + sim->d_dg_flag.n * 8;  // (the seed list and the device generator's flagged rows)
   *bytes = b;
   return CL_OK;
 }
@@ -2354,7 +2579,70 @@ int cl_instance_hashes(cl_sim* sim, int64_t lo, int64_t n, uint64_t* out) {
 
 int cl_go_delay_schedule(int64_t seed_base, int64_t n, int64_t draws, uint8_t* out) {
   if (!out || n < 0 || draws < 0) return set_err(CL_E_INVALID, "bad arguments");
-  go_schedule(seed_base, n, draws, out);
+  go_schedule(seed_base, nullptr, n, draws, out);
+  return CL_OK;
+}
+
+int cl_go_delay_schedule_jump(int64_t seed_base, const int64_t* seeds, int64_t n, int64_t draws, uint8_t* out,
+                              int64_t* rejected_rows) {
+  if (!out || n < 0 || draws < 0 || draws > (1 << 30)) return set_err(CL_E_INVALID, "bad arguments");
+  const int64_t r = go_schedule_jump(seed_base, seeds, n, draws, out);
+  if (rejected_rows) *rejected_rows = r;
+  return CL_OK;
+}
+
+int cl_go_delay_schedule_device(int32_t device, int64_t seed_base, const int64_t* seeds, int64_t n, int64_t draws,
+                                uint8_t* out, int64_t* patched_rows, double* device_ms) {
+  if (!out || n < 0 || draws < 0) return set_err(CL_E_INVALID, "bad arguments");
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+    return set_err(CL_E_DEVICE, "no HIP device available (the engine needs a gfx950 GPU)");
+  if (device < 0 || device >= count) return set_err(CL_E_DEVICE, "device %d out of range (%d)", device, count);
+  HIP_TRY(hipSetDevice(device));
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return set_err(CL_E_DEVICE, "device %d is %s, the engine is built for gfx950", device, prop.gcnArchName);
+  if (patched_rows) *patched_rows = 0;
+  if (device_ms) *device_ms = 0;
+  if (n == 0 || draws == 0) return CL_OK;
+  const int64_t row = std::max<int64_t>(16, (draws + 15) / 16 * 16);  // the engine's row padding
+  if (!delaygen_fits(n, row)) {  // above the cap: the host generator, as in the engine
+    go_schedule(seed_base, seeds, n, draws, out);
+    return CL_OK;
+  }
+  struct Scratch {  // (freed on every return path)
+    DevBuf<uint8_t> plane;
+    DevBuf<long long> seeds;
+    DevBuf<unsigned long long> flag;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~Scratch() {
+      plane.release(), seeds.release(), flag.release();
+      for (auto& e : ev)
+        if (e) (void)hipEventDestroy(e);
+      if (stream) (void)hipStreamDestroy(stream);
+    }
+  } s;
+  int rc;
+  if ((rc = s.plane.ensure((size_t)(n * row))) || (rc = s.flag.ensure(1 + (size_t)gorand::kDelayGenFlagCap))) return rc;
+  if (seeds) {
+    if ((rc = s.seeds.ensure((size_t)n))) return rc;
+    HIP_TRY(hipMemcpy(s.seeds.p, seeds, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+  for (auto& e : s.ev) HIP_TRY(hipEventCreate(&e));
+  DeviceGen g;
+  if ((rc = device_generate(device, s.stream, prop.multiProcessorCount, seed_base, seeds ? s.seeds.p : nullptr, n, row,
+                            draws, s.plane.p, s.flag.p, s.ev, &g)))
+    return rc;
+  if (g.overflow) {  // more flagged rows than the list holds: the host generator, as in the engine
+    go_schedule(seed_base, seeds, n, draws, out);
+    return CL_OK;
+  }
+  HIP_TRY(hipMemcpy2D(out, (size_t)draws, s.plane.p, (size_t)row, (size_t)draws, (size_t)n, hipMemcpyDeviceToHost));
+  if (patched_rows) *patched_rows = g.patched;
+  if (device_ms) *device_ms = g.device_ms;
   return CL_OK;
 }
 

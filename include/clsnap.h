@@ -118,6 +118,37 @@ int cl_set_delay_go_seeds(cl_sim* sim, int64_t seed_base);
 /* Explicit schedule: delays[i * draws_per_instance + k] in [0, 5) is the k-th draw
  * of instance i.  Copied; the caller may free it after the call. */
 int cl_set_delay_schedule(cl_sim* sim, const uint8_t* delays, int64_t draws_per_instance);
+/* Go stream with one seed per instance: instance i draws from rand.Seed(seeds[i]); any int64 is a
+ * seed (rng.go reduces it mod 2^31 - 1).  E.g. the instances cl_select_instances named, re-run as
+ * a batch of their own with seeds[k] = seed_base + insts[k].  n must be the instance count
+ * (CL_E_INVALID otherwise, and for NULL); the list is copied.  Works with both generators below;
+ * replaces, and is replaced by, cl_set_delay_go_seeds and cl_set_delay_schedule. */
+int cl_set_delay_go_seed_list(cl_sim* sim, const int64_t* seeds, int64_t n);
+/* Which generator makes the Go streams' delay rows:
+ *   CL_DELAYGEN_HOST    (default) sequential generators on up to 16 host threads, then one copy
+ *                       of the n_instances x row plane to the device
+ *   CL_DELAYGEN_DEVICE  a gfx950 kernel writes the plane in device memory from the generator's
+ *                       closed form; no host plane, no copy.  A row in which Go's
+ *                       Intn(5) rejects an output and draws again (about one row in 6 million at
+ *                       100 draws) is regenerated sequentially on the host and patched in.  The
+ *                       seed list, if any, then lives in device memory only.
+ * The rows are the same bytes either way.  Rows longer than CL_DELAYGEN_MAX_DRAWS (one wave
+ * keeps a row's 8-byte outputs in LDS), planes of 2^31 dwords or more, and batches in which more
+ * than 4,096 rows met a rejection silently take the host generator; cl_delay_generator tells.
+ * CL_E_INVALID for another mode.  Like cl_set_delay_go_seeds it may be called at any time: a
+ * change makes the next flush generate the rows again and replay the program from the start. */
+#define CL_DELAYGEN_HOST 0
+#define CL_DELAYGEN_DEVICE 1
+#define CL_DELAYGEN_MAX_DRAWS 4096
+int cl_set_delay_generator(cl_sim* sim, int32_t mode);
+/* The generator that made the rows now on the device (CL_DELAYGEN_*); -1 before any rows exist
+ * and for an explicit schedule. */
+int cl_delay_generator(cl_sim* sim, int32_t* mode);
+/* The latest generation of Go-stream rows (CL_E_STATE before any): device_ms = the generator
+ * kernel, from HIP events around it (0 for the host generator); host_ms = wall time of the host
+ * generator and its copy, or of patching the rejected rows; patched_rows = rows regenerated on
+ * the host after the kernel.  Any of the three pointers may be NULL. */
+int cl_delay_gen_time(cl_sim* sim, double* device_ms, double* host_ms, int64_t* patched_rows);
 
 /* ProcessEvent(PassTokenEvent) -> SendTokens (sim.go:58-62; node.go:112-131). */
 int cl_send_tokens(cl_sim* sim, const char* src, const char* dest, int64_t n);
@@ -442,9 +473,23 @@ int cl_trace_enable(cl_sim* sim, int64_t inst_lo, int32_t n_inst, int32_t cap);
  * copied to out.  CL_E_LIMIT if the instance emitted more than the enabled capacity. */
 int cl_trace_read(cl_sim* sim, int64_t inst, cl_log_event* out, int32_t cap, int32_t* n_events);
 
-/* ---- delay-stream utility (host only) ------------------------------------ */
+/* ---- delay-stream utility (host only, but for cl_go_delay_schedule_device) -- */
 /* out[i*draws + k] = k-th rand.Intn(5) of rand.Seed(seed_base + i), i in [0, n). */
 int cl_go_delay_schedule(int64_t seed_base, int64_t n, int64_t draws, uint8_t* out);
+/* The same schedule from the closed form the device generator evaluates (csrc/cl_gorand.h), on
+ * the host, no device needed: row i from seeds[i], or from seed_base + i when seeds is NULL.  A
+ * row in which Intn(5) rejects an output is regenerated sequentially; *rejected_rows (may be
+ * NULL) counts them. */
+int cl_go_delay_schedule_jump(int64_t seed_base, const int64_t* seeds /* [n] or NULL */, int64_t n, int64_t draws,
+                              uint8_t* out, int64_t* rejected_rows);
+/* The device form (needs a gfx950 device, CL_E_DEVICE otherwise): the generator kernel writes
+ * the plane in device memory with the engine's row padding, the host patches the rows that met
+ * a rejection, and the plane is copied back to out[n * draws].  *patched_rows and *device_ms
+ * (either may be NULL) as in cl_delay_gen_time.  Where the engine would take the host generator
+ * (see cl_set_delay_generator: a shape the kernel does not take, or more than 4,096 rows that met
+ * a rejection) the schedule comes from the host generator, and *patched_rows and *device_ms are 0. */
+int cl_go_delay_schedule_device(int32_t device, int64_t seed_base, const int64_t* seeds /* [n] or NULL */, int64_t n,
+                                int64_t draws, uint8_t* out, int64_t* patched_rows, double* device_ms);
 /* Go math/rand Int63 / Intn restatement, for known-answer tests. */
 int cl_go_int63(int64_t seed, int64_t n, int64_t* out);
 int cl_go_intn(int64_t seed, int32_t bound, int64_t n, int32_t* out);
