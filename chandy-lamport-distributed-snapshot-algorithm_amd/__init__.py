@@ -19,6 +19,7 @@ import os
 import numpy as np
 
 __all__ = ["ChandyLamportSim", "SnapshotStats", "STATS_LAYOUT_FIELDS", "SnapshotSelection", "SELECT_CLAUSE_DTYPE",
+           "InstanceSet",
 "GlobalSnapshot", "MsgSnapshot", "PassTokenEvent", "SnapshotEvent",
            "ClSnapError", "lib", "go_delay_schedule", "go_delay_schedule_device", "go_delay_schedule_jump",
            "DELAYGEN_MAX_DRAWS", "go_int63", "go_intn", "REFERENCE_SEED",
@@ -135,6 +136,16 @@ def lib():
         "cl_select_time": [vp, vp],
         "cl_select_stage_times": [vp, vp, vp],
         "cl_snapshot_ticks": [vp, i32, i64, i64, vp],
+        "cl_iset_from_clauses": [vp, i32, i64, i64, vp, i32, pp, vp],
+        "cl_iset_from_list": [vp, vp, i64, pp],
+        "cl_iset_combine": [vp, vp, vp, i32],
+        "cl_iset_count": [vp, i64, i64, vp],
+        "cl_iset_read": [vp, i64, i64, vp, i64, vp],
+        "cl_iset_destroy": [vp],
+        "cl_iset_time": [vp, vp],
+        "cl_snapshot_stats_in": [vp, i32, i64, i64, vp, vp, vp, i64],
+        "cl_snapshot_census_in": [vp, i32, i64, i64, vp, vp, vp, vp, vp],
+        "cl_select_instances_in": [vp, i32, i64, i64, vp, vp, i32, vp, vp, i64, vp],
         "cl_set_delay_go_seed_list": [vp, vp, i64],
         "cl_set_delay_generator": [vp, i32],
         "cl_delay_generator": [vp, vp],
@@ -563,6 +574,85 @@ class SnapshotSelection:
     __hash__ = None
 
 
+ISET_AND, ISET_OR, ISET_ANDNOT = range(3)   # include/clsnap.h CL_ISET_*
+
+
+class InstanceSet:
+    """A set of instances of one ``ChandyLamportSim``, kept on the GPU as a bitmap (cl_iset).
+
+    Made by ``sim.instance_set(snapshot_id, where)`` (the matches of select clauses; ``info`` is
+    then the (instances, ok, sample, n_match) of that selection) or ``sim.instance_set_from(insts)``
+    (``info`` is None).  ``a & b``, ``a | b`` and ``a - b`` give new sets; ``len(s)``, ``s.count(lo,
+    hi)`` and ``s.insts(lo, hi, max_out)`` read one.  A set is only a set of indices: it stays valid
+    across ``rerun()`` and engine switches, and a set made from one snapshot id may condition the
+    analysis of another (``sim.snapshot_stats_in``, ``snapshot_census_in``, ``select_instances_in``).
+    ``close()`` (or leaving a ``with`` block) frees the bitmap; the sim frees what is left."""
+
+    def __init__(self, sim, handle, info=None):
+        self._sim, self._h, self.info = sim, handle, info
+
+    def _handle(self):
+        if not self._h or not self._sim._h:
+            raise ValueError("InstanceSet: the set is closed")
+        return self._h
+
+    def close(self):
+        h, self._h = self._h, None
+        if h and self._sim._h:   # (a destroyed sim has freed its sets)
+            self._sim._L.cl_iset_destroy(h)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _combine(self, other, op):
+        if not isinstance(other, InstanceSet):
+            return NotImplemented
+        out = self._sim.instance_set_from(())
+        _check(self._sim._L.cl_iset_combine(out._handle(), self._handle(), other._handle(), op))
+        return out
+
+    def __and__(self, other):
+        return self._combine(other, ISET_AND)
+
+    def __or__(self, other):
+        return self._combine(other, ISET_OR)
+
+    def __sub__(self, other):
+        return self._combine(other, ISET_ANDNOT)
+
+    def combine_into(self, a, b, op):
+        """self = a op b in place (op one of ISET_AND, ISET_OR, ISET_ANDNOT); self may be a or b."""
+        _check(self._sim._L.cl_iset_combine(self._handle(), a._handle(), b._handle(), op))
+        self.info = None
+        return self
+
+    def count(self, lo=0, hi=None):
+        """Members in [lo, hi)."""
+        n = C.c_int64(0)
+        _check(self._sim._L.cl_iset_count(self._handle(), lo, self._sim.n_instances if hi is None else hi, C.byref(n)))
+        return n.value
+
+    def __len__(self):
+        return self.count()
+
+    def insts(self, lo=0, hi=None, max_out=None):
+        """The members in [lo, hi) as ascending int64 indices; at most max_out of them (the
+        smallest) when given."""
+        hi = self._sim.n_instances if hi is None else hi
+        cap = self.count(lo, hi) if max_out is None else max_out
+        out = np.zeros(max(cap, 0), dtype=np.int64)
+        n = C.c_int64(0)
+        _check(self._sim._L.cl_iset_read(self._handle(), lo, hi, _p(out) if cap > 0 else None, cap, C.byref(n)))
+        return out[:min(n.value, max(cap, 0))].copy()
+
+
 class ChandyLamportSim:
     """A batch of ``n_instances`` reference simulators (sim.go ChandyLamportSim).
 
@@ -727,12 +817,26 @@ class ChandyLamportSim:
         which it completed, reduced on the GPU (cl_snapshot_stats): a SnapshotStats with count,
         sum, sum of squares, min, max and histograms of the completion tick, each node's
         tokenMap entry, each channel's recorded messages and tokens, and the per-instance totals."""
+        return self._stats(None, snapshot_id, inst_lo, inst_hi, tick_lo, tick_bins, msg_bins)
+
+    def _stats(self, iset, snapshot_id, inst_lo, inst_hi, tick_lo, tick_bins, msg_bins):
         hi = self.n_instances if inst_hi is None else inst_hi
         layout = self.stats_layout(tick_lo, tick_bins, msg_bins)
         spec = np.array([tick_lo, tick_bins, msg_bins], dtype=np.int32)
         raw = np.zeros(layout["total_words"], dtype=np.int64)
-        _check(self._L.cl_snapshot_stats(self._h, snapshot_id, inst_lo, hi, _p(spec), _p(raw), raw.size))
+        if iset is None:
+            _check(self._L.cl_snapshot_stats(self._h, snapshot_id, inst_lo, hi, _p(spec), _p(raw), raw.size))
+        else:
+            _check(self._L.cl_snapshot_stats_in(self._h, snapshot_id, inst_lo, hi, iset._handle(), _p(spec), _p(raw),
+                                                raw.size))
         return SnapshotStats(layout, raw)
+
+    def snapshot_stats_in(self, snapshot_id, iset, inst_lo=0, inst_hi=None, tick_lo=0, tick_bins=256, msg_bins=16):
+        """snapshot_stats over the members of the InstanceSet `iset` (cl_snapshot_stats_in): the
+        sample is the members of [inst_lo, inst_hi) with status OK in which the snapshot completed;
+        `instances` and `ok` still count the whole range.  A SnapshotStats like any other: it merges
+        and reduces (dist.reduce_stats) unchanged."""
+        return self._stats(iset, snapshot_id, inst_lo, inst_hi, tick_lo, tick_bins, msg_bins)
 
     def stats_time(self):
         """Device ms of the latest snapshot_stats kernel(s)."""
@@ -746,16 +850,28 @@ class ChandyLamportSim:
         (cl_snapshot_census): a SnapshotCensus of at most `max_classes` classes, most frequent
         first.  class_of=True also returns each instance's class index.  lds_slots: 0 = the
         engine's workgroup table, -1 = none, else a power of two in [16, 4096] (results are the same)."""
+        return self._census(None, snapshot_id, inst_lo, inst_hi, max_classes, class_of, lds_slots)
+
+    def _census(self, iset, snapshot_id, inst_lo, inst_hi, max_classes, class_of, lds_slots):
         hi = self.n_instances if inst_hi is None else inst_hi
         spec = _CensusSpec(max_classes, lds_slots)
         classes = np.zeros(max(max_classes, 0), dtype=CENSUS_CLASS_DTYPE)
         cls = np.full(max(hi - inst_lo, 0), -1, dtype=np.int32) if class_of else None
         info = np.zeros(5, dtype=np.int64)
-        _check(self._L.cl_snapshot_census(self._h, snapshot_id, inst_lo, hi, C.byref(spec),
-                                          _p(classes) if max_classes > 0 else None,
-                                          _p(cls) if class_of else None, _p(info)))
+        tail = (C.byref(spec), _p(classes) if max_classes > 0 else None, _p(cls) if class_of else None, _p(info))
+        if iset is None:
+            _check(self._L.cl_snapshot_census(self._h, snapshot_id, inst_lo, hi, *tail))
+        else:
+            _check(self._L.cl_snapshot_census_in(self._h, snapshot_id, inst_lo, hi, iset._handle(), *tail))
         instances, ok, sample, n_classes, n_returned = info.tolist()
         return SnapshotCensus(snapshot_id, instances, ok, sample, n_classes, classes[:n_returned].copy(), cls)
+
+    def snapshot_census_in(self, snapshot_id, iset, inst_lo=0, inst_hi=None, max_classes=4096, class_of=False,
+                           lds_slots=0):
+        """snapshot_census over the members of the InstanceSet `iset` (cl_snapshot_census_in); class_of
+        is -1 for the instances of the range outside the conditional sample.  A SnapshotCensus like
+        any other (dist.gather_census takes it unchanged)."""
+        return self._census(iset, snapshot_id, inst_lo, inst_hi, max_classes, class_of, lds_slots)
 
     def census_time(self):
         """Device ms of the latest snapshot_census kernels."""
@@ -778,6 +894,9 @@ class ChandyLamportSim:
         hi inclusive, None for an open end.  max_out=None counts first and fetches every match;
         else at most max_out indices are returned (the smallest).  ticks=True also returns the
         completion ticks."""
+        return self._select(None, snapshot_id, where, inst_lo, inst_hi, max_out, ticks)
+
+    def _select(self, iset, snapshot_id, where, inst_lo, inst_hi, max_out, ticks):
         hi = self.n_instances if inst_hi is None else inst_hi
         clauses = self.select_clauses(where)
         info = np.zeros(5, dtype=np.int64)
@@ -785,9 +904,12 @@ class ChandyLamportSim:
         def call(cap):
             insts = np.zeros(max(cap, 0), dtype=np.int64)
             tk = np.zeros(max(cap, 0), dtype=np.int32) if ticks else None
-            _check(self._L.cl_select_instances(self._h, snapshot_id, inst_lo, hi, _p(clauses) if clauses.size else None,
-                                               clauses.size, _p(insts) if cap > 0 else None,
-                                               _p(tk) if ticks and cap > 0 else None, cap, _p(info)))
+            tail = (_p(clauses) if clauses.size else None, clauses.size, _p(insts) if cap > 0 else None,
+                    _p(tk) if ticks and cap > 0 else None, cap, _p(info))
+            if iset is None:
+                _check(self._L.cl_select_instances(self._h, snapshot_id, inst_lo, hi, *tail))
+            else:
+                _check(self._L.cl_select_instances_in(self._h, snapshot_id, inst_lo, hi, iset._handle(), *tail))
             k = int(info[4])
             return insts[:k].copy(), None if tk is None else tk[:k].copy()
 
@@ -798,6 +920,36 @@ class ChandyLamportSim:
             insts, tk = call(max_out)
         instances, ok, sample, n_match, _ = info.tolist()
         return SnapshotSelection(snapshot_id, instances, ok, sample, n_match, insts, tk)
+
+    def select_instances_in(self, snapshot_id, iset, where=(), inst_lo=0, inst_hi=None, max_out=None, ticks=False):
+        """select_instances over the members of the InstanceSet `iset` (cl_select_instances_in)."""
+        return self._select(iset, snapshot_id, where, inst_lo, inst_hi, max_out, ticks)
+
+    def instance_set(self, snapshot_id, where=(), inst_lo=0, inst_hi=None):
+        """The InstanceSet of the instances select_instances(snapshot_id, where, inst_lo, inst_hi)
+        would return, built and kept on the GPU (cl_iset_from_clauses); its ``info`` is
+        (instances, ok, sample, n_match) of that selection."""
+        hi = self.n_instances if inst_hi is None else inst_hi
+        clauses = self.select_clauses(where)
+        info = np.zeros(5, dtype=np.int64)
+        h = C.c_void_p()
+        _check(self._L.cl_iset_from_clauses(self._h, snapshot_id, inst_lo, hi, _p(clauses) if clauses.size else None,
+                                            clauses.size, C.byref(h), _p(info)))
+        return InstanceSet(self, h, tuple(info[:4].tolist()))
+
+    def instance_set_from(self, insts):
+        """The InstanceSet of the listed instances (cl_iset_from_list): any order, duplicates allowed."""
+        insts = np.ascontiguousarray(insts, dtype=np.int64).ravel()
+        h = C.c_void_p()
+        _check(self._L.cl_iset_from_list(self._h, _p(insts) if insts.size else None, insts.size, C.byref(h)))
+        return InstanceSet(self, h)
+
+    def iset_time(self):
+        """Device ms of the latest InstanceSet kernels (list scatter, combine, count, listing);
+        instance_set() is timed by select_time()."""
+        ms = C.c_double(0)
+        _check(self._L.cl_iset_time(self._h, C.byref(ms)))
+        return ms.value
 
     def select_time(self, stages=False):
         """Device ms of the latest select_instances kernels, both stages; stages=True: the pair

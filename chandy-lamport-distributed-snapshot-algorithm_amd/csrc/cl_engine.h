@@ -492,9 +492,10 @@ inline int32_t stats_blocks_per_cu(int32_t lds_bytes) {
 }
 
 // The sample of the analytics calls (statistics, census, select) and the planes their kernels walk
-// for it: the instances of [lo, hi) with status OK in which snapshot `sid` completed.  The walk
-// itself is cl_sample.h's (device code; this header is also compiled into the run-time lanes kernel
-// and holds declarations only).
+// for it: the instances of [lo, hi) with status OK in which snapshot `sid` completed -- and, for the
+// conditional calls (cl_*_in), that are members of the instance set `where`.  The walk itself is
+// cl_sample.h's (device code; this header is also compiled into the run-time lanes kernel and
+// holds declarations only).
 struct SampleParams {
   int32_t n_nodes, n_ch, s_cap, rw, sid;
   int64_t n_inst, stride;
@@ -505,6 +506,9 @@ struct SampleParams {
   const uint32_t* snap_nod;
   int32_t blocked;           // records block-major by slot (rec_word)
   const int32_t* inst_map;   // slot -> instance of a block-major replay (nullptr: identity)
+  // An instance set's bitmap (cl_iset: bit inst & 63 of word inst >> 6, stride / 64 words): only its
+  // members are in the sample; the instances / OK counters still count the range.  nullptr: no filter.
+  const unsigned long long* where;
 };
 
 struct StatsParams {
@@ -643,5 +647,23 @@ inline int32_t select_lds_bytes(bool staged) {
 int launch_select_eval(const SelectParams& p, int32_t blocks, void* stream);
 // count + scan (n_match left in p.info[3]), then the fill of the first p.cap matches
 int launch_select_compact(const SelectParams& p, void* stream);
+
+// ---- device-resident instance sets (cl_iset.hip; include/clsnap.h cl_iset) ----------------------
+// A subset of [0, n_instances) as a bitmap: bit inst & 63 of word inst >> 6, stride / 64 words, the
+// bits at and above n_instances 0.  The analytics kernels filter on it (SampleParams::where).
+enum : int32_t { ISET_AND = 0, ISET_OR = 1, ISET_ANDNOT = 2, ISET_NUM_OPS = 3 };
+constexpr int32_t kIsetThreads = 256;
+// bits[list[r] >> 6] |= 1 << (list[r] & 63), r < n, into a zeroed bitmap (entries outside
+// [0, n_inst) are skipped: the host has refused them before)
+int launch_iset_scatter(const long long* list, int64_t n, int64_t n_inst, unsigned long long* bits, void* stream);
+// dst[w] = a[w] op b[w], w < words (dst may be a or b)
+int launch_iset_combine(unsigned long long* dst, const unsigned long long* a, const unsigned long long* b,
+                        int32_t op, int64_t words, void* stream);
+// The words that overlap [lo, hi), lo < hi, the first and the last masked to the range:
+// dst[j] = src[lo / 64 + j] & mask, j < ceil(hi / 64) - lo / 64 -- what the selection's compaction
+// (launch_select_compact, base = lo rounded down to 64) reads; the count adds their set bits to
+// *count (zeroed by the host), one atomic per workgroup.
+int launch_iset_clip(unsigned long long* dst, const unsigned long long* src, int64_t lo, int64_t hi, void* stream);
+int launch_iset_count(const unsigned long long* src, int64_t lo, int64_t hi, unsigned long long* count, void* stream);
 
 }  // namespace clsnap

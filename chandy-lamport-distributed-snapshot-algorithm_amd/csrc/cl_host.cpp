@@ -279,6 +279,19 @@ int device_generate(int device, hipStream_t stream, int32_t n_cus, int64_t seed_
 }  // namespace
 
 // ---------------------------------------------------------------------------
+// cl_iset: a device-resident set of instances of one sim (cl_iset.hip)
+// ---------------------------------------------------------------------------
+// Only a set of indices: nothing in it refers to a run, an engine or a record layout.  The bitmap
+// (stride / 64 words, the bits from n_instances on 0) is allocated on the first call that needs it
+// on the device; until then a set made from a list keeps the list (`pending`; empty: the empty set).
+struct cl_iset {
+  cl_sim* sim = nullptr;
+  DevBuf<unsigned long long> bits;
+  bool resident = false;          // bits holds the set
+  std::vector<int64_t> pending;   // the list to scatter when the bitmap is made
+};
+
+// ---------------------------------------------------------------------------
 // cl_sim
 // ---------------------------------------------------------------------------
 struct cl_sim {
@@ -515,6 +528,13 @@ struct cl_sim {
   DevBuf<int32_t> d_sel_ticks;
   hipEvent_t sel_ev[3] = {nullptr, nullptr, nullptr};  // start, evaluated, compacted
   bool sel_timed = false;
+  // instance sets (cl_iset, cl_iset.hip): the sets alive (freed with the sim), the list upload and
+  // the count's scalar; the listing borrows the selection's compaction scratch
+  std::vector<cl_iset*> isets;
+  DevBuf<long long> d_is_list;
+  DevBuf<unsigned long long> d_is_count;
+  hipEvent_t is_ev[2] = {nullptr, nullptr};
+  bool is_timed = false;
   size_t hist_uploaded = (size_t)-1;  // history entries on the device
 
   ~cl_sim() {
@@ -534,6 +554,10 @@ struct cl_sim {
       d_cs_class.release(); d_cs_rank.release(); d_pk_list.release();
       d_sel_bits.release(); d_sel_info.release(); d_sel_bsum.release(); d_sel_out.release(); d_sel_ticks.release();
       d_seeds.release(); d_dg_flag.release();
+      d_is_list.release(); d_is_count.release();
+      for (cl_iset* s : isets) s->bits.release();
+      for (auto& e : is_ev)
+        if (e) (void)hipEventDestroy(e);
       for (auto& e : dg_ev)
         if (e) (void)hipEventDestroy(e);
       for (auto& e : sel_ev)
@@ -555,6 +579,7 @@ struct cl_sim {
       if (ev_join) (void)hipEventDestroy(ev_join);
       (void)hipStreamDestroy(stream);
     }
+    for (cl_iset* s : isets) delete s;  // (the sets still alive go with their sim)
   }
 
   int node_of(const char* id) const {
@@ -1370,13 +1395,15 @@ struct cl_sim {
 
   // The opening of the analytics calls (stats, census, select): executes what is pending, makes the
   // token histories resident, and describes the sample of snapshot sid over [lo, hi) and the planes
-  // its kernels walk (cl_sample.h).
-  int sample_begin(int32_t sid, int64_t lo, int64_t hi, SampleParams* s) {
+  // its kernels walk (cl_sample.h).  `in` (the conditional calls): the instance set whose members
+  // the sample is taken from, made resident here.
+  int sample_begin(int32_t sid, int64_t lo, int64_t hi, SampleParams* s, cl_iset* in = nullptr) {
     int rc = flush();
     if (rc) return rc;
     if (!dev_ready) return set_err(CL_E_STATE, "nothing has run on the device yet");
     HIP_TRY(hipSetDevice(device));
     if ((rc = upload_hist())) return rc;
+    if (in && (rc = iset_resident(in))) return rc;
     if (!n_cus) HIP_TRY(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device));
     *s = SampleParams{};
     s->n_nodes = (int32_t)ids.size();
@@ -1397,6 +1424,7 @@ struct cl_sim {
     // block-major records are in slot order: a sub-range's instances may sit in any tile
     s->tile_lo = rec_blocked ? 0 : lo / kWave;
     s->tile_hi = hi <= lo ? s->tile_lo : rec_blocked ? stride / kWave : (hi + kWave - 1) / kWave;
+    s->where = in ? in->bits.p : nullptr;  // (the conditional calls: only the set's members)
     return CL_OK;
   }
 
@@ -1413,9 +1441,9 @@ struct cl_sim {
   // (arguments checked by the caller).  One kernel pass when the topology's N * rw record
   // words fit the LDS accumulator budget (stats_pass_words), else one pass per range of chunks;
   // the first pass also takes the per-instance totals.
-  int stats(int32_t sid, int64_t lo, int64_t hi, const StatsLayout& L, int64_t* out) {
+  int stats(int32_t sid, int64_t lo, int64_t hi, const StatsLayout& L, int64_t* out, cl_iset* in = nullptr) {
     StatsParams p{};
-    int rc = sample_begin(sid, lo, hi, &p.s);
+    int rc = sample_begin(sid, lo, hi, &p.s, in);
     if (rc) return rc;
     for (auto& e : st_ev)
       if (!e) HIP_TRY(hipEventCreate(&e));
@@ -1465,9 +1493,9 @@ struct cl_sim {
   // [lo, hi), sorted, into *out; class_of[hi - lo] when asked for.  lds_slots: the workgroup
   // table's entries, 0 for none.
   int census(int32_t sid, int64_t lo, int64_t hi, int32_t lds_slots, std::vector<CensusEntry>* out,
-             int32_t* class_of, cl_census_info* info) {
+             int32_t* class_of, cl_census_info* info, cl_iset* in = nullptr) {
     CensusParams p{};
-    int rc = sample_begin(sid, lo, hi, &p.s);
+    int rc = sample_begin(sid, lo, hi, &p.s, in);
     if (rc) return rc;
     for (auto& e : cs_ev)
       if (!e) HIP_TRY(hipEventCreate(&e));
@@ -1548,19 +1576,39 @@ struct cl_sim {
     return CL_OK;
   }
 
+  // The scratch of the bitmap compaction (launch_select_compact) for p.words words and p.cap
+  // entries, shared by the selection and the listing of an instance set.
+  int compact_scratch(SelectParams* p, bool want_ticks) {
+    const int64_t n_blocks = (p->words + kSelBlockWords - 1) / kSelBlockWords;
+    int rc;
+    if ((rc = d_sel_bsum.ensure((size_t)n_blocks)) || (rc = d_sel_info.ensure(4)) ||
+        (rc = d_sel_out.ensure((size_t)std::max<int64_t>(p->cap, 1))))
+      return rc;
+    if (want_ticks && (rc = d_sel_ticks.ensure((size_t)std::max<int64_t>(p->cap, 1)))) return rc;
+    p->info = d_sel_info.p;
+    p->bsum = d_sel_bsum.p;
+    p->out = d_sel_out.p;
+    p->ticks = want_ticks ? d_sel_ticks.p : nullptr;
+    return CL_OK;
+  }
+
   // cl_select_instances (arguments checked by the caller): the instances of the sample of
   // snapshot sid over [lo, hi) that satisfy every clause, ascending, the first `cap` of them into
   // insts (and their completion ticks into ticks).  Both stages are enqueued back to back; the
   // host waits once, for the info, then copies the n_returned entries.
+  // `in` (cl_select_instances_in): the sample is that of the set's members.  `into`
+  // (cl_iset_from_clauses): the verdicts are written into that set's bitmap and stay there; nothing
+  // is listed (cap 0), the compaction only counts.  The verdict bitmap is never the one filtered on.
   int select(int32_t sid, int64_t lo, int64_t hi, const cl_select_clause* clauses, int32_t n_clauses, int64_t* insts,
-             int32_t* ticks, int64_t cap, cl_select_info* info) {
+             int32_t* ticks, int64_t cap, cl_select_info* info, cl_iset* in = nullptr, cl_iset* into = nullptr) {
     SelectParams p{};
-    int rc = sample_begin(sid, lo, hi, &p.s);
+    int rc = sample_begin(sid, lo, hi, &p.s, in);
     if (rc) return rc;
     for (auto& e : sel_ev)
       if (!e) HIP_TRY(hipEventCreate(&e));
     *info = cl_select_info{};
     const int64_t n = hi - lo;
+    if (into && n == 0) return iset_clear(into);
     if (n == 0) return CL_OK;
     p.ch_slot = d_ch_slot.p;
     p.hist_off = d_hist.p;
@@ -1578,21 +1626,20 @@ struct cl_sim {
     p.base = lo / kWave * kWave;
     p.words = (hi - p.base + kWave - 1) / kWave;
     p.cap = std::min(cap, n);
-    const int64_t n_blocks = (p.words + kSelBlockWords - 1) / kSelBlockWords;
-    if ((rc = d_sel_bits.ensure((size_t)p.words)) || (rc = d_sel_bsum.ensure((size_t)n_blocks)) ||
-        (rc = d_sel_info.ensure(4)) || (rc = d_sel_out.ensure((size_t)std::max<int64_t>(p.cap, 1))))
-      return rc;
-    if (ticks && (rc = d_sel_ticks.ensure((size_t)std::max<int64_t>(p.cap, 1)))) return rc;
-    p.bitmap = d_sel_bits.p;
-    p.info = d_sel_info.p;
-    p.bsum = d_sel_bsum.p;
-    p.out = d_sel_out.p;
-    p.ticks = ticks ? d_sel_ticks.p : nullptr;
+    if (!into && (rc = d_sel_bits.ensure((size_t)p.words))) return rc;
+    if ((rc = compact_scratch(&p, ticks != nullptr))) return rc;
     const int32_t blocks = sample_grid(p.s.tile_hi - p.s.tile_lo, select_lds_bytes(p.staged && p.need_records));
     HIP_TRY(hipEventRecord(sel_ev[0], stream));
     HIP_TRY(hipMemsetAsync(d_sel_info.p, 0, 4 * sizeof(unsigned long long), stream));
-    // block-major: the lanes OR their bits in; instance-major: every word is stored
-    if (rec_blocked) HIP_TRY(hipMemsetAsync(d_sel_bits.p, 0, (size_t)p.words * sizeof(unsigned long long), stream));
+    if (into) {
+      // the whole set is cleared: the words of [lo, hi) are a part of it
+      if ((rc = iset_clear(into))) return rc;
+      p.bitmap = into->bits.p + p.base / kWave;
+    } else {
+      p.bitmap = d_sel_bits.p;
+      // block-major: the lanes OR their bits in; instance-major: every word is stored
+      if (rec_blocked) HIP_TRY(hipMemsetAsync(d_sel_bits.p, 0, (size_t)p.words * sizeof(unsigned long long), stream));
+    }
     int e = launch_select_eval(p, blocks, stream);
     if (e) return set_err(CL_E_DEVICE, "select kernels: %s", hipGetErrorString((hipError_t)e));
     HIP_TRY(hipEventRecord(sel_ev[1], stream));
@@ -1614,6 +1661,121 @@ struct cl_sim {
       if (ticks) HIP_TRY(hipMemcpyAsync(ticks, d_sel_ticks.p, k * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
       HIP_TRY(hipStreamSynchronize(stream));
     }
+    return CL_OK;
+  }
+
+  // ---- instance sets (cl_iset) -------------------------------------------------------------------
+  int64_t iset_words() const { return stride / kWave; }
+
+  // The set as an all-zero bitmap on the device (allocated now if it never was).
+  int iset_clear(cl_iset* s) {
+    int rc = ensure_device();
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if ((rc = s->bits.ensure((size_t)iset_words()))) return rc;
+    HIP_TRY(hipMemsetAsync(s->bits.p, 0, (size_t)iset_words() * sizeof(unsigned long long), stream));
+    s->pending.clear();
+    s->resident = true;
+    return CL_OK;
+  }
+
+  int iset_time_begin() {
+    for (auto& e : is_ev)
+      if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(is_ev[0], stream));
+    return CL_OK;
+  }
+  int iset_time_end() {
+    HIP_TRY(hipEventRecord(is_ev[1], stream));
+    is_timed = true;
+    return CL_OK;
+  }
+
+  // The first device use of a set: its bitmap is made, the list it was built from scattered into
+  // it (`timed`: as the kernels of cl_iset_time).
+  int iset_resident(cl_iset* s, bool timed = false) {
+    if (s->resident) return CL_OK;
+    std::vector<int64_t> list = std::move(s->pending);
+    const int rc = iset_scatter(s, list, timed);
+    if (rc) {  // (still the list it was: the next use tries again)
+      s->resident = false;
+      s->pending = std::move(list);
+    }
+    return rc;
+  }
+  int iset_scatter(cl_iset* s, const std::vector<int64_t>& list, bool timed) {
+    int rc = iset_clear(s);
+    if (rc || list.empty()) return rc;
+    if ((rc = d_is_list.ensure(list.size()))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_is_list.p, list.data(), list.size() * sizeof(long long), hipMemcpyHostToDevice, stream));
+    if (timed && (rc = iset_time_begin())) return rc;
+    const int e = launch_iset_scatter(d_is_list.p, (int64_t)list.size(), n_inst, s->bits.p, stream);
+    if (e) return set_err(CL_E_DEVICE, "instance set kernels: %s", hipGetErrorString((hipError_t)e));
+    if (timed && (rc = iset_time_end())) return rc;
+    HIP_TRY(hipStreamSynchronize(stream));  // (the list is the host's until the copy is done)
+    return CL_OK;
+  }
+
+  int iset_combine(cl_iset* dst, cl_iset* a, cl_iset* b, int32_t op) {
+    int rc;
+    if ((rc = iset_resident(a)) || (rc = iset_resident(b))) return rc;
+    // (dst is overwritten: only its bitmap is needed, unless it is an operand)
+    if (dst != a && dst != b && (rc = iset_clear(dst))) return rc;
+    if ((rc = iset_time_begin())) return rc;
+    const int e = launch_iset_combine(dst->bits.p, a->bits.p, b->bits.p, op, iset_words(), stream);
+    if (e) return set_err(CL_E_DEVICE, "instance set kernels: %s", hipGetErrorString((hipError_t)e));
+    if ((rc = iset_time_end())) return rc;
+    HIP_TRY(hipStreamSynchronize(stream));
+    return CL_OK;
+  }
+
+  int iset_count(cl_iset* s, int64_t lo, int64_t hi, int64_t* n) {
+    int rc = iset_resident(s);
+    if (rc) return rc;
+    *n = 0;
+    if (hi == lo) return CL_OK;
+    if ((rc = d_is_count.ensure(1))) return rc;
+    HIP_TRY(hipMemsetAsync(d_is_count.p, 0, sizeof(unsigned long long), stream));
+    if ((rc = iset_time_begin())) return rc;
+    const int e = launch_iset_count(s->bits.p, lo, hi, d_is_count.p, stream);
+    if (e) return set_err(CL_E_DEVICE, "instance set kernels: %s", hipGetErrorString((hipError_t)e));
+    if ((rc = iset_time_end())) return rc;
+    unsigned long long h = 0;
+    HIP_TRY(hipMemcpyAsync(&h, d_is_count.p, sizeof h, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if ((int64_t)h > hi - lo)
+      return set_err(CL_E_DEVICE, "instance set: %lld members of %lld instances", (long long)h, (long long)(hi - lo));
+    *n = (int64_t)h;
+    return CL_OK;
+  }
+
+  // The members in [lo, hi), ascending, the first `cap` of them: the words of the range, clipped
+  // to it, through the selection's compaction.
+  int iset_read(cl_iset* s, int64_t lo, int64_t hi, int64_t* insts, int64_t cap, int64_t* n_match) {
+    int rc = iset_resident(s);
+    if (rc) return rc;
+    *n_match = 0;
+    if (hi == lo) return CL_OK;
+    SelectParams p{};
+    p.base = lo / kWave * kWave;
+    p.words = (hi - p.base + kWave - 1) / kWave;
+    p.cap = std::min(cap, hi - lo);
+    if ((rc = d_sel_bits.ensure((size_t)p.words)) || (rc = compact_scratch(&p, false))) return rc;
+    p.bitmap = d_sel_bits.p;
+    HIP_TRY(hipMemsetAsync(d_sel_info.p, 0, 4 * sizeof(unsigned long long), stream));
+    if ((rc = iset_time_begin())) return rc;
+    int e = launch_iset_clip(d_sel_bits.p, s->bits.p, lo, hi, stream);
+    if (!e) e = launch_select_compact(p, stream);
+    if (e) return set_err(CL_E_DEVICE, "instance set kernels: %s", hipGetErrorString((hipError_t)e));
+    if ((rc = iset_time_end())) return rc;
+    unsigned long long h[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, d_sel_info.p, sizeof h, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if ((int64_t)h[3] > hi - lo)
+      return set_err(CL_E_DEVICE, "instance set: %lld members of %lld instances", (long long)h[3], (long long)(hi - lo));
+    *n_match = (int64_t)h[3];
+    const int64_t k = std::min<int64_t>(*n_match, cap);
+    if (k > 0) HIP_TRY(hipMemcpy(insts, d_sel_out.p, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost));
     return CL_OK;
   }
 
@@ -2152,6 +2314,8 @@ int cl_device_bytes(const cl_sim* sim, int64_t* bytes) {
   b += sim->d_sel_bits.n * 8 + sim->d_sel_info.n * 8 + sim->d_sel_bsum.n * 8 + sim->d_sel_out.n * 8 +
        sim->d_sel_ticks.n * 4;  // (the selection's scratch, once a selection has run)
   b += sim->d_seeds.n * 8 + sim->d_dg_flag.n * 8;  // (the seed list and the device generator's flagged rows)
+  for (const cl_iset* s : sim->isets) b += s->bits.n * 8;  // (the instance sets alive, and their list upload)
+  b += sim->d_is_list.n * 8 + sim->d_is_count.n * 8;
   *bytes = b;
   return CL_OK;
 }
@@ -2364,6 +2528,13 @@ static int sample_args_ok(const cl_sim* sim, int32_t sid, int64_t inst_lo, int64
   return CL_OK;
 }
 
+// The set of a conditional call (cl_*_in): given, and this sim's.
+static int iset_arg_ok(const cl_sim* sim, const cl_iset* in) {
+  if (!in) return set_err(CL_E_INVALID, "null instance set");
+  if (in->sim != sim) return set_err(CL_E_INVALID, "the instance set belongs to another sim");
+  return CL_OK;
+}
+
 static_assert(sizeof(cl_stats_layout) == sizeof(StatsLayout), "cl_stats_layout mirrors StatsLayout");
 
 static int stats_spec_ok(const cl_stats_spec* spec) {
@@ -2386,12 +2557,14 @@ int cl_stats_layout_of(const cl_sim* sim, const cl_stats_spec* spec, cl_stats_la
   return CL_OK;
 }
 
-int cl_snapshot_stats(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_stats_spec* spec,
-                      int64_t* out, int64_t out_words) {
+// cl_snapshot_stats, and cl_snapshot_stats_in with its set (`conditional`).
+static int stats_call(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, bool conditional, const cl_iset* in,
+                      const cl_stats_spec* spec, int64_t* out, int64_t out_words) {
   SIM_CHECK(sim);
   // every argument is checked before any device work
-  int rc = stats_spec_ok(spec);
+  int rc = conditional ? iset_arg_ok(sim, in) : CL_OK;
   if (rc) return rc;
+  if ((rc = stats_spec_ok(spec))) return rc;
   if (!out) return set_err(CL_E_INVALID, "null output");
   if ((rc = sample_args_ok(sim, sid, inst_lo, inst_hi))) return rc;
   const StatsLayout L = stats_layout((int64_t)sim->ids.size(), (int64_t)sim->links.size(), spec->tick_lo,
@@ -2399,7 +2572,17 @@ int cl_snapshot_stats(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi
   if (out_words < L.total_words)
     return set_err(CL_E_LIMIT, "out_words %lld < %lld words of the statistics layout", (long long)out_words,
                    (long long)L.total_words);
-  return sim->stats(sid, inst_lo, inst_hi, L, out);
+  return sim->stats(sid, inst_lo, inst_hi, L, out, const_cast<cl_iset*>(in));
+}
+
+int cl_snapshot_stats(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_stats_spec* spec,
+                      int64_t* out, int64_t out_words) {
+  return stats_call(sim, sid, inst_lo, inst_hi, false, nullptr, spec, out, out_words);
+}
+
+int cl_snapshot_stats_in(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_iset* in,
+                         const cl_stats_spec* spec, int64_t* out, int64_t out_words) {
+  return stats_call(sim, sid, inst_lo, inst_hi, true, in, spec, out, out_words);
 }
 
 int cl_stats_time(cl_sim* sim, double* device_ms) {
@@ -2416,10 +2599,14 @@ int cl_stats_time(cl_sim* sim, double* device_ms) {
 static_assert(sizeof(cl_census_class) == sizeof(CensusEntry) && sizeof(CensusEntry) == 32,
               "cl_census_class mirrors CensusEntry");
 
-int cl_snapshot_census(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_census_spec* spec,
-                       cl_census_class* classes, int32_t* class_of, cl_census_info* info) {
+// cl_snapshot_census, and cl_snapshot_census_in with its set (`conditional`).
+static int census_call(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, bool conditional,
+                       const cl_iset* in, const cl_census_spec* spec, cl_census_class* classes, int32_t* class_of,
+                       cl_census_info* info) {
   SIM_CHECK(sim);
   // every argument is checked before any device work
+  if (conditional)
+    if (const int rc = iset_arg_ok(sim, in)) return rc;
   if (!spec || !info) return set_err(CL_E_INVALID, "null census spec or info");
   const int32_t ls = spec->lds_slots;
   if (spec->max_classes < 0 ||
@@ -2430,11 +2617,22 @@ int cl_snapshot_census(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_h
   if (const int rc = sample_args_ok(sim, sid, inst_lo, inst_hi)) return rc;
   std::vector<CensusEntry> got;
   const int32_t lds_slots = ls == 0 ? kCensusAutoLdsSlots : ls < 0 ? 0 : ls;
-  const int rc = sim->census(sid, inst_lo, inst_hi, lds_slots, &got, class_of, info);
+  const int rc = sim->census(sid, inst_lo, inst_hi, lds_slots, &got, class_of, info, const_cast<cl_iset*>(in));
   if (rc) return rc;
   info->n_returned = std::min<int64_t>(info->n_classes, spec->max_classes);
   if (info->n_returned > 0) std::memcpy(classes, got.data(), (size_t)info->n_returned * sizeof(cl_census_class));
   return CL_OK;
+}
+
+int cl_snapshot_census(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_census_spec* spec,
+                       cl_census_class* classes, int32_t* class_of, cl_census_info* info) {
+  return census_call(sim, sid, inst_lo, inst_hi, false, nullptr, spec, classes, class_of, info);
+}
+
+int cl_snapshot_census_in(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_iset* in,
+                          const cl_census_spec* spec, cl_census_class* classes, int32_t* class_of,
+                          cl_census_info* info) {
+  return census_call(sim, sid, inst_lo, inst_hi, true, in, spec, classes, class_of, info);
 }
 
 int cl_census_time(cl_sim* sim, double* device_ms) {
@@ -2457,10 +2655,14 @@ static_assert(sizeof(cl_select_clause) == sizeof(SelectClause) && sizeof(SelectC
 static_assert(CL_SELECT_MAX_CLAUSES == kSelMaxClauses && CL_SEL_KEY == SEL_KEY && CL_SEL_NOT == kSelNot,
               "CL_SEL_* mirror cl_engine.h");
 
-int cl_select_instances(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_select_clause* clauses,
-                        int32_t n_clauses, int64_t* insts, int32_t* ticks, int64_t cap, cl_select_info* info) {
-  SIM_CHECK(sim);
+// cl_select_instances; cl_select_instances_in with its set (`conditional`); cl_iset_from_clauses
+// with the set that takes the matches (`into`: no list, cap 0).
+static int select_call(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, bool conditional, const cl_iset* in,
+                       const cl_select_clause* clauses, int32_t n_clauses, int64_t* insts, int32_t* ticks,
+                       int64_t cap, cl_select_info* info, cl_iset* into) {
   // every argument is checked before any device work
+  if (conditional)
+    if (const int rc = iset_arg_ok(sim, in)) return rc;
   if (!info) return set_err(CL_E_INVALID, "null select info");
   if (n_clauses < 0 || n_clauses > CL_SELECT_MAX_CLAUSES || (n_clauses > 0 && !clauses))
     return set_err(CL_E_INVALID, "select: 0 <= n_clauses <= %d, with a clause array", CL_SELECT_MAX_CLAUSES);
@@ -2474,7 +2676,129 @@ int cl_select_instances(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_
   }
   if (cap < 0 || (cap > 0 && !insts)) return set_err(CL_E_INVALID, "select: cap >= 0, with an index array when cap > 0");
   if (const int rc = sample_args_ok(sim, sid, inst_lo, inst_hi)) return rc;
-  return sim->select(sid, inst_lo, inst_hi, clauses, n_clauses, insts, ticks, cap, info);
+  return sim->select(sid, inst_lo, inst_hi, clauses, n_clauses, insts, ticks, cap, info, const_cast<cl_iset*>(in), into);
+}
+
+int cl_select_instances(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_select_clause* clauses,
+                        int32_t n_clauses, int64_t* insts, int32_t* ticks, int64_t cap, cl_select_info* info) {
+  SIM_CHECK(sim);
+  return select_call(sim, sid, inst_lo, inst_hi, false, nullptr, clauses, n_clauses, insts, ticks, cap, info, nullptr);
+}
+
+int cl_select_instances_in(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_iset* in,
+                           const cl_select_clause* clauses, int32_t n_clauses, int64_t* insts, int32_t* ticks,
+                           int64_t cap, cl_select_info* info) {
+  SIM_CHECK(sim);
+  return select_call(sim, sid, inst_lo, inst_hi, true, in, clauses, n_clauses, insts, ticks, cap, info, nullptr);
+}
+
+// ---- instance sets ------------------------------------------------------------------------------
+static_assert(CL_ISET_AND == ISET_AND && CL_ISET_OR == ISET_OR && CL_ISET_ANDNOT == ISET_ANDNOT,
+              "CL_ISET_* mirror cl_engine.h");
+
+static cl_iset* iset_new(cl_sim* sim) {
+  cl_iset* s = new cl_iset();
+  s->sim = sim;
+  sim->isets.push_back(s);
+  return s;
+}
+
+static void iset_delete(cl_iset* s) {
+  cl_sim* sim = s->sim;
+  sim->isets.erase(std::remove(sim->isets.begin(), sim->isets.end(), s), sim->isets.end());
+  if (s->bits.p) {
+    (void)hipSetDevice(sim->device);
+    (void)hipStreamSynchronize(sim->stream);  // (a kernel may still read the bitmap)
+    s->bits.release();
+  }
+  delete s;
+}
+
+int cl_iset_from_clauses(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_select_clause* clauses,
+                         int32_t n_clauses, cl_iset** out, cl_select_info* info) {
+  SIM_CHECK(sim);
+  if (!out) return set_err(CL_E_INVALID, "null instance set output");
+  cl_iset* s = iset_new(sim);
+  const int rc = select_call(sim, sid, inst_lo, inst_hi, false, nullptr, clauses, n_clauses, nullptr, nullptr, 0, info, s);
+  if (rc) {
+    iset_delete(s);
+    return rc;
+  }
+  *out = s;
+  return CL_OK;
+}
+
+int cl_iset_from_list(cl_sim* sim, const int64_t* insts, int64_t n, cl_iset** out) {
+  SIM_CHECK(sim);
+  if (!out || n < 0 || (n > 0 && !insts)) return set_err(CL_E_INVALID, "instance list or set output out of range");
+  for (int64_t r = 0; r < n; ++r)
+    if (insts[r] < 0 || insts[r] >= sim->n_inst)
+      return set_err(CL_E_INVALID, "instance list entry %lld: instance %lld out of range", (long long)r,
+                     (long long)insts[r]);
+  cl_iset* s = iset_new(sim);
+  s->pending.assign(insts, insts + n);
+  // the scatter runs now when the sim already has its device, else with the set's first device use
+  if (sim->dev_ready) {
+    const int rc = sim->iset_resident(s, true);
+    if (rc) {
+      iset_delete(s);
+      return rc;
+    }
+  }
+  *out = s;
+  return CL_OK;
+}
+
+int cl_iset_combine(cl_iset* dst, const cl_iset* a, const cl_iset* b, int32_t op) {
+  if (!dst || !a || !b) return set_err(CL_E_INVALID, "null instance set");
+  cl_sim* sim = dst->sim;
+  SIM_CHECK(sim);
+  if (a->sim != sim || b->sim != sim) return set_err(CL_E_INVALID, "the instance sets belong to different sims");
+  if (op < 0 || op >= ISET_NUM_OPS) return set_err(CL_E_INVALID, "unknown instance set operation %d", op);
+  return sim->iset_combine(dst, const_cast<cl_iset*>(a), const_cast<cl_iset*>(b), op);
+}
+
+static int iset_range_ok(const cl_iset* s, int64_t lo, int64_t hi) {
+  if (lo < 0 || hi > s->sim->n_inst || lo > hi) return set_err(CL_E_INVALID, "instance range out of range");
+  return CL_OK;
+}
+
+int cl_iset_count(cl_iset* set, int64_t inst_lo, int64_t inst_hi, int64_t* n) {
+  if (!set) return set_err(CL_E_INVALID, "null instance set");
+  cl_sim* sim = set->sim;
+  SIM_CHECK(sim);
+  if (!n) return set_err(CL_E_INVALID, "null output");
+  if (const int rc = iset_range_ok(set, inst_lo, inst_hi)) return rc;
+  return sim->iset_count(set, inst_lo, inst_hi, n);
+}
+
+int cl_iset_read(cl_iset* set, int64_t inst_lo, int64_t inst_hi, int64_t* insts, int64_t cap, int64_t* n_match) {
+  if (!set) return set_err(CL_E_INVALID, "null instance set");
+  cl_sim* sim = set->sim;
+  SIM_CHECK(sim);
+  if (!n_match) return set_err(CL_E_INVALID, "null output");
+  if (cap < 0 || (cap > 0 && !insts)) return set_err(CL_E_INVALID, "iset read: cap >= 0, with an index array when cap > 0");
+  if (const int rc = iset_range_ok(set, inst_lo, inst_hi)) return rc;
+  return sim->iset_read(set, inst_lo, inst_hi, insts, cap, n_match);
+}
+
+int cl_iset_destroy(cl_iset* set) {
+  if (!set) return CL_OK;
+  cl_sim* sim = set->sim;
+  SIM_CHECK(sim);
+  iset_delete(set);
+  return CL_OK;
+}
+
+int cl_iset_time(cl_sim* sim, double* device_ms) {
+  SIM_CHECK(sim);
+  if (!device_ms) return set_err(CL_E_INVALID, "null output");
+  if (!sim->is_timed) return set_err(CL_E_STATE, "no instance set kernel has run");
+  HIP_TRY(hipStreamSynchronize(sim->stream));
+  float f = 0.f;
+  HIP_TRY(hipEventElapsedTime(&f, sim->is_ev[0], sim->is_ev[1]));
+  *device_ms = f;
+  return CL_OK;
 }
 
 int cl_select_stage_times(cl_sim* sim, double* evaluate_ms, double* compact_ms) {

@@ -3,7 +3,8 @@
 // also compiled into the run-time lanes kernel.
 //
 // The sample (SampleParams).  Every instance of [lo, hi) with status OK in which snapshot `sid`
-// completed (completion tick >= 0).
+// completed (completion tick >= 0) -- of the members of an instance set when one is given
+// (SampleParams::where, the cl_*_in calls).
 //
 // The walk.  A wave walks tiles of 64 record slots, grid-stride (sample_first_tile,
 // sample_tile_stride), the grid sized to the chip; lane = slot.  sample_lane() classifies the
@@ -52,15 +53,35 @@ struct SampleLane {
   bool in, ok, sample;
   int32_t tick;
 };
+//
+// With an instance set (s.where) only its members are in the sample; `in` and `ok` still describe
+// the range.  Where slot = instance the tile's 64 instances are bitmap word t: one wave-uniform
+// load per tile, each lane tests its own bit, and a tile whose word is 0 reads the status words
+// only.  Through a slot -> instance map every lane gathers the word of its instance.  A lane that is
+// no member does not read its tick (it stays -1).
 __device__ __forceinline__ SampleLane sample_lane(const SampleParams& s, int64_t t, int32_t lane) {
   const int64_t slot = t * 64 + lane;
   SampleLane l{-1, false, false, false, -1};
-  if (slot < s.n_inst) l.inst = s.blocked && s.inst_map ? (int64_t)s.inst_map[slot] : slot;
+  const bool mapped = s.blocked && s.inst_map;
+  if (slot < s.n_inst) l.inst = mapped ? (int64_t)s.inst_map[slot] : slot;
   l.in = l.inst >= s.lo && l.inst < s.hi;
+  bool member = true;
+  if (s.where) {  // (uniform over the grid)
+    if (mapped) {
+      if (l.in) member = (s.where[l.inst >> 6] >> (l.inst & 63)) & 1ULL;
+    } else {
+      // t is the same in every lane of the wave: a scalar load
+      const uint32_t t_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)t);
+      const uint32_t t_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)((uint64_t)t >> 32));
+      member = (s.where[((uint64_t)t_hi << 32) | t_lo] >> lane) & 1ULL;
+    }
+  }
   if (l.in) {
     l.ok = s.regs[l.inst * R_NUM + R_STATUS] == ST_OK;
-    l.tick = s.snap_tick[l.inst * s.s_cap + s.sid];
-    l.sample = l.ok && l.tick >= 0;
+    if (member) {
+      l.tick = s.snap_tick[l.inst * s.s_cap + s.sid];
+      l.sample = l.ok && l.tick >= 0;
+    }
   }
   return l;
 }

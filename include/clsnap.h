@@ -447,6 +447,70 @@ int cl_select_stage_times(cl_sim* sim, double* evaluate_ms, double* compact_ms);
  * flush and lock behaviour and argument checks as the result queries above. */
 int cl_snapshot_ticks(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, int32_t* out /* [hi-lo], -1 = not complete */);
 
+/* ---- instance sets: statistics, census and selection over a set of instances ------------------
+ * The three calls above describe one snapshot id over an index range.  A cl_iset is a subset of
+ * [0, n_instances) kept on the device as a bitmap (ceil(n_instances / 64) 64-bit words, bit
+ * inst % 64 of word inst / 64; the bits at and above n_instances are always 0), so the answer of
+ * one call can condition the next: the statistics of a census class, the completion ticks of the
+ * instances in which a channel recorded a message, the outcomes of snapshot 4 among the runs in
+ * which snapshot 0 finished late.  A set is made from select clauses or from an index list, sets
+ * combine with each other, and the cl_*_in calls take one as a fourth condition of their sample.
+ *
+ * A set belongs to the sim it was made from and is only a set of indices: it stays valid across
+ * cl_rerun, engine switches and both record layouts, and says nothing about a snapshot id -- a set
+ * made from clauses on one sid may condition the analysis of another.  Its bitmap is allocated by
+ * the first call that needs it on the device (a set made from a list before anything has run keeps
+ * the list until then).  cl_iset_destroy frees a set; cl_sim_destroy frees the sets still alive,
+ * whose handles are dead from then on.  Every call holds the lock of the set's sim, like the other
+ * result queries.
+ *
+ * cl_iset_from_clauses  the arguments, argument checks and `info` of cl_select_instances without
+ *     its output arrays: the set holds every match (there is no cap), info->n_returned is 0.
+ * cl_iset_from_list     the listed instances; any order, duplicates allowed, n == 0 gives the empty
+ *     set.  CL_E_INVALID, before any device work, for an index outside [0, n_instances), n < 0 or a
+ *     NULL list with n > 0.
+ * cl_iset_combine       dst = a AND b, a OR b, or a AND NOT b (CL_ISET_*); dst may be a or b.
+ *     CL_E_INVALID for a NULL set, an unknown op, or sets of different sims.
+ * cl_iset_count         *n = members in [inst_lo, inst_hi).
+ * cl_iset_read          the members in [inst_lo, inst_hi) as ascending absolute indices, the first
+ *     `cap` of them; *n_match counts them all, so truncation shows as n_match > cap, as in
+ *     cl_select_instances.  cap == 0 with insts == NULL only counts.
+ * cl_iset_time          device time of the kernels of the latest cl_iset_from_list (when it ran its
+ *     scatter), cl_iset_combine, cl_iset_count or cl_iset_read (HIP events); cl_iset_from_clauses is
+ *     timed by cl_select_time. */
+#define CL_ISET_AND    0
+#define CL_ISET_OR     1
+#define CL_ISET_ANDNOT 2
+typedef struct cl_iset cl_iset;
+int cl_iset_from_clauses(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi,
+                         const cl_select_clause* clauses, int32_t n_clauses, cl_iset** out, cl_select_info* info);
+int cl_iset_from_list(cl_sim* sim, const int64_t* insts, int64_t n, cl_iset** out);
+int cl_iset_combine(cl_iset* dst, const cl_iset* a, const cl_iset* b, int32_t op);
+int cl_iset_count(cl_iset* set, int64_t inst_lo, int64_t inst_hi, int64_t* n);
+int cl_iset_read(cl_iset* set, int64_t inst_lo, int64_t inst_hi, int64_t* insts /* [cap] or NULL iff cap == 0 */,
+                 int64_t cap, int64_t* n_match);
+int cl_iset_destroy(cl_iset* set);
+int cl_iset_time(cl_sim* sim, double* device_ms);
+/* The conditional forms of cl_snapshot_stats, cl_snapshot_census and cl_select_instances.  The
+ * sample is the intersection of four conditions: member of `in`, in [inst_lo, inst_hi), status
+ * CL_INST_OK, snapshot sid completed.  `instances` and `ok` still count the whole range, exactly as
+ * the unconditional calls report them; `sample` and everything reduced from it -- sums, minima,
+ * maxima, histograms, classes, class_of (-1 outside the sample), matches -- is conditional.  The
+ * results have the shapes of the unconditional calls and merge like them.  With a set that holds
+ * the whole batch a call returns byte for byte what the unconditional call returns.  CL_E_INVALID
+ * for a NULL set or a set of another sim; every other check, the CL_E_STATE and CL_E_LIMIT
+ * behaviour, the flush that adds no tick, the lock and the wait for a split replay's second half
+ * are those of the unconditional call.  Their device times are read with cl_stats_time,
+ * cl_census_time and cl_select_time. */
+int cl_snapshot_stats_in(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_iset* in,
+                         const cl_stats_spec* spec, int64_t* out, int64_t out_words);
+int cl_snapshot_census_in(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_iset* in,
+                          const cl_census_spec* spec, cl_census_class* classes, int32_t* class_of,
+                          cl_census_info* info);
+int cl_select_instances_in(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_iset* in,
+                           const cl_select_clause* clauses, int32_t n_clauses, int64_t* insts, int32_t* ticks,
+                           int64_t cap, cl_select_info* info);
+
 /* ---- device event trace: the reference's debug Logger (logger.go:12-76) ---- */
 /* One LogEvent (logger.go:18-23) per record, in the Logger's order.  Node ranks refer
  * to cl_node_id; `other` is the peer of a Sent/Received record (-1 for Start/End and

@@ -1,0 +1,362 @@
+"""InstanceSet (cl_iset, cl_iset.hip) and the conditional analytics -- snapshot_stats_in,
+snapshot_census_in, select_instances_in (the `where` filter of the sample walk, cl_sample.h) --
+against the oracle.
+
+Expected values: isetcheck turns a set into a boolean mask over the oracle's instances; the existing
+expected() functions of statscheck, censuscheck and selectcheck then give the conditional result,
+which must be equal exactly.  With a set that holds the whole batch the conditional calls must
+return byte for byte what the unconditional calls return.  Scenarios, ranges and layouts are those
+of the statistics, census and select tests (instance-major after flush(), block-major by slot after
+rerun() of a mapped plan).
+"""
+import importlib
+
+import numpy as np
+import pytest
+
+import censuscheck
+import oracle as O
+import selectcheck
+import statscheck
+from isetcheck import clause_mask, keys_in, list_mask, members, rows_in
+from selectcheck import assert_selection_equal, from_refs, scenario
+from snapcheck import read_text
+from statscheck import RING_EVENTS, RING_TOP, assert_stats_equal
+from test_census_gpu import (AUTO, C3_EVENTS, C3_TOP, ENGINES, HUB_EVENTS, HUB_TOP, both_layouts, make_sim,
+                             replay_blocked)
+from test_select_gpu import C3_SID0
+
+cl = importlib.import_module("chandy-lamport-distributed-snapshot-algorithm_amd")
+pytestmark = pytest.mark.gpu
+
+N = 4096                        # the smallest batch that gets a mapped block-major replay
+RANGES = [(0, N), (37, 3001)]
+SPEC = dict(tick_lo=0, tick_bins=64, msg_bins=4)
+SPARSE, DENSE, NEGATED, NOTHING = C3_SID0[0], C3_SID0[2], C3_SID0[6], C3_SID0[9]
+INNER = [[], [("tick", None, 19, 24)], [("node", 4, 1, 4, "not")]]   # clauses evaluated inside a set
+
+
+def check_in(sim, rows, keys, mask, iset, sid, ranges, what, wheres=INNER, spec=SPEC):
+    """Conditional statistics, census (with class_of) and selections of `sid` over `iset` against
+    the oracle rows restricted to `mask`."""
+    rin, kin = rows_in(rows, mask), keys_in(keys, mask)
+    layout = sim.stats_layout(**spec)
+    for lo, hi in ranges:
+        tag = f"{what} sid {sid} [{lo}, {hi})"
+        st = sim.snapshot_stats_in(sid, iset, lo, hi, **spec)
+        assert st.layout == layout
+        assert_stats_equal(st.raw, statscheck.expected(layout, rin, sid, lo, hi), layout, tag)
+        assert st.instances == hi - lo and st.ok == int((rows.status[lo:hi] == O.OK).sum())   # the range's
+        census = sim.snapshot_census_in(sid, iset, lo, hi, class_of=True)
+        censuscheck.assert_census_equal(census, censuscheck.expected(kin, sid, lo, hi), tag)
+        for where in wheres:
+            got = sim.select_instances_in(sid, iset, where, lo, hi, ticks=True)
+            assert_selection_equal(got, selectcheck.expected(rin, kin, sid, lo, hi, where), f"{tag} where {where}")
+
+
+def assert_identity(sim, whole, sids, ranges, what):
+    """With the whole batch as the set, every conditional call returns the unconditional call's bytes."""
+    for sid in sids:
+        for lo, hi in ranges:
+            tag = f"{what} sid {sid} [{lo}, {hi})"
+            a, b = sim.snapshot_stats(sid, lo, hi, **SPEC), sim.snapshot_stats_in(sid, whole, lo, hi, **SPEC)
+            assert a.raw.tobytes() == b.raw.tobytes(), tag
+            a = sim.snapshot_census(sid, lo, hi, class_of=True)
+            b = sim.snapshot_census_in(sid, whole, lo, hi, class_of=True)
+            assert (a.instances, a.ok, a.sample, a.n_classes) == (b.instances, b.ok, b.sample, b.n_classes), tag
+            assert a.classes.tobytes() == b.classes.tobytes() and a.class_of.tobytes() == b.class_of.tobytes(), tag
+            for where in INNER:
+                a = sim.select_instances(sid, where, lo, hi, ticks=True)
+                b = sim.select_instances_in(sid, whole, where, lo, hi, ticks=True)
+                assert a == b, f"{tag} where {where}"
+
+
+# ---- 1: the whole batch as the set: the invariant that ties the filtered walk to the plain one ----
+@ENGINES
+def test_whole_batch_set_is_the_unconditional_call(engine):
+    rows, _ = scenario(C3_TOP, C3_EVENTS, N)
+    outside = np.flatnonzero(~rows.done[0])
+    assert outside.size == 117                                        # the fatal instances
+    sim = make_sim(C3_TOP, C3_EVENTS, N, engine)
+    sample = sim.instance_set(0, [])                                  # the sample of sid 0 ...
+    assert sample.info == (N, 3979, 3979, 3979) and len(sample) == 3979
+    by_clauses = sample | sim.instance_set_from(outside)              # ... and everything else
+    by_list = sim.instance_set_from(np.arange(N))
+    assert len(by_clauses) == len(by_list) == N
+    assert np.array_equal(by_list.insts(), np.arange(N))
+
+    def body(what):
+        for name, whole in (("clauses | list", by_clauses), ("arange", by_list)):
+            assert_identity(sim, whole, (0, 3), RANGES, f"{what} {name}")
+
+    both_layouts(sim, engine, body)
+
+
+# ---- 2: a set made from clauses on the snapshot that is then analysed ---------------------------------
+def test_same_sid_conditioning_against_the_oracle():
+    rows, keys = scenario(C3_TOP, C3_EVENTS, N)
+    sim = make_sim(C3_TOP, C3_EVENTS, N, AUTO)
+    cases = []
+    for name, where, size in (("sparse", SPARSE, 22), ("dense", DENSE, 1400), ("negated", NEGATED, None),
+                              ("nothing", NOTHING, 0)):
+        mask = clause_mask(rows, keys, 0, where)
+        assert size is None or int(mask.sum()) == size, name
+        iset = sim.instance_set(0, where)
+        assert iset.info == selectcheck.expected(rows, keys, 0, 0, N, where)[0], name
+        cases.append((name, mask, iset))
+    assert 0 < int(cases[2][1].sum()) < 3979
+
+    def body(what):
+        for name, mask, iset in cases:
+            assert len(iset) == int(mask.sum()) and np.array_equal(iset.insts(), members(mask)), name
+            check_in(sim, rows, keys, mask, iset, 0, RANGES, f"{what} {name}")
+
+    both_layouts(sim, AUTO, body)
+    # a set made over a sub-range holds matches of that range only
+    part = sim.instance_set(0, DENSE, 37, 3001)
+    want = clause_mask(rows, keys, 0, DENSE, 37, 3001)
+    assert part.info == selectcheck.expected(rows, keys, 0, 37, 3001, DENSE)[0]
+    assert np.array_equal(part.insts(), members(want))
+    check_in(sim, rows, keys, want, part, 0, [(0, N)], "block-major sub-range set")
+
+
+# ---- 3: a set made from one snapshot conditions the analysis of others --------------------------------
+def _drive(target, lines):
+    """The events of an .events text without the closing drain, so late snapshots stay incomplete in
+    some instances; target is a ChandyLamportSim or an OracleSim."""
+    engine = isinstance(target, cl.ChandyLamportSim)
+    for line in lines:
+        f = line.split()
+        if f[0] == "send":
+            if engine:
+                target.ProcessEvent(cl.PassTokenEvent(f[1], f[2], int(f[3])))
+            else:
+                target.send_tokens(f[1], f[2], int(f[3]))
+        elif f[0] == "snapshot":
+            if engine:
+                target.StartSnapshot(f[1])
+            else:
+                target.start_snapshot(f[1])
+        else:
+            for _ in range(int(f[1]) if len(f) > 1 else 1):
+                target.Tick(1) if engine else target.tick()
+
+
+def test_cross_sid_conditioning_with_incomplete_snapshots():
+    # C3's events, then 6 ticks and no drain: by then snapshot 0 is complete in 3557 instances,
+    # snapshots 3 and 4 (started at tick 13) in 1690 and 125
+    lines = [x for x in read_text(C3_EVENTS).splitlines() if x.strip()] + ["tick 6"]
+    refs = []
+    for i in range(N):
+        r = O.OracleSim()
+        r.seed_go(O.REFERENCE_SEED + i)
+        assert r.read_topology_text(read_text(C3_TOP)) == 0
+        _drive(r, lines)
+        refs.append(r)
+    rows, keys = from_refs(refs)
+    assert rows.n_sids == 5 and [int(d.sum()) for d in rows.done] == [3557, 3460, 3979, 1690, 125]
+    ok = rows.status == O.OK
+    early = [("tick", None, None, 18)]                                # sid 0 finished early
+    late = [("tick", None, 19, None), ("msgs", None, 1, None)]
+    sim = make_sim(C3_TOP, None, N, AUTO)
+    _drive(sim, lines)
+    for where in (early, late):
+        mask = clause_mask(rows, keys, 0, where)
+        assert mask.any() and (mask <= ok).all()
+        # snapshots 3 and 4 are incomplete in some members: set & completed(sid) is a proper subset
+        for sid in (3, 4):
+            both = int((mask & rows.done[sid]).sum())
+            assert 0 < both < int(mask.sum()), (where, sid)
+        iset = sim.instance_set(0, where)             # executes the pending events, adds no tick
+        assert iset.info == selectcheck.expected(rows, keys, 0, 0, N, where)[0]
+        for sid in (3, 4):
+            check_in(sim, rows, keys, mask, iset, sid, RANGES, f"undrained {where}", wheres=[[], [("msgs", None, 1, None)]])
+
+
+def test_cross_sid_conditioning_both_layouts():
+    rows, keys = scenario(C3_TOP, C3_EVENTS, N)
+    sim = make_sim(C3_TOP, C3_EVENTS, N, AUTO)
+    sets = [(where, clause_mask(rows, keys, 0, where), sim.instance_set(0, where)) for where in (SPARSE, DENSE)]
+
+    def body(what):
+        for where, mask, iset in sets:
+            for sid in (3, 4):
+                check_in(sim, rows, keys, mask, iset, sid, RANGES, f"{what} sid-0 set {where}",
+                         wheres=[[], [("msgs", None, 1, None)]])
+
+    both_layouts(sim, AUTO, body)
+
+
+# ---- 4: the algebra, ranged counts and listings ----------------------------------------------------
+def test_set_algebra_ranges_truncation_and_duplicates():
+    rows, keys = scenario(C3_TOP, C3_EVENTS, N)
+    sim = make_sim(C3_TOP, C3_EVENTS, N, AUTO)
+    wa, wb = DENSE, NEGATED
+    ma, mb = clause_mask(rows, keys, 0, wa), clause_mask(rows, keys, 0, wb)
+    assert (ma & mb).any() and (ma & ~mb).any() and (mb & ~ma).any()
+    a, b = sim.instance_set(0, wa), sim.instance_set(0, wb)
+    ranges = [(0, N), (37, 3001), (64, 128), (63, 65), (100, 100), (N - 1, N), (0, 1)]
+    for name, iset, mask in (("a", a, ma), ("a & b", a & b, ma & mb), ("a | b", a | b, ma | mb),
+                             ("a - b", a - b, ma & ~mb), ("b - a", b - a, mb & ~ma)):
+        assert len(iset) == int(mask.sum()), name
+        for lo, hi in ranges:
+            assert iset.count(lo, hi) == int(mask[lo:hi].sum()), f"{name} count [{lo}, {hi})"
+            got = iset.insts(lo, hi)
+            assert got.dtype == np.int64 and np.array_equal(got, members(mask, lo, hi)), f"{name} insts [{lo}, {hi})"
+        for lo, hi in RANGES:                                         # max_out: the smallest members
+            assert np.array_equal(iset.insts(lo, hi, max_out=10), members(mask, lo, hi)[:10]), name
+            assert iset.insts(lo, hi, max_out=0).size == 0
+            assert np.array_equal(iset.insts(lo, hi, max_out=N), members(mask, lo, hi))
+    assert sim.iset_time() >= 0
+    # dst may be an operand
+    c = sim.instance_set(0, wa)
+    assert c.combine_into(c, b, cl.ISET_ANDNOT) is c
+    assert np.array_equal(c.insts(), members(ma & ~mb))
+    c.combine_into(b, c, cl.ISET_OR)
+    assert np.array_equal(c.insts(), members(mb | (ma & ~mb)))
+    # a list with duplicates, in any order
+    listed = np.array([4095, 7, 7, 64, 63, 4095, 0, 128, 64], dtype=np.int64)
+    d = sim.instance_set_from(listed)
+    assert len(d) == 6 and np.array_equal(d.insts(), np.unique(listed))
+    assert np.array_equal((d | a).insts(), members(list_mask(N, listed) | ma))
+    # the set of a listing conditions like the set it came from
+    again = sim.instance_set_from(a.insts())
+    assert np.array_equal(again.insts(), a.insts())
+    check_in(sim, rows, keys, ma, again, 1, [(37, 3001)], "listed again")
+    empty = sim.instance_set_from(())
+    assert len(empty) == 0 and empty.insts().size == 0 and len(empty | empty) == 0
+    st = sim.snapshot_stats_in(0, empty)
+    assert (st.instances, st.ok, st.sample) == (N, 3979, 0)
+
+
+# ---- 5: ragged batches: no bit at or past n_instances, ever ------------------------------------------
+@pytest.mark.parametrize("n", [1, 63, 65, 200])
+def test_ragged_batch_sizes(n):
+    rows, keys = scenario(C3_TOP, C3_EVENTS, N)      # (instance i is seeded by i alone)
+    sim = make_sim(C3_TOP, C3_EVENTS, n, AUTO)
+    sim.flush()
+    assert not sim.records_blocked()
+    la, lb = np.arange(0, n, 3), np.array([n - 1, 0, n - 1] + list(range(n // 2, n)))
+    ma, mb = list_mask(n, la), list_mask(n, lb)
+    a, b = sim.instance_set_from(la), sim.instance_set_from(lb)
+    sample = sim.instance_set(0, [])
+    ms = rows.done[0][:n]
+    for name, iset, mask in (("a", a, ma), ("a | b", a | b, ma | mb), ("a - b", a - b, ma & ~mb),
+                             ("b - a", b - a, mb & ~ma), ("sample", sample, ms), ("a - sample", a - sample, ma & ~ms),
+                             ("(a | b) - (a & b)", (a | b) - (a & b), ma ^ mb)):
+        got = iset.insts()
+        assert len(iset) == int(mask.sum()) <= n and np.array_equal(got, members(mask)), name
+        assert got.size == 0 or got[-1] < n
+        assert iset.count(0, n) == iset.count(n // 2, n) + iset.count(0, n // 2)
+    whole = (a | b) | sim.instance_set_from(np.arange(n))
+    assert len(whole) == n
+    full = np.zeros(N, dtype=bool)
+    for name, iset, mask in (("whole", whole, np.ones(n, dtype=bool)), ("a | b", a | b, ma | mb)):
+        full[:] = False
+        full[:n] = mask
+        for sid in (0, 4):
+            check_in(sim, rows, keys, full, iset, sid, [(0, n)], f"n = {n} {name}", wheres=[[]])
+
+
+# ---- 6: long records (not staged, staged word by word) and the multi-pass statistics -----------------
+def _halves(rows, keys, sid):
+    """A clause on the completion tick that splits the sample of `sid` near the middle."""
+    t = np.sort(rows.tick[sid][rows.done[sid]])
+    where = [("tick", None, None, int(t[t.size // 2]))]
+    mask = clause_mask(rows, keys, sid, where)
+    assert 0 < int(mask.sum()) < int(rows.done[sid].sum())
+    return where, mask
+
+
+def test_hub_three_word_records_both_layouts():
+    rows, keys = scenario(HUB_TOP, HUB_EVENTS, N)
+    assert (rows.status == O.OK).all() and rows.n_sids == 4
+    sim = make_sim(HUB_TOP, HUB_EVENTS, N, AUTO)
+    assert sim.num_nodes * 3 == 33                              # 33 record words: not staged in LDS
+    where, mask = _halves(rows, keys, 1)
+    iset = sim.instance_set(1, where)
+    few = sim.instance_set(0, [("node", 4, 5, None, "not")])
+    mfew = clause_mask(rows, keys, 0, [("node", 4, 5, None, "not")])
+    assert int(mfew.sum()) == 507
+    inner = [[], [("ch_msgs", 11, 1, 1)]]
+
+    def body(what):
+        for sid in (1, 3):
+            check_in(sim, rows, keys, mask, iset, sid, RANGES, f"hub {what} halves", wheres=inner)
+        check_in(sim, rows, keys, mfew, few, 2, RANGES, f"hub {what} few", wheres=inner)
+
+    both_layouts(sim, AUTO, body)
+
+
+def test_ring_two_word_records_both_layouts():
+    rows, keys = scenario(RING_TOP, RING_EVENTS, N)
+    assert int((rows.status == O.OK).sum()) == 2417
+    sim = make_sim(RING_TOP, RING_EVENTS, N, AUTO)
+    where = [("msgs", None, 2, None)]
+    mask = clause_mask(rows, keys, 0, where)
+    assert int(mask.sum()) == 813
+    iset = sim.instance_set(0, where)
+
+    def body(what):
+        for sid in range(2):
+            check_in(sim, rows, keys, mask, iset, sid, RANGES, f"ring {what}", wheres=[[], [("ch_tok", 1, 2, None)]])
+
+    both_layouts(sim, AUTO, body)
+
+
+def test_multi_pass_statistics_over_half_the_sample():
+    n, k = 128, 24                                   # test_stats_gpu's accumulators-beyond-LDS topology
+    ids = [f"N{v:02d}" for v in range(k)]
+    top = f"{k}\n" + "".join(f"{x} 100\n" for x in ids) + "".join(f"{a} {b}\n" for a in ids for b in ids if a != b)
+    events = ("send N00 N01 3\nsend N05 N02 1\nsnapshot N03\nsend N01 N00 2\ntick 1\n"
+              "send N10 N11 4\nsnapshot N20\nsend N02 N05 1\ntick 2\n")
+    rows = statscheck.scenario_rows(top, events, n)
+    assert (rows.status == O.OK).all() and rows.n_sids == 2
+    where, mask = _halves(rows, None, 0)
+    sim = make_sim(top, events, n, AUTO)
+    assert sim.num_channels == 552
+    iset = sim.instance_set(0, where)
+    assert np.array_equal(iset.insts(), members(mask))
+    spec = dict(tick_lo=0, tick_bins=4096, msg_bins=64)          # several passes over chunk ranges
+    layout = sim.stats_layout(**spec)
+    for sid in range(2):
+        st = sim.snapshot_stats_in(sid, iset, 5, 70, **spec)
+        assert_stats_equal(st.raw, statscheck.expected(layout, rows_in(rows, mask), sid, 5, 70), layout,
+                           f"24-node complete digraph sid {sid}")
+    whole = sim.instance_set_from(np.arange(n))
+    assert sim.snapshot_stats_in(0, whole, 5, 70, **spec).raw.tobytes() == sim.snapshot_stats(0, 5, 70, **spec).raw.tobytes()
+
+
+# ---- 7: lifetime ---------------------------------------------------------------------------------------
+def test_sets_outlive_reruns_and_die_with_their_sim():
+    rows, keys = scenario(C3_TOP, C3_EVENTS, N)
+    sim = make_sim(C3_TOP, C3_EVENTS, N, AUTO)
+    sim.flush()
+    mask = clause_mask(rows, keys, 0, DENSE)
+    iset = sim.instance_set(0, DENSE)
+    listed = sim.instance_set_from(members(mask))
+    before = sim.snapshot_stats_in(3, iset, **SPEC)
+    replay_blocked(sim)                                # the layout has switched to block-major
+    for s in (iset, listed):
+        assert sim.snapshot_stats_in(3, s, **SPEC) == before
+        assert np.array_equal(s.insts(), members(mask))
+    check_in(sim, rows, keys, mask, listed, 3, [(37, 3001)], "after rerun")
+    iset.close()
+    iset.close()                                       # closing twice is harmless
+    with pytest.raises(ValueError):
+        sim.snapshot_stats_in(3, iset)
+    with sim.instance_set(0, SPARSE) as tmp:
+        assert len(tmp) == 22
+    assert tmp._h is None
+    # the sim goes with sets alive (listed, and two more); their handles are dead, closing them is not
+    more = [sim.instance_set(1, []), sim.instance_set_from([1, 2, 3])]
+    sim.__del__()
+    for s in [listed] + more:
+        s.close()
+    # ... and a new sim is unharmed: the identity on the smallest case
+    sim = make_sim(C3_TOP, C3_EVENTS, N, AUTO)
+    whole = sim.instance_set_from(np.arange(N))        # before anything has run: the list waits for the device
+    some = sim.instance_set_from([5, 64, 4000]) | sim.instance_set_from([64, 65])
+    sim.flush()
+    assert_identity(sim, whole, (0,), [(37, 3001)], "new sim")
+    assert some.insts().tolist() == [5, 64, 65, 4000]
