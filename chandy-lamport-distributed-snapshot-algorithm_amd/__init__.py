@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 __all__ = ["ChandyLamportSim", "SnapshotStats", "STATS_LAYOUT_FIELDS", "SnapshotSelection", "SELECT_CLAUSE_DTYPE",
-           "InstanceSet",
+           "InstanceSet", "SnapshotCrosstab", "CROSSTAB_AXIS_DTYPE",
 "GlobalSnapshot", "MsgSnapshot", "PassTokenEvent", "SnapshotEvent",
            "ClSnapError", "lib", "go_delay_schedule", "go_delay_schedule_device", "go_delay_schedule_jump",
            "DELAYGEN_MAX_DRAWS", "go_int63", "go_intn", "REFERENCE_SEED",
@@ -146,6 +146,9 @@ def lib():
         "cl_snapshot_stats_in": [vp, i32, i64, i64, vp, vp, vp, i64],
         "cl_snapshot_census_in": [vp, i32, i64, i64, vp, vp, vp, vp, vp],
         "cl_select_instances_in": [vp, i32, i64, i64, vp, vp, i32, vp, vp, i64, vp],
+        "cl_snapshot_crosstab": [vp, i64, i64, vp, vp, vp, i64],
+        "cl_snapshot_crosstab_in": [vp, i64, i64, vp, vp, vp, vp, i64],
+        "cl_crosstab_time": [vp, vp],
         "cl_set_delay_go_seed_list": [vp, vp, i64],
         "cl_set_delay_generator": [vp, i32],
         "cl_delay_generator": [vp, vp],
@@ -479,6 +482,28 @@ SELECT_NOT = 1
 SELECT_MAX_CLAUSES = 8
 
 
+def _field_index(what, field, index, ids, chans):
+    """The `index` of a select clause or crosstab axis as the C ABI takes it: a node id or rank
+    ("node"), a channel number or (src, dest) pair of ids or ranks ("ch_msgs", "ch_tok"), None for
+    the fields that take none; ids = node ids by rank, chans = (src rank, dest rank) per channel."""
+    if field == "node":
+        if isinstance(index, str):
+            if index not in ids:
+                raise ValueError(f"{what}: no node {index!r}")
+            index = ids.index(index)
+    elif field in ("ch_msgs", "ch_tok"):
+        if isinstance(index, (tuple, list)):
+            pair = tuple(ids.index(x) if isinstance(x, str) and x in ids else x for x in index)
+            if pair not in chans:
+                raise ValueError(f"{what}: no channel {tuple(index)!r}")
+            index = chans.index(pair)
+    elif index is None:
+        index = 0
+    if index is None or isinstance(index, (str, tuple, list)):
+        raise ValueError(f"{what}: {field!r} does not take index {index!r}")
+    return int(index)
+
+
 def _select_clauses(where, ids, chans):
     """`where` of ChandyLamportSim.select_instances as a SELECT_CLAUSE_DTYPE array; ids = node ids
     by rank, chans = (src rank, dest rank) per channel."""
@@ -491,21 +516,7 @@ def _select_clauses(where, ids, chans):
         field, index, lo, hi = clause[:4]
         if field not in SELECT_FIELDS:
             raise ValueError(f"select clause {q}: field must be one of {SELECT_FIELDS}")
-        if field == "node":
-            if isinstance(index, str):
-                if index not in ids:
-                    raise ValueError(f"select clause {q}: no node {index!r}")
-                index = ids.index(index)
-        elif field in ("ch_msgs", "ch_tok"):
-            if isinstance(index, (tuple, list)):
-                pair = tuple(ids.index(x) if isinstance(x, str) and x in ids else x for x in index)
-                if pair not in chans:
-                    raise ValueError(f"select clause {q}: no channel {tuple(index)!r}")
-                index = chans.index(pair)
-        elif index is None:
-            index = 0
-        if index is None or isinstance(index, (str, tuple, list)):
-            raise ValueError(f"select clause {q}: {field!r} does not take index {index!r}")
+        index = _field_index(f"select clause {q}", field, index, ids, chans)
         if field == "key":
             lo, hi = 0 if lo is None else int(lo), 2**64 - 1 if hi is None else int(hi)
             if not (0 <= lo < 2**64 and 0 <= hi < 2**64):
@@ -575,6 +586,129 @@ class SnapshotSelection:
 
 
 ISET_AND, ISET_OR, ISET_ANDNOT = range(3)   # include/clsnap.h CL_ISET_*
+
+
+# cl_crosstab_axis (include/clsnap.h) and the words of the flat result (CL_XT_*)
+CROSSTAB_AXIS_DTYPE = np.dtype([("sid", np.int32), ("field", np.int32), ("index", np.int32), ("bins", np.int32),
+                                ("lo", np.int64), ("width", np.int64)])
+CROSSTAB_FIELDS = SELECT_FIELDS[:6]     # every select field but "key": a hash is not binnable
+CROSSTAB_MAX_BINS = CROSSTAB_MAX_CELLS = 4096
+(XT_INSTANCES, XT_OK, XT_SAMPLE, XT_SUM_A, XT_SUM_B, XT_SUM_AA, XT_SUM_AB, XT_SUM_BB, XT_MIN_A, XT_MIN_B, XT_MAX_A,
+ XT_MAX_B, XT_CELLS) = range(13)
+
+
+def _crosstab_axis(name, axis, ids, chans):
+    """An axis of ChandyLamportSim.snapshot_crosstab, (sid, field, index, lo, width, bins), as a
+    CROSSTAB_AXIS_DTYPE record; ValueError for anything the C call would have to refuse by shape."""
+    what = f"crosstab axis {name}"
+    if not isinstance(axis, (tuple, list)) or len(axis) != 6:
+        raise ValueError(f"{what}: (sid, field, index, lo, width, bins)")
+    sid, field, index, lo, width, bins = axis
+    if field not in CROSSTAB_FIELDS:
+        raise ValueError(f"{what}: field must be one of {CROSSTAB_FIELDS}")
+    index = _field_index(what, field, index, ids, chans)
+    i64 = np.iinfo(np.int64)
+    for k, v in (("sid", sid), ("lo", lo), ("width", width), ("bins", bins)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what}: {k} must be an integer")
+    if not (0 <= sid <= np.iinfo(np.int32).max and i64.min <= lo <= i64.max and 1 <= width <= i64.max
+            and 1 <= bins <= CROSSTAB_MAX_BINS):
+        raise ValueError(f"{what}: sid >= 0, int64 lo, width >= 1, 1 <= bins <= {CROSSTAB_MAX_BINS}")
+    out = np.zeros(1, dtype=CROSSTAB_AXIS_DTYPE)
+    out[0] = (sid, CROSSTAB_FIELDS.index(field), index, bins, lo, width)
+    return out
+
+
+class SnapshotCrosstab:
+    """The result of ``ChandyLamportSim.snapshot_crosstab``: the joint distribution of two snapshot
+    quantities over the OK instances in which the snapshots of both axes completed.
+
+    ``axes`` is the pair of CROSSTAB_AXIS_DTYPE records, ``raw`` the flat int64 array of
+    cl_snapshot_crosstab (include/clsnap.h CL_XT_*).  ``instances``, ``ok`` count the range,
+    ``sample`` the joint sample; ``table`` is the int64 [bins_a, bins_b] view of the cells; ``min``
+    and ``max`` are the (a, b) pairs (INT64_MAX / INT64_MIN on an empty sample).  The sums of
+    products are modulo 2**64."""
+
+    def __init__(self, axes, raw):
+        a, b = (np.array(x, dtype=CROSSTAB_AXIS_DTYPE).reshape(1) for x in axes)
+        self.axes = (a, b)
+        self.raw = np.ascontiguousarray(raw, dtype=np.int64)
+        if self.raw.shape != (XT_CELLS + self.shape[0] * self.shape[1],):
+            raise ValueError(f"SnapshotCrosstab: raw must hold {XT_CELLS} + bins_a * bins_b int64 words")
+
+    @property
+    def shape(self):
+        return int(self.axes[0]["bins"][0]), int(self.axes[1]["bins"][0])
+
+    instances = property(lambda self: int(self.raw[XT_INSTANCES]))
+    ok = property(lambda self: int(self.raw[XT_OK]))
+    sample = property(lambda self: int(self.raw[XT_SAMPLE]))
+    min = property(lambda self: (int(self.raw[XT_MIN_A]), int(self.raw[XT_MIN_B])))
+    max = property(lambda self: (int(self.raw[XT_MAX_A]), int(self.raw[XT_MAX_B])))
+
+    @property
+    def table(self):
+        return self.raw[XT_CELLS:].reshape(self.shape)
+
+    def marginal(self, axis):
+        """The histogram of one axis (0: a, 1: b) over the joint sample."""
+        return self.table.sum(axis=1 - self._axis(axis))
+
+    @staticmethod
+    def _axis(axis):
+        if axis not in (0, 1):
+            raise ValueError("SnapshotCrosstab: axis must be 0 or 1")
+        return axis
+
+    def _sum(self, word):
+        return int(self.raw[word])
+
+    def _sumsq(self, word):
+        return int(self.raw[word]) & (2**64 - 1)
+
+    def mean(self, axis):
+        """Mean of axis 0 (a) or 1 (b) over the sample; nan on an empty sample."""
+        n = self.sample
+        return self._sum(XT_SUM_A + self._axis(axis)) / n if n else float("nan")
+
+    def variance(self, axis):
+        """Population variance of an axis from the exact integer moments (valid while the true sum
+        of squares is below 2**64, as SnapshotStats.variance); nan on an empty sample."""
+        n, k = self.sample, self._axis(axis)
+        s, q = self._sum(XT_SUM_A + k), self._sumsq(XT_SUM_BB if k else XT_SUM_AA)
+        return (n * q - s * s) / (n * n) if n else float("nan")
+
+    def covariance(self):
+        """Population covariance of the two axes (valid while the true sum of products lies in
+        [-2**63, 2**63): the wrapped word is read as int64); nan on an empty sample."""
+        n = self.sample
+        return (n * self._sum(XT_SUM_AB) - self._sum(XT_SUM_A) * self._sum(XT_SUM_B)) / (n * n) if n else float("nan")
+
+    def correlation(self):
+        """Pearson correlation of the two axes; nan on an empty sample or a constant axis."""
+        va, vb = self.variance(0), self.variance(1)
+        if not (va > 0 and vb > 0):
+            return float("nan")
+        return self.covariance() / float(np.sqrt(va) * np.sqrt(vb))
+
+    def merge(self, other):
+        """The crosstab of the union of two disjoint samples (other ranks, other instance ranges):
+        a wrapping SUM over the counters, sums and cells, MIN and MAX over the extrema.  Raises
+        ValueError when the axes differ."""
+        if not isinstance(other, SnapshotCrosstab) or any(x.tobytes() != y.tobytes()
+                                                          for x, y in zip(self.axes, other.axes)):
+            raise ValueError("SnapshotCrosstab.merge: the axes differ")
+        raw = (self.raw.view(np.uint64) + other.raw.view(np.uint64)).view(np.int64)  # wraps
+        raw[XT_MIN_A:XT_MAX_A] = np.minimum(self.raw[XT_MIN_A:XT_MAX_A], other.raw[XT_MIN_A:XT_MAX_A])
+        raw[XT_MAX_A:XT_CELLS] = np.maximum(self.raw[XT_MAX_A:XT_CELLS], other.raw[XT_MAX_A:XT_CELLS])
+        return SnapshotCrosstab(self.axes, raw)
+
+    def __eq__(self, other):
+        return (isinstance(other, SnapshotCrosstab)
+                and all(x.tobytes() == y.tobytes() for x, y in zip(self.axes, other.axes))
+                and bool(np.array_equal(other.raw, self.raw)))
+
+    __hash__ = None
 
 
 class InstanceSet:
@@ -924,6 +1058,44 @@ class ChandyLamportSim:
     def select_instances_in(self, snapshot_id, iset, where=(), inst_lo=0, inst_hi=None, max_out=None, ticks=False):
         """select_instances over the members of the InstanceSet `iset` (cl_select_instances_in)."""
         return self._select(iset, snapshot_id, where, inst_lo, inst_hi, max_out, ticks)
+
+    def crosstab_axis(self, axis, name="a"):
+        """An axis of snapshot_crosstab, (sid, field, index, lo, width, bins), as a
+        CROSSTAB_AXIS_DTYPE record (host only): index normalised as in select_clauses."""
+        return _crosstab_axis(name, axis, self.node_ids(), self.channels())
+
+    def snapshot_crosstab(self, a, b, inst_lo=0, inst_hi=None):
+        """The joint distribution of two snapshot quantities over the OK instances of
+        [inst_lo, inst_hi) in which the snapshots of both axes completed, reduced on the GPU
+        (cl_snapshot_crosstab): a SnapshotCrosstab with the contingency table and the joint
+        moments.  An axis is (sid, field, index, lo, width, bins): field one of CROSSTAB_FIELDS,
+        index as in a select clause, bin(v) = 0 below lo, else min((v - lo) // width, bins - 1).
+        The axes may name different snapshot ids."""
+        return self._crosstab(None, a, b, inst_lo, inst_hi)
+
+    def _crosstab(self, iset, a, b, inst_lo, inst_hi):
+        hi = self.n_instances if inst_hi is None else inst_hi
+        a, b = self.crosstab_axis(a, "a"), self.crosstab_axis(b, "b")
+        if int(a["bins"][0]) * int(b["bins"][0]) > CROSSTAB_MAX_CELLS:
+            raise ValueError(f"crosstab: bins_a * bins_b <= {CROSSTAB_MAX_CELLS}")
+        raw = np.zeros(XT_CELLS + int(a["bins"][0]) * int(b["bins"][0]), dtype=np.int64)
+        if iset is None:
+            _check(self._L.cl_snapshot_crosstab(self._h, inst_lo, hi, _p(a), _p(b), _p(raw), raw.size))
+        else:
+            _check(self._L.cl_snapshot_crosstab_in(self._h, inst_lo, hi, iset._handle(), _p(a), _p(b), _p(raw),
+                                                   raw.size))
+        return SnapshotCrosstab((a, b), raw)
+
+    def snapshot_crosstab_in(self, iset, a, b, inst_lo=0, inst_hi=None):
+        """snapshot_crosstab over the members of the InstanceSet `iset` (cl_snapshot_crosstab_in);
+        `instances` and `ok` still count the whole range."""
+        return self._crosstab(iset, a, b, inst_lo, inst_hi)
+
+    def crosstab_time(self):
+        """Device ms of the latest snapshot_crosstab kernel."""
+        ms = C.c_double(0)
+        _check(self._L.cl_crosstab_time(self._h, C.byref(ms)))
+        return ms.value
 
     def instance_set(self, snapshot_id, where=(), inst_lo=0, inst_hi=None):
         """The InstanceSet of the instances select_instances(snapshot_id, where, inst_lo, inst_hi)

@@ -666,4 +666,35 @@ int launch_iset_combine(unsigned long long* dst, const unsigned long long* a, co
 int launch_iset_clip(unsigned long long* dst, const unsigned long long* src, int64_t lo, int64_t hi, void* stream);
 int launch_iset_count(const unsigned long long* src, int64_t lo, int64_t hi, unsigned long long* count, void* stream);
 
+// ---- joint distribution of two snapshot quantities (cl_crosstab.hip; include/clsnap.h cl_snapshot_crosstab) ----
+// A two-axis contingency table with the five joint moments over the instances of [lo, hi) with
+// status OK in which the snapshots of both axes completed.  An axis is one of the quantities a
+// select clause names (SEL_TICK .. SEL_CH_TOK) of one snapshot id, binned:
+//   bin(v) = v < lo ? 0 : min((uint64)(v - lo) / width, bins - 1).
+struct CrosstabAxis {  // the layout of cl_crosstab_axis
+  int32_t sid, field, index, bins;
+  int64_t lo, width;
+};
+constexpr int32_t kXtMaxBins = 4096;   // per axis
+constexpr int32_t kXtMaxCells = 4096;  // bins_a * bins_b: 16 KB of 32-bit workgroup counters
+constexpr int32_t kXtThreads = 256;
+// Words of the flat int64 result (CL_XT_*): wrapping sums, then minima, maxima and the cells.
+enum : int32_t {
+  XT_INSTANCES = 0, XT_OK = 1, XT_SAMPLE = 2, XT_SUM_A = 3, XT_SUM_B = 4, XT_SUM_AA = 5, XT_SUM_AB = 6, XT_SUM_BB = 7,
+  XT_MIN_A = 8, XT_MIN_B = 9, XT_MAX_A = 10, XT_MAX_B = 11, XT_CELLS = 12,
+};
+struct CrosstabParams {
+  SampleParams s;            // the walk, and the planes of axis a's snapshot (s.sid == a.sid)
+  CrosstabAxis a, b;
+  const int32_t* ch_slot;    // [C] record word of channel c
+  const int32_t* hist_off;   // [C + 1]
+  const long long* hist_pre; // as StatsParams::hist_pre
+  int32_t staged;            // N * rw <= kCensusStageWords: the planes an axis reads are staged in LDS
+  long long* out;            // [XT_CELLS + a.bins * b.bins], initialised by the host (0 / INT64_MAX / INT64_MIN)
+};
+inline int32_t crosstab_lds_bytes(int32_t cells, bool staged) {
+  return 16 * 8 + cells * 4 + (staged ? kWavesPerBlock * kStatsStageWords * 4 : 0);
+}
+int launch_crosstab(const CrosstabParams& p, int32_t blocks, void* stream);
+
 }  // namespace clsnap

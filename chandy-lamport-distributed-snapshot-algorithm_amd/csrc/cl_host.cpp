@@ -535,6 +535,10 @@ struct cl_sim {
   DevBuf<unsigned long long> d_is_count;
   hipEvent_t is_ev[2] = {nullptr, nullptr};
   bool is_timed = false;
+  // joint distribution of two snapshot quantities (cl_snapshot_crosstab, cl_crosstab.hip): the result words
+  DevBuf<long long> d_xt;
+  hipEvent_t xt_ev[2] = {nullptr, nullptr};
+  bool xt_timed = false;
   size_t hist_uploaded = (size_t)-1;  // history entries on the device
 
   ~cl_sim() {
@@ -554,8 +558,10 @@ struct cl_sim {
       d_cs_class.release(); d_cs_rank.release(); d_pk_list.release();
       d_sel_bits.release(); d_sel_info.release(); d_sel_bsum.release(); d_sel_out.release(); d_sel_ticks.release();
       d_seeds.release(); d_dg_flag.release();
-      d_is_list.release(); d_is_count.release();
+      d_is_list.release(); d_is_count.release(); d_xt.release();
       for (cl_iset* s : isets) s->bits.release();
+      for (auto& e : xt_ev)
+        if (e) (void)hipEventDestroy(e);
       for (auto& e : is_ev)
         if (e) (void)hipEventDestroy(e);
       for (auto& e : dg_ev)
@@ -1664,6 +1670,44 @@ struct cl_sim {
     return CL_OK;
   }
 
+  // cl_snapshot_crosstab (arguments checked by the caller): the contingency table and joint
+  // moments of axes a and b over [lo, hi) into out[XT_CELLS + a->bins * b->bins].  One kernel; the
+  // walk is that of axis a's snapshot, the kernel takes axis b's planes from the same SampleParams.
+  int crosstab(int64_t lo, int64_t hi, const cl_crosstab_axis* a, const cl_crosstab_axis* b, int64_t* out,
+               cl_iset* in = nullptr) {
+    CrosstabParams p{};
+    int rc = sample_begin(a->sid, lo, hi, &p.s, in);
+    if (rc) return rc;
+    for (auto& e : xt_ev)
+      if (!e) HIP_TRY(hipEventCreate(&e));
+    std::memcpy(&p.a, a, sizeof p.a);
+    std::memcpy(&p.b, b, sizeof p.b);
+    const int32_t cells = a->bins * b->bins;
+    std::vector<long long> h((size_t)XT_CELLS + (size_t)cells, 0);
+    h[XT_MIN_A] = h[XT_MIN_B] = INT64_MAX;
+    h[XT_MAX_A] = h[XT_MAX_B] = INT64_MIN;
+    if ((rc = d_xt.ensure(h.size()))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_xt.p, h.data(), h.size() * sizeof(long long), hipMemcpyHostToDevice, stream));
+    p.ch_slot = d_ch_slot.p;
+    p.hist_off = d_hist.p;
+    p.hist_pre = d_hist_pre.p;
+    p.staged = p.s.n_nodes * p.s.rw <= kCensusStageWords ? 1 : 0;
+    p.out = d_xt.p;
+    const int64_t tiles = p.s.tile_hi - p.s.tile_lo;
+    const bool reads_records = a->field != SEL_TICK || b->field != SEL_TICK;
+    const int32_t blocks = sample_grid(tiles, crosstab_lds_bytes(cells, p.staged && reads_records));
+    HIP_TRY(hipEventRecord(xt_ev[0], stream));
+    if (tiles > 0) {
+      const int e = launch_crosstab(p, blocks, stream);
+      if (e) return set_err(CL_E_DEVICE, "crosstab kernel: %s", hipGetErrorString((hipError_t)e));
+    }
+    HIP_TRY(hipEventRecord(xt_ev[1], stream));
+    xt_timed = true;
+    HIP_TRY(hipMemcpyAsync(out, d_xt.p, h.size() * sizeof(long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return CL_OK;
+  }
+
   // ---- instance sets (cl_iset) -------------------------------------------------------------------
   int64_t iset_words() const { return stride / kWave; }
 
@@ -2316,6 +2360,7 @@ int cl_device_bytes(const cl_sim* sim, int64_t* bytes) {
   b += sim->d_seeds.n * 8 + sim->d_dg_flag.n * 8;  // (the seed list and the device generator's flagged rows)
   for (const cl_iset* s : sim->isets) b += s->bits.n * 8;  // (the instance sets alive, and their list upload)
   b += sim->d_is_list.n * 8 + sim->d_is_count.n * 8;
+  b += sim->d_xt.n * 8;  // (the crosstab's result words, once a crosstab has run)
   *bytes = b;
   return CL_OK;
 }
@@ -2690,6 +2735,66 @@ int cl_select_instances_in(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t in
                            int64_t cap, cl_select_info* info) {
   SIM_CHECK(sim);
   return select_call(sim, sid, inst_lo, inst_hi, true, in, clauses, n_clauses, insts, ticks, cap, info, nullptr);
+}
+
+static_assert(sizeof(cl_crosstab_axis) == sizeof(CrosstabAxis) && sizeof(CrosstabAxis) == 32,
+              "cl_crosstab_axis mirrors CrosstabAxis");
+static_assert(CL_CROSSTAB_MAX_BINS == kXtMaxBins && CL_CROSSTAB_MAX_CELLS == kXtMaxCells && CL_XT_SUM_A == XT_SUM_A &&
+                  CL_XT_MIN_A == XT_MIN_A && CL_XT_MAX_A == XT_MAX_A && CL_XT_CELLS == XT_CELLS,
+              "CL_CROSSTAB_* and CL_XT_* mirror cl_engine.h");
+
+static int crosstab_axis_ok(const cl_sim* sim, const cl_crosstab_axis* z, const char* name) {
+  if (!z) return set_err(CL_E_INVALID, "crosstab: null axis %s", name);
+  // (CL_SEL_KEY is a select field only: a hash is not binnable)
+  if (z->field < CL_SEL_TICK || z->field > CL_SEL_CH_TOK)
+    return set_err(CL_E_INVALID, "crosstab axis %s: field %d is not one of CL_SEL_TICK .. CL_SEL_CH_TOK", name, z->field);
+  const int64_t N = (int64_t)sim->ids.size(), Cn = (int64_t)sim->links.size();
+  const int64_t bound = z->field == CL_SEL_NODE ? N : z->field == CL_SEL_CH_MSGS || z->field == CL_SEL_CH_TOK ? Cn : 1;
+  if (z->index < 0 || z->index >= bound) return set_err(CL_E_INVALID, "crosstab axis %s: index %d out of range", name, z->index);
+  if (z->bins < 1 || z->bins > CL_CROSSTAB_MAX_BINS || z->width < 1)
+    return set_err(CL_E_INVALID, "crosstab axis %s: 1 <= bins <= %d, width >= 1", name, CL_CROSSTAB_MAX_BINS);
+  return CL_OK;
+}
+
+// cl_snapshot_crosstab, and cl_snapshot_crosstab_in with its set (`conditional`).
+static int crosstab_call(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, bool conditional, const cl_iset* in,
+                         const cl_crosstab_axis* a, const cl_crosstab_axis* b, int64_t* out, int64_t out_words) {
+  SIM_CHECK(sim);
+  // every argument is checked before any device work
+  int rc = conditional ? iset_arg_ok(sim, in) : CL_OK;
+  if (rc) return rc;
+  if ((rc = crosstab_axis_ok(sim, a, "a")) || (rc = crosstab_axis_ok(sim, b, "b"))) return rc;
+  const int64_t cells = (int64_t)a->bins * (int64_t)b->bins;
+  if (cells > CL_CROSSTAB_MAX_CELLS)
+    return set_err(CL_E_INVALID, "crosstab: %lld cells, bins_a * bins_b <= %d", (long long)cells, CL_CROSSTAB_MAX_CELLS);
+  if (!out) return set_err(CL_E_INVALID, "null output");
+  if ((rc = sample_args_ok(sim, a->sid, inst_lo, inst_hi))) return rc;
+  if (b->sid < 0 || b->sid >= sim->n_sids) return set_err(CL_E_INVALID, "snapshot id out of range");
+  if (out_words < CL_XT_CELLS + cells)
+    return set_err(CL_E_LIMIT, "out_words %lld < %lld words of the crosstab", (long long)out_words,
+                   (long long)(CL_XT_CELLS + cells));
+  return sim->crosstab(inst_lo, inst_hi, a, b, out, const_cast<cl_iset*>(in));
+}
+
+int cl_snapshot_crosstab(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_crosstab_axis* a,
+                         const cl_crosstab_axis* b, int64_t* out, int64_t out_words) {
+  return crosstab_call(sim, inst_lo, inst_hi, false, nullptr, a, b, out, out_words);
+}
+
+int cl_snapshot_crosstab_in(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_iset* in, const cl_crosstab_axis* a,
+                            const cl_crosstab_axis* b, int64_t* out, int64_t out_words) {
+  return crosstab_call(sim, inst_lo, inst_hi, true, in, a, b, out, out_words);
+}
+
+int cl_crosstab_time(cl_sim* sim, double* device_ms) {
+  SIM_CHECK(sim);
+  if (!device_ms) return set_err(CL_E_INVALID, "null output");
+  if (!sim->xt_timed) return set_err(CL_E_STATE, "no crosstab call has run");
+  HIP_TRY(hipStreamSynchronize(sim->stream));
+  float f = 0.f;
+  HIP_TRY(hipEventElapsedTime(&f, sim->xt_ev[0], sim->xt_ev[1]));
+  *device_ms = f;
+  return CL_OK;
 }
 
 // ---- instance sets ------------------------------------------------------------------------------

@@ -53,6 +53,21 @@ def reduce_stats(stats, device):
     return type(stats)(L, t.cpu().numpy())
 
 
+def reduce_crosstab(xt, device):
+    """A rank's SnapshotCrosstab (ChandyLamportSim.snapshot_crosstab of its shard) reduced over all
+    ranks, as reduce_stats: SUM over the counters, sums and cells (wrapping modulo 2**64), MIN and
+    MAX over the extrema.  Every rank must pass the same axes.  Returns a new SnapshotCrosstab;
+    without an initialised group, a copy."""
+    t = torch.from_numpy(xt.raw.copy()).to(device)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        for lo, hi, op in ((0, 8, dist.ReduceOp.SUM), (8, 10, dist.ReduceOp.MIN), (10, 12, dist.ReduceOp.MAX),
+                           (12, t.numel(), dist.ReduceOp.SUM)):
+            part = t[lo:hi].contiguous()
+            dist.all_reduce(part, op=op)
+            t[lo:hi] = part
+    return type(xt)(tuple(a.copy() for a in xt.axes), t.cpu().numpy())
+
+
 def gather_census(census, first_instance, device):
     """A rank's SnapshotCensus (ChandyLamportSim.snapshot_census of its shard, whose instance 0 is
     global instance `first_instance`) combined over all ranks: one all_gather of the (class

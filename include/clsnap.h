@@ -511,6 +511,70 @@ int cl_select_instances_in(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t in
                            const cl_select_clause* clauses, int32_t n_clauses, int64_t* insts, int32_t* ticks,
                            int64_t cap, cl_select_info* info);
 
+/* ---- joint distribution of two snapshot quantities: how do they move together? ----------------
+ * cl_snapshot_stats gives the marginal distribution of every quantity; this call gives the joint
+ * distribution of two of them: a two-axis contingency table and the five joint moments, reduced on
+ * the GPU in one sample walk (cl_crosstab.hip); only the 12 + bins_a * bins_b result words cross PCIe.
+ *
+ * Axis.  `field` is one of CL_SEL_TICK, CL_SEL_MSGS, CL_SEL_INFLIGHT, CL_SEL_NODE, CL_SEL_CH_MSGS,
+ * CL_SEL_CH_TOK, with the meaning and the `index` rule it has in cl_select_clause (node rank,
+ * channel number, 0 for the others), of snapshot `sid`; CL_SEL_KEY is refused (a hash is not
+ * binnable).  The two axes may name different snapshot ids, the same one, or be identical.
+ * Bin rule per axis:  bin(v) = v < lo ? 0 : min((uint64)(v - lo) / width, bins - 1)  -- the first and
+ * the last bin take everything below and above; the subtraction happens only when v >= lo, so it
+ * is exact for every int64 lo.  width >= 1, 1 <= bins <= CL_CROSSTAB_MAX_BINS,
+ * bins_a * bins_b <= CL_CROSSTAB_MAX_CELLS.
+ *
+ * Sample.  The instances of [inst_lo, inst_hi) with status CL_INST_OK in which both a->sid and
+ * b->sid completed (cl_snapshot_crosstab_in: that are also members of `in`).
+ *
+ * out[] (int64 words, out_words >= CL_XT_CELLS + bins_a * bins_b):
+ *   CL_XT_INSTANCES  hi - lo                      CL_XT_OK      instances of the range with status OK
+ *   CL_XT_SAMPLE     instances in the sample      (the first two count the range, as in every other call)
+ *   CL_XT_SUM_A, CL_XT_SUM_B                      sums of the two values over the sample, exact int64
+ *   CL_XT_SUM_AA, CL_XT_SUM_AB, CL_XT_SUM_BB      sums of a*a, a*b, b*b, accumulated modulo 2^64 (the
+ *                                                 convention of cl_snapshot_stats' sums of squares)
+ *   CL_XT_MIN_A, CL_XT_MIN_B                      minima (INT64_MAX on an empty sample)
+ *   CL_XT_MAX_A, CL_XT_MAX_B                      maxima (INT64_MIN on an empty sample)
+ *   CL_XT_CELLS + ia * bins_b + ib                instances of the sample with bin(a) == ia, bin(b) == ib
+ * Ranks and sub-ranges merge with a wrapping SUM over words [0, 8) and [12, end), a MIN over
+ * [8, 10) and a MAX over [10, 12).  All integer: the result does not depend on the grid, the
+ * record layout or the exec kernel.
+ *
+ * Errors, all found before any device work, `out` untouched:
+ *   CL_E_INVALID  a NULL sim, axis or out; a field outside CL_SEL_TICK .. CL_SEL_CH_TOK; an index out
+ *                 of range for its field; bins outside [1, CL_CROSSTAB_MAX_BINS]; width < 1;
+ *                 bins_a * bins_b > CL_CROSSTAB_MAX_CELLS; the instance range or either sid out of
+ *                 bounds; (_in) a NULL set or a set of another sim
+ *   CL_E_STATE    no event was ever issued
+ *   CL_E_LIMIT    out_words < CL_XT_CELLS + bins_a * bins_b
+ * inst_lo == inst_hi is the empty sample: zero counts, empty MIN / MAX, zero cells.  The flush that
+ * adds no tick, the lock and the wait for a split replay's second half are those of
+ * cl_snapshot_stats.  The scratch (the result words) is allocated on first use and counted by
+ * cl_device_bytes.  cl_crosstab_time: device ms (HIP events) of the latest call's kernel;
+ * CL_E_STATE before any call. */
+#define CL_CROSSTAB_MAX_BINS  4096   /* per axis */
+#define CL_CROSSTAB_MAX_CELLS 4096   /* bins_a * bins_b */
+typedef struct { int32_t sid, field, index, bins; int64_t lo, width; } cl_crosstab_axis;   /* 32 B */
+#define CL_XT_INSTANCES 0
+#define CL_XT_OK        1
+#define CL_XT_SAMPLE    2
+#define CL_XT_SUM_A     3
+#define CL_XT_SUM_B     4
+#define CL_XT_SUM_AA    5
+#define CL_XT_SUM_AB    6
+#define CL_XT_SUM_BB    7
+#define CL_XT_MIN_A     8
+#define CL_XT_MIN_B     9
+#define CL_XT_MAX_A     10
+#define CL_XT_MAX_B     11
+#define CL_XT_CELLS     12   /* cells[ia * bins_b + ib] follow */
+int cl_snapshot_crosstab(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_crosstab_axis* a,
+                         const cl_crosstab_axis* b, int64_t* out, int64_t out_words);
+int cl_snapshot_crosstab_in(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_iset* in,
+                            const cl_crosstab_axis* a, const cl_crosstab_axis* b, int64_t* out, int64_t out_words);
+int cl_crosstab_time(cl_sim* sim, double* device_ms);
+
 /* ---- device event trace: the reference's debug Logger (logger.go:12-76) ---- */
 /* One LogEvent (logger.go:18-23) per record, in the Logger's order.  Node ranks refer
  * to cl_node_id; `other` is the peer of a Sent/Received record (-1 for Start/End and
