@@ -270,6 +270,12 @@ struct ExecParams {
   // slot -> instance for a replay (nullptr: slot i runs instance i).  cl_host orders a
   // replay's instances by their final tick so the segments of a wave finish together
   const int32_t* inst_map;
+  // The delay rows of a replay through the slot map, packed to nibbles (8 delays per word) and
+  // block-major by launch slot: word w of slot r at ((r / 64) * (sched_row / 8) + w) * 64 +
+  // r % 64, so a wave of the instance-per-lane kernel reads word w of its 64 rows as one 256-byte
+  // access and copies it to its LDS column as it is (cl_rowpack.hip packs them once per plan and
+  // schedule; nullptr: the byte rows of `sched`)
+  const uint32_t* sched_pk;
   // event trace of instances [trace_lo, trace_lo + trace_n) (trace kernel build only)
   TraceRec* trace;          // [trace_n][trace_cap]
   uint32_t* trace_cnt;      // [trace_n] records emitted (may exceed trace_cap: overflow)
@@ -353,6 +359,14 @@ int launch_exec(const ExecParams& p, const uint32_t* topo, const Op* ops, const 
 bool lanes_fit(const ExecParams& p);
 int64_t debug_knob(const char* name, int64_t def);  // (A/B knobs of dbg builds; def in the product)
 int launch_lanes(const ExecParams& p, const uint32_t* topo, const Op* ops, const uint8_t* sched, const ExecLaunch& L);
+// ExecParams::sched_pk from the byte rows and the slot map (cl_rowpack.hip): words of the
+// plane (its blocks reach the last wave of a launch that starts at any slot below n_inst), and
+// the packing kernel on `stream`.
+inline size_t row_pack_words(int64_t n_inst, int64_t sched_row) {
+  return (size_t)((n_inst + 63) / 64 + 1) * 64 * (size_t)(sched_row / 8);
+}
+int launch_row_pack(const uint8_t* sched, int64_t sched_row, const int32_t* inst_map, int64_t n_inst, uint32_t* out,
+                    void* stream);
 const char* lanes_error();
 void lanes_jit_stats(double* compile_ms, int64_t* compiles);
 }  // namespace clsnap

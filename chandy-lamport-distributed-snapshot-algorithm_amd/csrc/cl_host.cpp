@@ -485,6 +485,12 @@ struct cl_sim {
   std::vector<int32_t> plan_inv, h_rec_slot;
   int64_t plan_gen = 0, rec_slot_gen = -1;
   DevBuf<int32_t> d_rec_slot;
+  // The plan's delay rows packed for the instance-per-lane kernel (ExecParams::sched_pk,
+  // cl_rowpack.hip): made at the first replay through the slot map, valid for the plan (plan_gen)
+  // and the rows on the device (sched_gen: every write of d_sched advances it) it was packed
+  // from; a replay that finds another plan or other rows packs again.
+  DevBuf<uint32_t> d_sched_pk;
+  int64_t sched_gen = 0, pk_plan_gen = -1, pk_sched_gen = -1;
   DevBuf<int32_t> d_hist;
   DevBuf<unsigned long long> d_sums;
   // device event trace (cl_trace_enable): instances [trace_lo, trace_lo + trace_n)
@@ -548,7 +554,7 @@ struct cl_sim {
       (void)hipStreamSynchronize(stream);
       d_ops.release(); d_topo.release(); d_sched.release(); d_state.release(); d_regs.release();
       d_snap_nod.release(); d_ch_slot.release(); d_snap_tick.release(); d_ovf.release(); d_fin_tok.release();
-      d_ovh.release(); d_spill_inst.release(); d_map.release(); d_rec_slot.release(); d_hist.release();
+      d_ovh.release(); d_spill_inst.release(); d_map.release(); d_rec_slot.release(); d_sched_pk.release(); d_hist.release();
       d_sums.release();
       d_trace.release(); d_trace_cnt.release(); d_ch_dest.release();
       d_pk_tok.release(); d_pk_done.release(); d_pk_msg.release(); d_pk_cnt.release(); d_pk_bsum.release();
@@ -717,6 +723,7 @@ struct cl_sim {
     int rc;
     HIP_TRY(hipStreamSynchronize(stream));  // (an async launch may read d_sched)
     dev_draws = -1;                         // (the rows on the device are about to be overwritten)
+    sched_gen += 1;
     if ((rc = d_sched.ensure((size_t)(D * n_inst)))) return rc;
     if ((rc = d_dg_flag.ensure(1 + (size_t)gorand::kDelayGenFlagCap))) return rc;
     if (seed_list && !seeds_on_dev) {
@@ -765,6 +772,7 @@ struct cl_sim {
         if (dev_ready) HIP_TRY(hipStreamSynchronize(stream));  // (an async launch may read d_sched)
         if ((rc = d_sched.ensure(sched.size()))) return rc;
         HIP_TRY(hipMemcpy(d_sched.p, sched.data(), sched.size(), hipMemcpyHostToDevice));
+        sched_gen += 1;
         dg_device_ms = 0;
         dg_host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         dg_patched = 0;
@@ -785,6 +793,7 @@ struct cl_sim {
     int rc = d_sched.ensure(padded.size());
     if (rc) return rc;
     HIP_TRY(hipMemcpy(d_sched.p, padded.data(), padded.size(), hipMemcpyHostToDevice));
+    sched_gen += 1;
     dev_draws = user_draws;
     dev_row = row;
     plan_ops = plan_tried = -1;
@@ -1044,6 +1053,33 @@ struct cl_sim {
       p.nospill = plan_nospill ? 1 : 0;
       p.split_slot = plan_split;
     }
+    // the instance-per-lane kernel, compiled for this topology, wherever it fits (N <= 16, every
+    // degree <= 4) and the batch fills the chip with one instance per lane (AUTO); the
+    // node-parallel kernel otherwise, or when run-time compilation failed
+    const bool lanes = engine != CL_ENGINE_NODES && lanes_fit(p) &&
+                       (engine == CL_ENGINE_LANES ||
+                        (!lanes_unavailable && (int64_t)n_inst >= kLanesAutoMinInstances &&
+                         std::max(max_out, max_in) >= 2));
+    if (engine == CL_ENGINE_LANES && !lanes)
+      return set_err(CL_E_LIMIT, "the instance-per-lane kernel needs <= %d nodes, degrees <= %d, <= 16 snapshots",
+                     kLanesMaxNodes, kLanesMaxDegree);
+    // a lanes replay through the slot map reads its delay rows from the plan's packed copy
+    // (CLSNAP_ROW_PACK=0 in a dbg build: the byte rows, for A/Bs)
+    if (lanes && planned && p.inst_map && debug_knob("CLSNAP_ROW_PACK", 1)) {
+      if (pk_plan_gen != plan_gen || pk_sched_gen != sched_gen) {
+        // (an earlier replay's halves may still read the plane; stream2's half of the coming one
+        // does not wait for `stream`, so the packing is finished before it is launched)
+        if ((rc = join_stream2())) return rc;
+        HIP_TRY(hipStreamSynchronize(stream));
+        if ((rc = d_sched_pk.ensure(row_pack_words(n_inst, dev_row)))) return rc;
+        const int pe = launch_row_pack(d_sched.p, dev_row, d_map.p, n_inst, d_sched_pk.p, stream);
+        if (pe != 0) return set_err(CL_E_DEVICE, "row pack launch failed: %s", hipGetErrorString((hipError_t)pe));
+        HIP_TRY(hipStreamSynchronize(stream));
+        pk_plan_gen = plan_gen;
+        pk_sched_gen = sched_gen;
+      }
+      p.sched_pk = d_sched_pk.p;
+    }
     // the first fresh full run of a program is the probe: per-instance spill flags (cleared
     // once per program, not per replay) and final ticks
     probe = begin == 0 && trace_n == 0 && !planned && plan_tried != (int64_t)ops.size();
@@ -1082,16 +1118,6 @@ struct cl_sim {
     // 1.6146-1.6151 / 1.6104-1.6113 ms, gpurun_out/r05z)
     const ExecLaunch el{stream, pr.start, pr.stop, stream2, ev_fork, ev_join, (!pipe || s_dirty) ? 1 : 0,
                         pipe ? 0 : 1, pr.stop2, &pr.stop2_used, pr.start2};
-    // the instance-per-lane kernel, compiled for this topology, wherever it fits (N <= 16, every
-    // degree <= 4) and the batch fills the chip with one instance per lane (AUTO); the
-    // node-parallel kernel otherwise, or when run-time compilation failed
-    const bool lanes = engine != CL_ENGINE_NODES && lanes_fit(p) &&
-                       (engine == CL_ENGINE_LANES ||
-                        (!lanes_unavailable && (int64_t)n_inst >= kLanesAutoMinInstances &&
-                         std::max(max_out, max_in) >= 2));
-    if (engine == CL_ENGINE_LANES && !lanes)
-      return set_err(CL_E_LIMIT, "the instance-per-lane kernel needs <= %d nodes, degrees <= %d, <= 16 snapshots",
-                     kLanesMaxNodes, kLanesMaxDegree);
     // a replay through the slot map with no state image (so the next launch starts from the
     // initial state again) writes its records block-major by slot: a wave's stores of one
     // node's records are contiguous (both kernels; C3 2^20 1.636 -> 1.567 ms per replay on the
@@ -2352,7 +2378,7 @@ int cl_delay_draws_needed(const cl_sim* sim, int64_t* draws) {
 int cl_device_bytes(const cl_sim* sim, int64_t* bytes) {
   SIM_CHECK(sim);
   int64_t b = 0;
-  b += sim->d_ops.n * sizeof(Op) + sim->d_topo.n * 4 + sim->d_sched.n + sim->d_state.n * 4 + sim->d_regs.n * 4;
+  b += sim->d_ops.n * sizeof(Op) + sim->d_topo.n * 4 + sim->d_sched.n + sim->d_sched_pk.n * 4 + sim->d_state.n * 4 + sim->d_regs.n * 4;
   b += sim->d_snap_nod.n * 4 + sim->d_snap_tick.n * 4 + sim->d_ovf.n * 4;
   b += sim->d_ovh.n * 4 + sim->d_hist.n * 4 + sim->d_sums.n * 8 + sim->d_fin_tok.n * 4;
   b += sim->d_sel_bits.n * 8 + sim->d_sel_info.n * 8 + sim->d_sel_bsum.n * 8 + sim->d_sel_out.n * 8 +

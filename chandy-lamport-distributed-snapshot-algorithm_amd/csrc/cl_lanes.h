@@ -171,6 +171,60 @@ __device__ __forceinline__ V opaque(V v) {
   return v;
 }
 
+// Diagnostic build (dbg library, CLSNAP_TIMELINE=1; never the product): where a wave's shader
+// clock cycles go, by segment of program().  mark(k) adds the cycles since the previous stamp
+// to segment k (s_memtime: a scalar read, the same value for the whole wave); drain() waits for
+// every vector memory operation the wave has in flight -- stores included, they share vmcnt
+// with loads -- so the segment marked after it is the time the wave would spend parked at its
+// next use of a loaded value (after a tick loop: the reloads of the registers spilled around
+// it, which queue behind the loop's record stores).  Lane 0 adds the wave's segments to
+// clsnap_lanes_tl[kernel][block & 63] (64 copies: no contended word), read and summed by
+// cl_lanes_timeline_read (cl_jit.cpp).
+enum { TL_ROW, TL_PRO, TL_OPS, TL_LOOP, TL_WAIT, TL_EPI, TL_WAVES, TL_LOOPS, TL_NUM };
+#if defined(CLSNAP_TIMELINE)
+extern "C" {
+__device__ unsigned long long clsnap_lanes_tl[2][64][TL_NUM];
+}
+struct Timeline {
+  uint64_t last;
+  uint32_t seg[TL_NUM];
+  __device__ __forceinline__ static uint64_t now() {
+    __builtin_amdgcn_sched_barrier(0);
+    const uint64_t t = __builtin_amdgcn_s_memtime();
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+  }
+  __device__ __forceinline__ void begin() {
+#pragma unroll
+    for (int k = 0; k < TL_NUM; ++k) seg[k] = 0;
+    seg[TL_WAVES] = 1;
+    last = now();
+  }
+  __device__ __forceinline__ void mark(int k) {
+    const uint64_t t = now();
+    seg[k] += (uint32_t)(t - last);
+    last = t;
+  }
+  __device__ __forceinline__ void count(int k) { seg[k] += 1; }
+  __device__ __forceinline__ void drain() { __builtin_amdgcn_s_waitcnt(0x0f70); }  // vmcnt(0)
+  __device__ __forceinline__ void flush(int kernel) {
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int k = 0; k < TL_NUM; ++k)
+        atomicAdd(&clsnap_lanes_tl[kernel][blockIdx.x & 63u][k], (unsigned long long)seg[k]);
+    }
+  }
+};
+#else
+struct Timeline {
+  __device__ __forceinline__ void begin() {}
+  __device__ __forceinline__ void mark(int) {}
+  __device__ __forceinline__ void count(int) {}
+  __device__ __forceinline__ void drain() {}
+  __device__ __forceinline__ void flush(int) {}
+};
+#endif
+
 // Compile-time loop: f(IC<I>) for I in [B, E).
 template <int I>
 struct IC {
@@ -692,18 +746,48 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
               opaque((int32_t)(p.draws < 0x7fffffffLL ? p.draws : 0x7fffffffLL)),
               opaque(Lds<T>::DB + nd - 1)};
 
+  Timeline tl;
+  tl.begin();
   // The instance's delay row, packed to nibbles (delays are < maxDelay = 5), in the column.
-  if (valid) {
+  // Its 16-byte chunks are loaded kRowGroup at a time, every load of a group issued before
+  // the first is used: one memory round trip per group instead of one per chunk (through the
+  // slot map a wave's 64 rows are 64 scattered lines).  A group's chunks past the row's end
+  // repeat its last chunk -- the same bytes packed into the same column words again.
+  // A replay through the slot map has the rows packed already and block-major by slot
+  // (ExecParams::sched_pk, cl_rowpack.hip): word w of the wave's rows is one contiguous access
+  // that does not wait for the slot map's load, copied to the column as it is -- 16 words in
+  // flight at a time.  (Lanes past the batch load nothing: the plane ends with the batch's
+  // last block, and a split's second half starts mid-block.)
+  if (valid && p.sched_pk) {
+    constexpr uint32_t kWordGroup = 16;
+    const uint32_t* pk = p.sched_pk + ((size_t)(slot >> 6) * nd * 64u + (slot & 63u));
+    for (uint32_t g = 0; g < nd; g += kWordGroup) {
+      uint32_t b[kWordGroup];
+#pragma unroll
+      for (uint32_t j = 0; j < kWordGroup; ++j) b[j] = pk[(size_t)min(g + j, nd - 1) * 64u];
+#pragma unroll
+      for (uint32_t j = 0; j < kWordGroup; ++j) col_wr(x, Lds<T>::DB + min(g + j, nd - 1), b[j]);
+    }
+  } else if (valid) {
     const uint4* row = reinterpret_cast<const uint4*>(sched + (size_t)inst * p.sched_row);
-    for (uint32_t q = 0; q < nd / 2; ++q) {
-      const uint4 b = row[q];
-      auto nib = [](uint32_t w) {
-        return (w & 0xfu) | ((w >> 4) & 0xf0u) | ((w >> 8) & 0xf00u) | ((w >> 12) & 0xf000u);
-      };
-      col_wr(x, Lds<T>::DB + 2 * q, nib(b.x) | (nib(b.y) << 16));
-      col_wr(x, Lds<T>::DB + 2 * q + 1, nib(b.z) | (nib(b.w) << 16));
+    constexpr uint32_t kRowGroup = 8;
+    const uint32_t nq = nd / 2;  // (>= 1: the host pads a row to a multiple of 16 bytes)
+    auto nib = [](uint32_t w) {
+      return (w & 0xfu) | ((w >> 4) & 0xf0u) | ((w >> 8) & 0xf00u) | ((w >> 12) & 0xf000u);
+    };
+    for (uint32_t g = 0; g < nq; g += kRowGroup) {
+      uint4 b[kRowGroup];
+#pragma unroll
+      for (uint32_t j = 0; j < kRowGroup; ++j) b[j] = row[min(g + j, nq - 1)];
+#pragma unroll
+      for (uint32_t j = 0; j < kRowGroup; ++j) {
+        const uint32_t q = min(g + j, nq - 1);
+        col_wr(x, Lds<T>::DB + 2 * q, nib(b[j].x) | (nib(b[j].y) << 16));
+        col_wr(x, Lds<T>::DB + 2 * q + 1, nib(b[j].z) | (nib(b[j].w) << 16));
+      }
     }
   }
+  tl.mark(TL_ROW);
 
   State<T> s;
   s.flag = 0;
@@ -774,6 +858,7 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
   }
   s.alive = valid && s.status == ST_OK;
   int32_t n_started = p.n_started_before;
+  tl.mark(TL_PRO);
 
   // the program through the constant address space: scalar loads, so every op field is a
   // uniform SGPR value (a vector load would make the node dispatch divergent)
@@ -781,16 +866,12 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
   COp* cops = (COp*)ops;
   for (int32_t i = p.op_begin; i < p.op_end; ++i) {
     const Op op = cops[i];
-    if (op.kind == OP_SEND) {
-      send_one<T, SPILL>(x, s, op);
-    } else if (op.kind == OP_SENDS) {
-      // a group of sends from distinct senders: one by one is the same program (cl_engine.h)
-      for (int32_t q = 1; q <= op.a; ++q) send_one<T, SPILL>(x, s, (Op)cops[i + q]);
-      i += op.a;
-    } else if (op.kind == OP_SNAP) {
-      start_snapshot<T, SPILL>(x, s, op);
-      n_started++;
-    } else if (op.kind == OP_TICK || op.kind == OP_DRAIN) {
+    // The tick ops first, leaving through `continue`: as the last arm of the chain below, the
+    // tick loop's exit joined the other arms' paths into the next op, and the compiler kept the
+    // state's registers of those paths alive across the loop -- 14 VGPRs stored to scratch
+    // before every tick loop and loaded again (unused on this path) after it, behind the loop's
+    // record stores.  This way the spill-free kernel has no scratch (C3: 168 -> 154 VGPRs).
+    if (op.kind == OP_TICK || op.kind == OP_DRAIN) {
       // TICK: op.a ticks.  DRAIN: tick until every started snapshot completed (at most op.a
       // ticks, else HANG), then op.b more (test_common.go:123-137).  Per lane: a lane ticks
       // while iter < until (cl_kernels.hip exec_wave).
@@ -798,6 +879,7 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
       constexpr int32_t kNoUntil = 0x7fffffff;
       int32_t until = drain ? kNoUntil : op.a;
       bool anyw = drain;
+      tl.mark(TL_OPS);
       for (int32_t iter = 0;; ++iter) {
         if (anyw) {
           const bool w = until == kNoUntil;
@@ -829,11 +911,27 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
           }
         }
       }
+      tl.mark(TL_LOOP);
+      tl.drain();
+      tl.mark(TL_WAIT);
+      tl.count(TL_LOOPS);
+      continue;
+    }
+    if (op.kind == OP_SEND) {
+      send_one<T, SPILL>(x, s, op);
+    } else if (op.kind == OP_SENDS) {
+      // a group of sends from distinct senders: one by one is the same program (cl_engine.h)
+      for (int32_t q = 1; q <= op.a; ++q) send_one<T, SPILL>(x, s, (Op)cops[i + q]);
+      i += op.a;
+    } else if (op.kind == OP_SNAP) {
+      start_snapshot<T, SPILL>(x, s, op);
+      n_started++;
     }
   }
+  tl.mark(TL_OPS);
 
   // ---- epilogue: tokens still queued, pop counts, results, state image --------------------
-  if (!valid) return;
+  if (!valid) return;  // (never a wave's lane 0, which reports the wave's timeline)
   const uint32_t cap = 1u << capl;
   int32_t inflight = 0;
   uint32_t ptok = 0, pmk = 0, queued = 0;
@@ -882,6 +980,11 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
   r[R_INFLIGHT_TOK] = inflight;
 #pragma unroll
   for (int v = 0; v < N; ++v) p.fin_tok[inst * (uint32_t)N + v] = s.tok[v];
+  // (the timeline build's epilogue is the results' stores, drained; not the state image, which
+  // replays do not save)
+  tl.drain();
+  tl.mark(TL_EPI);
+  tl.flush(SPILL ? 1 : 0);
   if (!p.save_state) return;
   // the node-parallel state image (peek and push counts as node 0's, the others 0)
   uint32_t* S = p.state + inst;
