@@ -31,51 +31,12 @@
 
 #include "../../include/clgraph.h"
 #include "cg_engine.h"
+#include "cl_dev.h"
 #include "cl_text.h"
 
 using namespace clsnap;
 
 namespace {
-
-int gerr(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  const int rc = set_error_v(code, fmt, ap);
-  va_end(ap);
-  return rc;
-}
-
-#define GHIP(expr)                                                                      \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess) return gerr(CL_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
-template <class T>
-struct GBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  int ensure(size_t count) {
-    if (count == 0) count = 1;
-    if (count <= n && p) return CL_OK;
-    release();
-    GHIP(hipMalloc((void**)&p, count * sizeof(T)));
-    n = count;
-    return CL_OK;
-  }
-  int upload(const std::vector<T>& v) {
-    int rc = ensure(v.size());
-    if (rc) return rc;
-    if (!v.empty()) GHIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return CL_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  size_t bytes() const { return n * sizeof(T); }
-};
 
 // P_HOST: n consecutive host events (gops, in order); P_TICK: n ticks; P_DRAIN: a = snapshots
 // started before the drain.
@@ -153,69 +114,71 @@ struct cl_graph {
   size_t ev_used = 0;
   double run_ms = 0;
   int64_t runs = 0, run_ticks = 0, pending_ticks = 0;
-  // phases of the latest run (cl_graph_phase_time): start, first drain, end
-  hipEvent_t ph_ev[3] = {nullptr, nullptr, nullptr};
+  // timing only: no cache writeback per record
+  template <int N>
+  using Timer = DevTimer<N, hipEventDisableSystemFence>;
+  // phases of the latest run (cl_graph_phase_time): start, first drain, end; done: a run has begun
+  Timer<3> ph;
   bool ph_drain = false, ph_fresh = false;
   int64_t ph_time[3] = {0, 0, 0};
 
   GParams P{};
   int32_t s_cap = 0, hist = 0, alloc_cap_log2 = -1;
   int64_t sched_len = 0;
-  GBuf<int32_t> d_out_off, d_in_off, d_in_src, d_init_tok;
-  GBuf<int2> d_route;
-  GBuf<int32_t> d_tokens, d_ltrig, d_lsend, d_crn, d_mcnt;
-  GBuf<int2> d_pp;
-  GBuf<MDel> d_mlist;
-  GBuf<uint32_t> d_tokcnt;
-  GBuf<uint8_t> d_in_oj;
-  GBuf<BigX> d_big;
-  GBuf<unsigned long long> d_cpart;
-  GBuf<uint64_t> d_cre;
-  GBuf<long long> d_bsum;
-  GBuf<uint32_t> d_histv;
-  GBuf<uint64_t> d_hq;
-  GBuf<uint64_t> d_fifo, d_rec;
-  GBuf<SNode> d_sn;
-  GBuf<int32_t> d_done, d_ctick;
-  GBuf<GScal> d_sc;
-  GBuf<GOp> d_ops;
-  GBuf<uint8_t> d_sched;
-  GBuf<unsigned long long> d_scratch;
+  DevBuf<int32_t> d_out_off, d_in_off, d_in_src, d_init_tok;
+  DevBuf<int2> d_route;
+  DevBuf<int32_t> d_tokens, d_ltrig, d_lsend, d_crn, d_mcnt;
+  DevBuf<int2> d_pp;
+  DevBuf<MDel> d_mlist;
+  DevBuf<uint32_t> d_tokcnt;
+  DevBuf<uint8_t> d_in_oj;
+  DevBuf<BigX> d_big;
+  DevBuf<unsigned long long> d_cpart;
+  DevBuf<uint64_t> d_cre;
+  DevBuf<long long> d_bsum;
+  DevBuf<uint32_t> d_histv;
+  DevBuf<uint64_t> d_hq;
+  DevBuf<uint64_t> d_fifo, d_rec;
+  DevBuf<SNode> d_sn;
+  DevBuf<int32_t> d_done, d_ctick;
+  DevBuf<GScal> d_sc;
+  DevBuf<GOp> d_ops;
+  DevBuf<uint8_t> d_sched;
+  DevBuf<unsigned long long> d_scratch;
   // per-snapshot summary table (cl_graph_snapshot_table): channel of every in-position, the
   // device rows, the events around the latest call's kernels
-  GBuf<int32_t> d_in_ch;
-  GBuf<long long> d_table;
-  hipEvent_t tb_ev[2] = {nullptr, nullptr};
-  bool tb_timed = false;
+  DevBuf<int32_t> d_in_ch;
+  DevBuf<long long> d_table;
+  Timer<2> tb;
   int32_t n_cus = 0;
   // sparse packed collect (cl_graph_collect_sparse): per-(sid, tile) offsets, per-sid totals,
   // the head the host reads between scan and write (row_offsets, message offsets, complete),
-  // the packed outputs, and the events around the scan ([0], [1]) and the write ([2], [3])
-  GBuf<ulonglong2> d_sp_tiles, d_sp_rows;
-  GBuf<long long> d_sp_head;
-  GBuf<int32_t> d_sp_chan, d_sp_cnt, d_sp_msg, d_sp_tok;
-  hipEvent_t sp_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool sp_timed = false, sp_wrote = false;
+  // the packed outputs, and the events around the scan ([0], [1]) and the write ([2], [3]);
+  // done: the pairs of the latest call that completed
+  DevBuf<ulonglong2> d_sp_tiles, d_sp_rows;
+  DevBuf<long long> d_sp_head;
+  DevBuf<int32_t> d_sp_chan, d_sp_cnt, d_sp_msg, d_sp_tok;
+  Timer<4> sp;
   size_t ops_uploaded = 0;
   // device event trace (cl_graph_trace_enable)
   int32_t trace_cap = 0;
-  GBuf<GTraceRec> d_trace;
-  GBuf<uint32_t> d_trace_cnt;
+  DevBuf<GTraceRec> d_trace;
+  DevBuf<uint32_t> d_trace_cnt;
   // graph-partitioned mode (cl_graph_part_begin)
   bool part = false;
   int32_t part_lo = 0, part_hi = 0;
-  GBuf<PDel> d_outbox, d_inbox;
-  GBuf<uint32_t> d_out_n;
-  GBuf<MDel> d_rmlist;
-  GBuf<int2> d_reports, d_rep_in;
-  GBuf<int32_t> d_trigv, d_s0;
-  GBuf<unsigned long long> d_rdraw, d_draw0;
-  GBuf<long long> d_replies;
-  GBuf<GOp> d_pop;
+  DevBuf<PDel> d_outbox, d_inbox;
+  DevBuf<uint32_t> d_out_n;
+  DevBuf<MDel> d_rmlist;
+  DevBuf<int2> d_reports, d_rep_in;
+  DevBuf<int32_t> d_trigv, d_s0;
+  DevBuf<unsigned long long> d_rdraw, d_draw0;
+  DevBuf<long long> d_replies;
+  DevBuf<GOp> d_pop;
   // device-resident exchange (cl_graph_part_dev_bind): caller-owned buckets and totals
   int32_t bk_world = 0, bk_rank = 0, bk_span = 0, bk_cap = 0;
   void *bk_send = nullptr, *bk_recv = nullptr, *tot_send = nullptr, *tot_recv = nullptr;
-  GBuf<uint32_t> d_bk_cnt;
+  DevBuf<uint32_t> d_bk_cnt;
 
   ~cl_graph() {
     if (!dev_ready) return;
@@ -224,31 +187,10 @@ struct cl_graph {
     // the engine's own, which may hold work issued before the switch
     (void)hipStreamSynchronize(stream);
     if (own_stream != stream) (void)hipStreamSynchronize(own_stream);
-    GBuf<int32_t>* i32s[] = {&d_out_off, &d_in_off, &d_in_src, &d_init_tok, &d_tokens,
-                             &d_ltrig,  &d_lsend,    &d_crn,    &d_mcnt,
-                             &d_done,    &d_ctick};
-    for (auto* b : i32s) b->release();
-    d_cre.release(); d_bsum.release(); d_hq.release(); d_histv.release(); d_mlist.release(); d_route.release();
-    d_tokcnt.release(); d_pp.release(); d_in_oj.release(); d_fifo.release(); d_sn.release(); d_rec.release(); d_sc.release(); d_ops.release();
-    d_sched.release(); d_scratch.release(); d_big.release(); d_cpart.release();
-    d_trace.release(); d_trace_cnt.release();
-    d_outbox.release(); d_inbox.release(); d_out_n.release(); d_rmlist.release(); d_reports.release();
-    d_rep_in.release(); d_trigv.release(); d_s0.release(); d_rdraw.release(); d_draw0.release();
-    d_replies.release(); d_pop.release(); d_bk_cnt.release();
-    d_in_ch.release(); d_table.release();
-    d_sp_tiles.release(); d_sp_rows.release(); d_sp_head.release();
-    d_sp_chan.release(); d_sp_cnt.release(); d_sp_msg.release(); d_sp_tok.release();
-    for (auto& e : tb_ev)
-      if (e) (void)hipEventDestroy(e);
-    for (auto& e : sp_ev)
-      if (e) (void)hipEventDestroy(e);
     for (auto& ev : ev_pool) {
       (void)hipEventDestroy(ev.first);
       (void)hipEventDestroy(ev.second);
     }
-    for (auto& e : ph_ev)
-      if (e) (void)hipEventDestroy(e);
-    (void)hipStreamSynchronize(own_stream);
     (void)hipStreamDestroy(own_stream);
   }
 
@@ -300,7 +242,7 @@ struct cl_graph {
   int build_csr(std::vector<std::pair<int32_t, int32_t>>& ch) {
     std::sort(ch.begin(), ch.end());
     ch.erase(std::unique(ch.begin(), ch.end()), ch.end());
-    if (ch.size() >= (size_t)INT32_MAX) return gerr(CL_E_LIMIT, "too many channels");
+    if (ch.size() >= (size_t)INT32_MAX) return set_err(CL_E_LIMIT, "too many channels");
     e = (int64_t)ch.size();
     out_off.assign(n + 1, 0);
     in_off.assign(n + 1, 0);
@@ -330,7 +272,7 @@ struct cl_graph {
       max_in = std::max(max_in, in_off[v + 1] - in_off[v]);
     }
     if (max_out > kGMaxOutDegree)
-      return gerr(CL_E_LIMIT, "out-degree %d exceeds the graph engine's %d", max_out, kGMaxOutDegree);
+      return set_err(CL_E_LIMIT, "out-degree %d exceeds the graph engine's %d", max_out, kGMaxOutDegree);
     ch_sends.assign(e, 0);
     frozen = true;
     return CL_OK;
@@ -358,27 +300,27 @@ struct cl_graph {
 
   int set_topology(int32_t nn, int32_t width, const int64_t* tokens, int64_t m, const int32_t* src,
                    const int32_t* dst) {
-    if (frozen || !ids.empty()) return gerr(CL_E_STATE, "the topology is already set");
-    if (nn <= 0 || !tokens || (m > 0 && (!src || !dst)) || m < 0) return gerr(CL_E_INVALID, "bad topology arrays");
+    if (frozen || !ids.empty()) return set_err(CL_E_STATE, "the topology is already set");
+    if (nn <= 0 || !tokens || (m > 0 && (!src || !dst)) || m < 0) return set_err(CL_E_INVALID, "bad topology arrays");
     if (width == 0) width = digits(nn - 1);
     if (width < digits(nn - 1) || width > 10)
-      return gerr(CL_E_INVALID, "id width %d cannot keep %d ranks in lexicographic order", width, nn);
+      return set_err(CL_E_INVALID, "id width %d cannot keep %d ranks in lexicographic order", width, nn);
     n = nn;
     bulk = true;
     id_width = width;
     init_tok.resize(n);
     total_tokens = 0;
     for (int32_t r = 0; r < n; ++r) {
-      if (tokens[r] < 0 || tokens[r] > INT32_MAX) return gerr(CL_E_LIMIT, "token count out of range");
+      if (tokens[r] < 0 || tokens[r] > INT32_MAX) return set_err(CL_E_LIMIT, "token count out of range");
       init_tok[r] = (int32_t)tokens[r];
       total_tokens += tokens[r];
     }
-    if (total_tokens > INT32_MAX) return gerr(CL_E_LIMIT, "total tokens exceed int32");
+    if (total_tokens > INT32_MAX) return set_err(CL_E_LIMIT, "total tokens exceed int32");
     std::vector<std::pair<int32_t, int32_t>> ch;
     ch.reserve((size_t)m);
     for (int64_t i = 0; i < m; ++i) {
       if (src[i] < 0 || src[i] >= n || dst[i] < 0 || dst[i] >= n)
-        return gerr(CL_E_UNKNOWN_NODE, "edge %lld references a rank outside [0, %d)", (long long)i, n);
+        return set_err(CL_E_UNKNOWN_NODE, "edge %lld references a rank outside [0, %d)", (long long)i, n);
       if (src[i] != dst[i]) ch.emplace_back(src[i], dst[i]);  // node.go:88-90
     }
     return build_csr(ch);
@@ -386,7 +328,7 @@ struct cl_graph {
 
   // ---- program -------------------------------------------------------------------
   int append_send(int32_t a, int32_t b, int64_t nt) {
-    if (nt < 0 || nt > (int64_t)kGPayload) return gerr(CL_E_LIMIT, "token count %lld out of range", (long long)nt);
+    if (nt < 0 || nt > (int64_t)kGPayload) return set_err(CL_E_LIMIT, "token count %lld out of range", (long long)nt);
     if (nt != 1) nonunit = true;
     if (b >= 0) {
       // out-index lookup only to count per-channel sends (history sizing)
@@ -410,7 +352,7 @@ struct cl_graph {
   }
 
   int append_snap(int32_t a, int32_t* out_sid) {
-    if (n_sids == INT32_MAX) return gerr(CL_E_LIMIT, "too many snapshots");
+    if (n_sids == INT32_MAX) return set_err(CL_E_LIMIT, "too many snapshots");
     const int32_t sid = n_sids++;
     if (out_sid) *out_sid = sid;
     append_host();
@@ -434,15 +376,15 @@ struct cl_graph {
     if (dev_ready) return CL_OK;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-      return gerr(CL_E_DEVICE, "no HIP device available (the engine needs a gfx950 GPU)");
-    if (device < 0 || device >= count) return gerr(CL_E_DEVICE, "device %d out of range (%d)", device, count);
-    GHIP(hipSetDevice(device));
+      return set_err(CL_E_DEVICE, "no HIP device available (the engine needs a gfx950 GPU)");
+    if (device < 0 || device >= count) return set_err(CL_E_DEVICE, "device %d out of range (%d)", device, count);
+    HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
-    GHIP(hipGetDeviceProperties(&prop, device));
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-      return gerr(CL_E_DEVICE, "device %d is %s, the engine is built for gfx950", device, prop.gcnArchName);
+      return set_err(CL_E_DEVICE, "device %d is %s, the engine is built for gfx950", device, prop.gcnArchName);
     n_cus = prop.multiProcessorCount;
-    GHIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     own_stream = stream;
     dev_ready = true;
     int rc;
@@ -491,7 +433,7 @@ struct cl_graph {
     const size_t N = (size_t)n, E = (size_t)std::max<int64_t>(e, 1);
     const size_t NP = (N + kGThreads - 1) / kGThreads;
     if ((uint64_t)s_cap * N >= (1ull << 40) || (uint64_t)s_cap * E >= (1ull << 40))
-      return gerr(CL_E_LIMIT, "snapshot state too large");
+      return set_err(CL_E_LIMIT, "snapshot state too large");
     int rc;
     if ((rc = d_tokens.ensure(N)) || (rc = d_pp.ensure(N)) || (rc = d_ltrig.ensure(N)) ||
         (rc = d_lsend.ensure(N)) || (rc = d_crn.ensure(N)) || (rc = d_mlist.ensure(NP * kGThreads)) ||
@@ -601,18 +543,18 @@ struct cl_graph {
     if (gops.size() == ops_uploaded && d_ops.p) return CL_OK;
     int rc = d_ops.ensure(std::max<size_t>(gops.size(), 64));
     if (rc) return rc;
-    if (!gops.empty()) GHIP(hipMemcpy(d_ops.p, gops.data(), gops.size() * sizeof(GOp), hipMemcpyHostToDevice));
+    if (!gops.empty()) HIP_TRY(hipMemcpy(d_ops.p, gops.data(), gops.size() * sizeof(GOp), hipMemcpyHostToDevice));
     ops_uploaded = gops.size();
     return CL_OK;
   }
 
   int k_err(int e_) {
-    if (e_) return gerr(CL_E_DEVICE, "graph kernel launch failed: %s", hipGetErrorString((hipError_t)e_));
+    if (e_) return set_err(CL_E_DEVICE, "graph kernel launch failed: %s", hipGetErrorString((hipError_t)e_));
     return CL_OK;
   }
 
   int launch_tick() {
-    if (time + 1 > kMaxGraphTime) return gerr(CL_E_LIMIT, "simulated time would exceed %lld ticks", (long long)kMaxGraphTime);
+    if (time + 1 > kMaxGraphTime) return set_err(CL_E_LIMIT, "simulated time would exceed %lld ticks", (long long)kMaxGraphTime);
     ++time;
     ++run_ticks;
     return k_err(cg_launch_tick(P, (int32_t)time, stream));
@@ -654,8 +596,8 @@ struct cl_graph {
 
   int read_status(int32_t* st) {
     GScal sc;
-    GHIP(hipMemcpyAsync(&sc, d_sc.p, sizeof sc, hipMemcpyDeviceToHost, stream));
-    GHIP(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpyAsync(&sc, d_sc.p, sizeof sc, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     *st = sc.status;
     return CL_OK;
   }
@@ -674,8 +616,8 @@ struct cl_graph {
     for (;;) {
       if ((rc = k_err(cg_launch_drain_ticks(P, n_before, max_drain, launched, batch, stream)))) return rc;
       launched += batch;
-      GHIP(hipMemcpyAsync(&sc, d_sc.p, sizeof sc, hipMemcpyDeviceToHost, stream));
-      GHIP(hipStreamSynchronize(stream));
+      HIP_TRY(hipMemcpyAsync(&sc, d_sc.p, sizeof sc, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
       if (sc.status || sc.dphase == kDrainDone || sc.dphase == kDrainHang) break;
       batch = std::min(batch * 2, 256);
     }
@@ -688,14 +630,14 @@ struct cl_graph {
 
   // Execute program ops [executed, end) on the device; from scratch if `fresh`.
   int run(bool fresh) {
-    if (part) return gerr(CL_E_STATE, "a partitioned run advances only through the cl_graph_part_* calls");
+    if (part) return set_err(CL_E_STATE, "a partitioned run advances only through the cl_graph_part_* calls");
     int rc = freeze();
     if (rc) return rc;
-    if (n == 0) return gerr(CL_E_STATE, "the topology has no nodes");
+    if (n == 0) return set_err(CL_E_STATE, "the topology has no nodes");
     if ((rc = ensure_device())) return rc;
-    GHIP(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     // buffers are only replaced between runs: wait for the previous one first
-    if (gops.size() != ops_uploaded || !state_valid) GHIP(hipStreamSynchronize(stream));
+    if (gops.size() != ops_uploaded || !state_valid) HIP_TRY(hipStreamSynchronize(stream));
     bool realloc = false;
     if ((rc = ensure_state(&realloc))) return rc;
     if ((rc = ensure_sched()) || (rc = upload_ops())) return rc;
@@ -705,15 +647,14 @@ struct cl_graph {
     if (!fresh && executed == prog.size()) return CL_OK;
     if (ev_used == ev_pool.size()) {
       std::pair<hipEvent_t, hipEvent_t> pr;
-      GHIP(hipEventCreateWithFlags(&pr.first, hipEventDisableSystemFence));  // timing only: no cache writeback per record
-      GHIP(hipEventCreateWithFlags(&pr.second, hipEventDisableSystemFence));
+      HIP_TRY(hipEventCreateWithFlags(&pr.first, hipEventDisableSystemFence));  // timing only: no cache writeback per record
+      HIP_TRY(hipEventCreateWithFlags(&pr.second, hipEventDisableSystemFence));
       ev_pool.push_back(pr);
     }
     auto& ev = ev_pool[ev_used++];
-    GHIP(hipEventRecord(ev.first, stream));
-    for (auto& e : ph_ev)
-      if (!e) GHIP(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-    GHIP(hipEventRecord(ph_ev[0], stream));
+    HIP_TRY(hipEventRecord(ev.first, stream));
+    if ((rc = ph.mark(0, stream))) return rc;
+    ph.done = 1;
     ph_drain = false;
     ph_fresh = fresh;
     ph_time[0] = fresh ? 0 : time;
@@ -725,7 +666,7 @@ struct cl_graph {
       hang = false;
       if ((rc = k_err(cg_launch_reset(P, d_init_tok.p, stream)))) return rc;
       // a replay from the initial state restarts the log (an incremental run appends)
-      if (trace_cap > 0) GHIP(hipMemsetAsync(d_trace_cnt.p, 0, sizeof(uint32_t), stream));
+      if (trace_cap > 0) HIP_TRY(hipMemsetAsync(d_trace_cnt.p, 0, sizeof(uint32_t), stream));
       if (traffic_steps > 0 && (rc = k_err(cg_launch_sends(P, 0, stream)))) return rc;  // step 0 traffic
     }
     state_valid = false;
@@ -743,7 +684,7 @@ struct cl_graph {
       } else if (op.kind == P_DRAIN) {
         if ((rc = flush_hostops(pend_begin, pend_count))) return rc;
         if (!ph_drain) {  // the first drain of the run: the traffic / drain phase boundary
-          GHIP(hipEventRecord(ph_ev[1], stream));
+          if ((rc = ph.mark(1, stream))) return rc;
           ph_drain = true;
           ph_time[1] = time;
         }
@@ -751,8 +692,8 @@ struct cl_graph {
       }
     }
     if ((rc = flush_hostops(pend_begin, pend_count))) return rc;
-    GHIP(hipEventRecord(ev.second, stream));
-    GHIP(hipEventRecord(ph_ev[2], stream));
+    HIP_TRY(hipEventRecord(ev.second, stream));
+    if ((rc = ph.mark(2, stream))) return rc;
     ph_time[2] = time;
     gop_cursor = pend_begin;
     executed = prog.size();
@@ -764,9 +705,9 @@ struct cl_graph {
   // Counter totals: sum of the per-shard partials (cg_engine.h kParts).
   int counter_totals(uint64_t* out) {
     std::vector<unsigned long long> part((size_t)kParts * kNumCnt);
-    GHIP(hipMemcpyAsync(part.data(), d_cpart.p, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+    HIP_TRY(hipMemcpyAsync(part.data(), d_cpart.p, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                         stream));
-    GHIP(hipStreamSynchronize(stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     for (int c = 0; c < kNumCnt; ++c) out[c] = 0;
     for (int sh = 0; sh < kParts; ++sh)
       for (int c = 0; c < kNumCnt; ++c) out[c] += part[(size_t)sh * kNumCnt + c];
@@ -775,8 +716,8 @@ struct cl_graph {
 
   int sync() {
     if (!dev_ready) return CL_OK;
-    GHIP(hipSetDevice(device));
-    GHIP(hipStreamSynchronize(stream));
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamSynchronize(stream));
     return CL_OK;
   }
 
@@ -793,7 +734,7 @@ struct cl_graph {
     double ms = 0;
     for (size_t i = 0; i < ev_used; ++i) {
       float f = 0.f;
-      GHIP(hipEventElapsedTime(&f, ev_pool[i].first, ev_pool[i].second));
+      HIP_TRY(hipEventElapsedTime(&f, ev_pool[i].first, ev_pool[i].second));
       ms += f;
     }
     ev_used = 0;
@@ -811,11 +752,11 @@ struct cl_graph {
 // ---------------------------------------------------------------------------
 #define G_CHECK(g)                                                     \
   do {                                                                 \
-    if (!(g)) return gerr(CL_E_INVALID, "null cl_graph handle");       \
+    if (!(g)) return set_err(CL_E_INVALID, "null cl_graph handle");       \
   } while (0)
 #define G_TOPO_OPEN(g)                                                                       \
   do {                                                                                       \
-    if ((g)->frozen) return gerr(CL_E_STATE, "topology changes after events are not supported"); \
+    if ((g)->frozen) return set_err(CL_E_STATE, "topology changes after events are not supported"); \
   } while (0)
 
 extern "C" {
@@ -823,7 +764,7 @@ extern "C" {
 uint64_t cl_counter_hash(uint64_t seed, uint64_t a, uint64_t b) { return cg_hash(seed, a, b); }
 
 int cl_graph_create(cl_graph** out) {
-  if (!out) return gerr(CL_E_INVALID, "null output");
+  if (!out) return set_err(CL_E_INVALID, "null output");
   *out = new cl_graph();
   return CL_OK;
 }
@@ -835,7 +776,7 @@ int cl_graph_destroy(cl_graph* g) {
 
 int cl_graph_set_device(cl_graph* g, int32_t device_ordinal) {
   G_CHECK(g);
-  if (g->dev_ready) return gerr(CL_E_STATE, "device already selected");
+  if (g->dev_ready) return set_err(CL_E_STATE, "device already selected");
   g->device = device_ordinal;
   return CL_OK;
 }
@@ -843,11 +784,11 @@ int cl_graph_set_device(cl_graph* g, int32_t device_ordinal) {
 int cl_graph_add_node(cl_graph* g, const char* id, int64_t tokens) {
   G_CHECK(g);
   G_TOPO_OPEN(g);
-  if (g->bulk) return gerr(CL_E_STATE, "bulk topology already set");
-  if (!id) return gerr(CL_E_INVALID, "null id");
-  if (g->id_index.count(id)) return gerr(CL_E_DUPLICATE_NODE, "node %s already exists", id);
-  if (tokens < 0 || tokens > INT32_MAX) return gerr(CL_E_LIMIT, "token count out of range");
-  if (g->total_tokens + tokens > INT32_MAX) return gerr(CL_E_LIMIT, "total tokens exceed int32");
+  if (g->bulk) return set_err(CL_E_STATE, "bulk topology already set");
+  if (!id) return set_err(CL_E_INVALID, "null id");
+  if (g->id_index.count(id)) return set_err(CL_E_DUPLICATE_NODE, "node %s already exists", id);
+  if (tokens < 0 || tokens > INT32_MAX) return set_err(CL_E_LIMIT, "token count out of range");
+  if (g->total_tokens + tokens > INT32_MAX) return set_err(CL_E_LIMIT, "total tokens exceed int32");
   g->total_tokens += tokens;
   g->id_index[id] = (int)g->ids.size();
   g->ids.emplace_back(id);
@@ -858,8 +799,8 @@ int cl_graph_add_node(cl_graph* g, const char* id, int64_t tokens) {
 int cl_graph_add_link(cl_graph* g, const char* src, const char* dest) {
   G_CHECK(g);
   const int a = g->rank_of_id(src), b = g->rank_of_id(dest);
-  if (a < 0) return gerr(CL_E_UNKNOWN_NODE, "Node %s does not exist", src ? src : "(null)");  // sim.go:49-51
-  if (b < 0) return gerr(CL_E_UNKNOWN_NODE, "Node %s does not exist", dest ? dest : "(null)");  // sim.go:52-54
+  if (a < 0) return set_err(CL_E_UNKNOWN_NODE, "Node %s does not exist", src ? src : "(null)");  // sim.go:49-51
+  if (b < 0) return set_err(CL_E_UNKNOWN_NODE, "Node %s does not exist", dest ? dest : "(null)");  // sim.go:52-54
   G_TOPO_OPEN(g);
   if (a != b) g->links.emplace_back(a, b);  // node.go:88-90; duplicates collapse at freeze
   return CL_OK;
@@ -873,7 +814,7 @@ int cl_graph_add_link(cl_graph* g, const char* src, const char* dest) {
 // first error in file order is the one reported, as in a sequential parse.
 int cl_graph_read_topology_text(cl_graph* g, const char* text) {
   G_CHECK(g);
-  if (!text) return gerr(CL_E_INVALID, "null text");
+  if (!text) return set_err(CL_E_INVALID, "null text");
   const std::string_view all(text);
   LineIter it{all};
   std::string_view line, f[3];
@@ -882,7 +823,7 @@ int cl_graph_read_topology_text(cl_graph* g, const char* text) {
   while (it.next(&line)) {
     if (line[0] == '#') continue;
     if (left < 0) {
-      if (!go_atoi_sv(line, &left)) return gerr(CL_E_PARSE, "bad node count line: %.*s", (int)line.size(), line.data());
+      if (!go_atoi_sv(line, &left)) return set_err(CL_E_PARSE, "bad node count line: %.*s", (int)line.size(), line.data());
       if (left == 0) {
         link_start = it.i;
         break;
@@ -890,9 +831,9 @@ int cl_graph_read_topology_text(cl_graph* g, const char* text) {
       continue;
     }
     if (go_fields_sv(line, f, 3) != 2)
-      return gerr(CL_E_PARSE, "Expected 2 tokens in line: %.*s", (int)line.size(), line.data());
+      return set_err(CL_E_PARSE, "Expected 2 tokens in line: %.*s", (int)line.size(), line.data());
     int64_t tok;
-    if (!go_atoi_sv(f[1], &tok)) return gerr(CL_E_PARSE, "bad token count: %.*s", (int)f[1].size(), f[1].data());
+    if (!go_atoi_sv(f[1], &tok)) return set_err(CL_E_PARSE, "bad token count: %.*s", (int)f[1].size(), f[1].data());
     int rc = cl_graph_add_node(g, std::string(f[0]).c_str(), tok);
     if (rc) return rc;
     if (--left == 0) {
@@ -901,7 +842,7 @@ int cl_graph_read_topology_text(cl_graph* g, const char* text) {
     }
   }
   if (link_start >= all.size()) return CL_OK;
-  if (g->frozen) return gerr(CL_E_STATE, "topology changes after events are not supported");
+  if (g->frozen) return set_err(CL_E_STATE, "topology changes after events are not supported");
   // ---- the link section, in parallel ----
   const std::string_view rest = all.substr(link_start);
   const int T = (int)std::max<size_t>(1, std::min<size_t>(std::max(1u, std::thread::hardware_concurrency()),
@@ -950,7 +891,7 @@ int cl_graph_read_topology_text(cl_graph* g, const char* text) {
   for (auto& x : th) x.join();
   for (int t = 0; t < T; ++t) {  // file order: links of earlier chunks, then the first error
     g->links.insert(g->links.end(), parts[t].links.begin(), parts[t].links.end());
-    if (parts[t].err_code) return gerr(parts[t].err_code, "%s", parts[t].err.c_str());
+    if (parts[t].err_code) return set_err(parts[t].err_code, "%s", parts[t].err.c_str());
   }
   return CL_OK;
 }
@@ -958,7 +899,7 @@ int cl_graph_read_topology_text(cl_graph* g, const char* text) {
 int cl_graph_read_topology_file(cl_graph* g, const char* path) {
   G_CHECK(g);
   std::string text;
-  if (!path || !read_file(path, &text)) return gerr(CL_E_IO, "cannot read %s", path ? path : "(null)");
+  if (!path || !read_file(path, &text)) return set_err(CL_E_IO, "cannot read %s", path ? path : "(null)");
   return cl_graph_read_topology_text(g, text.c_str());
 }
 
@@ -970,7 +911,7 @@ int cl_graph_set_topology(cl_graph* g, int32_t n_nodes, int32_t id_width, const 
 
 int cl_graph_generate_regular(cl_graph* g, int32_t n_nodes, int32_t degree, int64_t tokens, uint64_t seed) {
   G_CHECK(g);
-  if (n_nodes <= 0 || degree < 0 || degree > kGMaxOutDegree) return gerr(CL_E_INVALID, "bad regular graph size");
+  if (n_nodes <= 0 || degree < 0 || degree > kGMaxOutDegree) return set_err(CL_E_INVALID, "bad regular graph size");
   const size_t N = (size_t)n_nodes;
   std::vector<int32_t> src(N * degree), dst(N * degree);
   std::vector<std::thread> th;
@@ -996,7 +937,7 @@ int cl_graph_generate_regular(cl_graph* g, int32_t n_nodes, int32_t degree, int6
 int cl_graph_generate_powerlaw(cl_graph* g, int32_t n_nodes, int32_t targets, double exponent, int32_t ring,
                                int64_t tokens, uint64_t seed) {
   G_CHECK(g);
-  if (n_nodes <= 0 || targets < 0 || targets > kGMaxOutDegree - 2) return gerr(CL_E_INVALID, "bad power-law graph size");
+  if (n_nodes <= 0 || targets < 0 || targets > kGMaxOutDegree - 2) return set_err(CL_E_INVALID, "bad power-law graph size");
   const size_t N = (size_t)n_nodes;
   std::vector<double> cdf(N);
   double acc = 0;
@@ -1032,7 +973,7 @@ int cl_graph_generate_powerlaw(cl_graph* g, int32_t n_nodes, int32_t targets, do
 
 int cl_graph_num_nodes(cl_graph* g, int32_t* n) {
   G_CHECK(g);
-  if (!n) return gerr(CL_E_INVALID, "null output");
+  if (!n) return set_err(CL_E_INVALID, "null output");
   int rc = g->freeze();
   if (rc) return rc;
   *n = g->n;
@@ -1041,7 +982,7 @@ int cl_graph_num_nodes(cl_graph* g, int32_t* n) {
 
 int cl_graph_num_channels(cl_graph* g, int64_t* n) {
   G_CHECK(g);
-  if (!n) return gerr(CL_E_INVALID, "null output");
+  if (!n) return set_err(CL_E_INVALID, "null output");
   int rc = g->freeze();
   if (rc) return rc;
   *n = g->e;
@@ -1061,9 +1002,9 @@ int cl_graph_node_id(cl_graph* g, int32_t rank, char* buf, int32_t cap) {
   G_CHECK(g);
   int rc = g->freeze();
   if (rc) return rc;
-  if (rank < 0 || rank >= g->n || !buf || cap <= 0) return gerr(CL_E_INVALID, "bad rank or buffer");
+  if (rank < 0 || rank >= g->n || !buf || cap <= 0) return set_err(CL_E_INVALID, "bad rank or buffer");
   const std::string s = g->node_id(rank);
-  if ((int32_t)s.size() >= cap) return gerr(CL_E_LIMIT, "buffer too small");
+  if ((int32_t)s.size() >= cap) return set_err(CL_E_LIMIT, "buffer too small");
   std::memcpy(buf, s.c_str(), s.size() + 1);
   return CL_OK;
 }
@@ -1073,8 +1014,8 @@ int cl_graph_set_limits(cl_graph* g, int32_t fifo_slots, int32_t max_snapshots, 
   int l = 0;
   while ((1 << l) < fifo_slots) ++l;
   if (fifo_slots < 2 || fifo_slots > 32768 || (1 << l) != fifo_slots)
-    return gerr(CL_E_INVALID, "fifo_slots must be a power of two in [2, 32768]");
-  if (max_snapshots < 0 || max_drain_ticks < 0) return gerr(CL_E_INVALID, "negative limit");
+    return set_err(CL_E_INVALID, "fifo_slots must be a power of two in [2, 32768]");
+  if (max_snapshots < 0 || max_drain_ticks < 0) return set_err(CL_E_INVALID, "negative limit");
   if (l != g->cap_log2) g->state_valid = false;
   g->cap_log2 = l;
   g->max_snaps_cfg = max_snapshots;
@@ -1085,7 +1026,7 @@ int cl_graph_set_limits(cl_graph* g, int32_t fifo_slots, int32_t max_snapshots, 
 int cl_graph_set_push_lanes(cl_graph* g, int32_t lanes) {
   G_CHECK(g);
   if (lanes != 0 && lanes != 1 && lanes != kPushLanes)
-    return gerr(CL_E_INVALID, "push lanes must be 0 (automatic), 1 or %d", kPushLanes);
+    return set_err(CL_E_INVALID, "push lanes must be 0 (automatic), 1 or %d", kPushLanes);
   g->push_lanes = lanes;
   return CL_OK;
 }
@@ -1094,7 +1035,7 @@ int cl_graph_node_id_length(cl_graph* g, int32_t rank, int32_t* len) {
   G_CHECK(g);
   int rc = g->freeze();
   if (rc) return rc;
-  if (rank < 0 || rank >= g->n || !len) return gerr(CL_E_INVALID, "bad rank or output");
+  if (rank < 0 || rank >= g->n || !len) return set_err(CL_E_INVALID, "bad rank or output");
   *len = (int32_t)g->node_id(rank).size();
   return CL_OK;
 }
@@ -1120,9 +1061,9 @@ int cl_graph_set_delay_go_seed(cl_graph* g, int64_t seed) {
 
 int cl_graph_set_delay_schedule(cl_graph* g, const uint8_t* delays, int64_t n) {
   G_CHECK(g);
-  if (!delays || n <= 0) return gerr(CL_E_INVALID, "empty schedule");
+  if (!delays || n <= 0) return set_err(CL_E_INVALID, "empty schedule");
   for (int64_t i = 0; i < n; ++i)
-    if (delays[i] >= 5) return gerr(CL_E_INVALID, "delay %u at %lld outside [0, maxDelay)", delays[i], (long long)i);
+    if (delays[i] >= 5) return set_err(CL_E_INVALID, "delay %u at %lld outside [0, maxDelay)", delays[i], (long long)i);
   g->user_sched.assign(delays, delays + n);
   g->delay_mode = 1;
   g->go_seed = false;
@@ -1133,7 +1074,7 @@ int cl_graph_set_delay_schedule(cl_graph* g, const uint8_t* delays, int64_t n) {
 
 int cl_graph_set_traffic(cl_graph* g, uint64_t seed, uint32_t threshold, int64_t steps) {
   G_CHECK(g);
-  if (steps < 0) return gerr(CL_E_INVALID, "negative traffic steps");
+  if (steps < 0) return set_err(CL_E_INVALID, "negative traffic steps");
   g->traffic_seed = seed;
   g->traffic_thresh = threshold;
   g->traffic_steps = threshold ? steps : 0;
@@ -1145,7 +1086,7 @@ int cl_graph_send_tokens_rank(cl_graph* g, int32_t src, int32_t dest, int64_t n)
   G_CHECK(g);
   int rc = g->freeze();
   if (rc) return rc;
-  if (src < 0 || src >= g->n) return gerr(CL_E_UNKNOWN_NODE, "send from unknown rank %d", src);
+  if (src < 0 || src >= g->n) return set_err(CL_E_UNKNOWN_NODE, "send from unknown rank %d", src);
   return g->append_send(src, dest >= 0 && dest < g->n ? dest : -1, n);
 }
 
@@ -1154,7 +1095,7 @@ int cl_graph_send_tokens(cl_graph* g, const char* src, const char* dest, int64_t
   int rc = g->freeze();
   if (rc) return rc;
   const int32_t a = g->rank_of_id(src);
-  if (a < 0) return gerr(CL_E_UNKNOWN_NODE, "send from unknown node %s", src ? src : "(null)");
+  if (a < 0) return set_err(CL_E_UNKNOWN_NODE, "send from unknown node %s", src ? src : "(null)");
   return g->append_send(a, g->rank_of_id(dest), n);  // unknown dest: fatal at run time (node.go:121-124)
 }
 
@@ -1162,7 +1103,7 @@ int cl_graph_start_snapshot_rank(cl_graph* g, int32_t node, int32_t* out_sid) {
   G_CHECK(g);
   int rc = g->freeze();
   if (rc) return rc;
-  if (node < 0 || node >= g->n) return gerr(CL_E_UNKNOWN_NODE, "snapshot at unknown rank %d", node);
+  if (node < 0 || node >= g->n) return set_err(CL_E_UNKNOWN_NODE, "snapshot at unknown rank %d", node);
   return g->append_snap(node, out_sid);
 }
 
@@ -1171,7 +1112,7 @@ int cl_graph_start_snapshot(cl_graph* g, const char* node, int32_t* out_sid) {
   int rc = g->freeze();
   if (rc) return rc;
   const int32_t a = g->rank_of_id(node);
-  if (a < 0) return gerr(CL_E_UNKNOWN_NODE, "snapshot at unknown node %s", node ? node : "(null)");
+  if (a < 0) return set_err(CL_E_UNKNOWN_NODE, "snapshot at unknown node %s", node ? node : "(null)");
   return g->append_snap(a, out_sid);
 }
 
@@ -1196,7 +1137,7 @@ int cl_graph_drain(cl_graph* g) {
 // execute as parallel send groups (cg_launch_sendgroup).
 int cl_graph_read_events_text(cl_graph* g, const char* text, int32_t* n_snapshots) {
   G_CHECK(g);
-  if (!text) return gerr(CL_E_INVALID, "null text");
+  if (!text) return set_err(CL_E_INVALID, "null text");
   int rc = g->freeze();
   if (rc) return rc;
   int32_t snaps = 0;
@@ -1205,26 +1146,26 @@ int cl_graph_read_events_text(cl_graph* g, const char* text, int32_t* n_snapshot
   while (it.next(&line)) {
     if (line == "#") continue;  // strings.HasPrefix("#", line) (test_common.go:90, sic)
     const int nf = go_fields_sv(line, f, 4);
-    if (nf == 0) return gerr(CL_E_PARSE, "empty event line");
+    if (nf == 0) return set_err(CL_E_PARSE, "empty event line");
     if (f[0] == "send") {
       int64_t nt;
-      if (nf < 4 || !go_atoi_sv(f[3], &nt)) return gerr(CL_E_PARSE, "bad send line: %.*s", (int)line.size(), line.data());
+      if (nf < 4 || !go_atoi_sv(f[3], &nt)) return set_err(CL_E_PARSE, "bad send line: %.*s", (int)line.size(), line.data());
       const int32_t a = g->rank_of_sv(f[1]);
-      if (a < 0) return gerr(CL_E_UNKNOWN_NODE, "send from unknown node %.*s", (int)f[1].size(), f[1].data());
+      if (a < 0) return set_err(CL_E_UNKNOWN_NODE, "send from unknown node %.*s", (int)f[1].size(), f[1].data());
       rc = g->append_send(a, g->rank_of_sv(f[2]), nt);  // unknown dest: fatal at run time (node.go:121-124)
     } else if (f[0] == "snapshot") {
-      if (nf < 2) return gerr(CL_E_PARSE, "bad snapshot line: %.*s", (int)line.size(), line.data());
+      if (nf < 2) return set_err(CL_E_PARSE, "bad snapshot line: %.*s", (int)line.size(), line.data());
       snaps++;
       const int32_t a = g->rank_of_sv(f[1]);
-      if (a < 0) return gerr(CL_E_UNKNOWN_NODE, "snapshot at unknown node %.*s", (int)f[1].size(), f[1].data());
+      if (a < 0) return set_err(CL_E_UNKNOWN_NODE, "snapshot at unknown node %.*s", (int)f[1].size(), f[1].data());
       rc = g->append_snap(a, nullptr);
     } else if (f[0] == "tick") {
       int64_t nt = 1;
-      if (nf > 1 && !go_atoi_sv(f[1], &nt)) return gerr(CL_E_PARSE, "bad tick line: %.*s", (int)line.size(), line.data());
-      if (nt > INT32_MAX) return gerr(CL_E_LIMIT, "tick count too large");
+      if (nf > 1 && !go_atoi_sv(f[1], &nt)) return set_err(CL_E_PARSE, "bad tick line: %.*s", (int)line.size(), line.data());
+      if (nt > INT32_MAX) return set_err(CL_E_LIMIT, "tick count too large");
       rc = g->append_tick(std::max<int64_t>(nt, 0));
     } else {
-      return gerr(CL_E_PARSE, "Unknown event command: %.*s", (int)f[0].size(), f[0].data());
+      return set_err(CL_E_PARSE, "Unknown event command: %.*s", (int)f[0].size(), f[0].data());
     }
     if (rc) return rc;
   }
@@ -1235,7 +1176,7 @@ int cl_graph_read_events_text(cl_graph* g, const char* text, int32_t* n_snapshot
 int cl_graph_read_events_file(cl_graph* g, const char* path, int32_t* n_snapshots) {
   G_CHECK(g);
   std::string text;
-  if (!path || !read_file(path, &text)) return gerr(CL_E_IO, "cannot read %s", path ? path : "(null)");
+  if (!path || !read_file(path, &text)) return set_err(CL_E_IO, "cannot read %s", path ? path : "(null)");
   return cl_graph_read_events_text(g, text.c_str(), n_snapshots);
 }
 
@@ -1256,49 +1197,46 @@ int cl_graph_synchronize(cl_graph* g) {
 
 int cl_graph_run_time(cl_graph* g, double* total_ms, int64_t* runs, int64_t* ticks) {
   G_CHECK(g);
-  if (!total_ms || !runs || !ticks) return gerr(CL_E_INVALID, "null output");
+  if (!total_ms || !runs || !ticks) return set_err(CL_E_INVALID, "null output");
   return g->fold_time(total_ms, runs, ticks);
 }
 
 int cl_graph_debug_poison_outputs(cl_graph* g) {
   G_CHECK(g);
   if (!g->dev_ready || !g->d_tokens.p) return CL_OK;
-  GHIP(hipSetDevice(g->device));
-  GHIP(hipMemsetAsync(g->d_tokens.p, 0xA5, g->d_tokens.bytes(), g->stream));
+  HIP_TRY(hipSetDevice(g->device));
+  HIP_TRY(hipMemsetAsync(g->d_tokens.p, 0xA5, g->d_tokens.bytes(), g->stream));
   // (the whole record plane: the run's reset rewrites W and cnt, so stok stays poisoned
   // wherever the run creates no local snapshot)
-  GHIP(hipMemsetAsync(g->d_sn.p, 0xA5, g->d_sn.bytes(), g->stream));
-  GHIP(hipMemsetAsync(g->d_rec.p, 0xA5, g->d_rec.bytes(), g->stream));
-  GHIP(hipMemsetAsync(g->d_ctick.p, 0xA5, g->d_ctick.bytes(), g->stream));
-  GHIP(hipMemsetAsync(g->d_cpart.p, 0xA5, g->d_cpart.bytes(), g->stream));
+  HIP_TRY(hipMemsetAsync(g->d_sn.p, 0xA5, g->d_sn.bytes(), g->stream));
+  HIP_TRY(hipMemsetAsync(g->d_rec.p, 0xA5, g->d_rec.bytes(), g->stream));
+  HIP_TRY(hipMemsetAsync(g->d_ctick.p, 0xA5, g->d_ctick.bytes(), g->stream));
+  HIP_TRY(hipMemsetAsync(g->d_cpart.p, 0xA5, g->d_cpart.bytes(), g->stream));
   return CL_OK;
 }
 
 int cl_graph_phase_time(cl_graph* g, double* ms, int64_t* ticks) {
   G_CHECK(g);
-  if (!ms || !ticks) return gerr(CL_E_INVALID, "null output");
-  if (!g->ph_ev[2]) return gerr(CL_E_STATE, "nothing has run");
+  if (!ms || !ticks) return set_err(CL_E_INVALID, "null output");
+  if (!g->ph.done) return set_err(CL_E_STATE, "nothing has run");
   int rc = g->sync();
   if (rc) return rc;
-  float a = 0.f, b = 0.f;
+  ms[1] = 0;
   if (g->ph_drain) {
-    GHIP(hipEventElapsedTime(&a, g->ph_ev[0], g->ph_ev[1]));
-    GHIP(hipEventElapsedTime(&b, g->ph_ev[1], g->ph_ev[2]));
+    if ((rc = g->ph.ms(0, 1, &ms[0])) || (rc = g->ph.ms(1, 2, &ms[1]))) return rc;
     ticks[0] = g->ph_time[1] - g->ph_time[0];
     ticks[1] = g->ph_time[2] - g->ph_time[1];
   } else {
-    GHIP(hipEventElapsedTime(&a, g->ph_ev[0], g->ph_ev[2]));
+    if ((rc = g->ph.ms(0, 2, &ms[0]))) return rc;
     ticks[0] = g->ph_time[2] - g->ph_time[0];
     ticks[1] = 0;
   }
-  ms[0] = a;
-  ms[1] = b;
   return CL_OK;
 }
 
 int cl_graph_device_bytes(cl_graph* g, int64_t* bytes) {
   G_CHECK(g);
-  if (!bytes) return gerr(CL_E_INVALID, "null output");
+  if (!bytes) return set_err(CL_E_INVALID, "null output");
   size_t b = 0;
   b += g->d_out_off.bytes() + g->d_route.bytes() + g->d_in_off.bytes() +
        g->d_in_src.bytes() + g->d_init_tok.bytes() + g->d_tokens.bytes() + g->d_pp.bytes() + g->d_tokcnt.bytes() + g->d_in_oj.bytes() +
@@ -1312,7 +1250,7 @@ int cl_graph_device_bytes(cl_graph* g, int64_t* bytes) {
 
 int cl_graph_get_status(cl_graph* g, int32_t* status) {
   G_CHECK(g);
-  if (!status) return gerr(CL_E_INVALID, "null output");
+  if (!status) return set_err(CL_E_INVALID, "null output");
   int rc = g->flush();
   if (rc) return rc;
   if ((rc = g->read_status(status))) return rc;
@@ -1322,62 +1260,62 @@ int cl_graph_get_status(cl_graph* g, int32_t* status) {
 
 int cl_graph_get_time(cl_graph* g, int64_t* time) {
   G_CHECK(g);
-  if (!time) return gerr(CL_E_INVALID, "null output");
+  if (!time) return set_err(CL_E_INVALID, "null output");
   int rc = g->flush();
   if (rc) return rc;
   GScal sc;
-  GHIP(hipMemcpy(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost));
   *time = sc.status ? sc.time : g->time;
   return CL_OK;
 }
 
 int cl_graph_num_snapshots(cl_graph* g, int32_t* n) {
   G_CHECK(g);
-  if (!n) return gerr(CL_E_INVALID, "null output");
+  if (!n) return set_err(CL_E_INVALID, "null output");
   *n = g->n_sids;
   return CL_OK;
 }
 
 int cl_graph_node_tokens(cl_graph* g, int64_t* out) {
   G_CHECK(g);
-  if (!out) return gerr(CL_E_INVALID, "null output");
+  if (!out) return set_err(CL_E_INVALID, "null output");
   int rc = g->flush();
   if (rc) return rc;
   std::vector<int32_t> t((size_t)g->n);
-  GHIP(hipMemcpy(t.data(), g->d_tokens.p, t.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(t.data(), g->d_tokens.p, t.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
   for (size_t i = 0; i < t.size(); ++i) out[i] = t[i];
   return CL_OK;
 }
 
 int cl_graph_snapshot_tick(cl_graph* g, int32_t sid, int32_t* tick) {
   G_CHECK(g);
-  if (!tick) return gerr(CL_E_INVALID, "null output");
-  if (sid < 0 || sid >= g->n_sids) return gerr(CL_E_INVALID, "unknown snapshot %d", sid);
+  if (!tick) return set_err(CL_E_INVALID, "null output");
+  if (sid < 0 || sid >= g->n_sids) return set_err(CL_E_INVALID, "unknown snapshot %d", sid);
   int rc = g->flush();
   if (rc) return rc;
-  GHIP(hipMemcpy(tick, g->d_ctick.p + sid, sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tick, g->d_ctick.p + sid, sizeof(int32_t), hipMemcpyDeviceToHost));
   return CL_OK;
 }
 
 int cl_graph_collect_snapshot(cl_graph* g, int32_t sid, int64_t* tokens, int64_t* msg_offsets, int64_t* msg_tokens,
                               int64_t msg_cap) {
   G_CHECK(g);
-  if (sid < 0 || sid >= g->n_sids) return gerr(CL_E_INVALID, "unknown snapshot %d", sid);
+  if (sid < 0 || sid >= g->n_sids) return set_err(CL_E_INVALID, "unknown snapshot %d", sid);
   int32_t tick;
   int rc = cl_graph_snapshot_tick(g, sid, &tick);
   if (rc) return rc;
-  if (tick < 0) return gerr(CL_E_NOT_COMPLETE, "snapshot %d has not completed", sid);
+  if (tick < 0) return set_err(CL_E_NOT_COMPLETE, "snapshot %d has not completed", sid);
   const size_t N = (size_t)g->n, E = (size_t)g->e;
   if (tokens) {
     std::vector<int32_t> st(N);
     // (the stok word of each 16-byte record of the plane: one strided copy)
-    GHIP(hipMemcpy2D(st.data(), sizeof(int32_t), &g->d_sn.p[(size_t)sid * N].stok, sizeof(SNode), sizeof(int32_t), N,
+    HIP_TRY(hipMemcpy2D(st.data(), sizeof(int32_t), &g->d_sn.p[(size_t)sid * N].stok, sizeof(SNode), sizeof(int32_t), N,
                      hipMemcpyDeviceToHost));
     for (size_t v = 0; v < N; ++v) tokens[v] = st[v];
   }
   if (!msg_offsets) return CL_OK;
   std::vector<uint64_t> rec(E);
-  if (E) GHIP(hipMemcpy(rec.data(), g->d_rec.p + (size_t)sid * E, E * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (E) HIP_TRY(hipMemcpy(rec.data(), g->d_rec.p + (size_t)sid * E, E * sizeof(uint64_t), hipMemcpyDeviceToHost));
   int64_t m = 0;
   for (size_t c = 0; c < E; ++c) {
     const uint64_t x = rec[g->ch_inpos[c]];
@@ -1385,11 +1323,11 @@ int cl_graph_collect_snapshot(cl_graph* g, int32_t sid, int64_t* tokens, int64_t
     m += (int64_t)((uint32_t)(x >> 32) - (uint32_t)x);
   }
   msg_offsets[E] = m;
-  if (m > msg_cap || (m > 0 && !msg_tokens)) return gerr(CL_E_LIMIT, "%lld messages exceed msg_cap", (long long)m);
+  if (m > msg_cap || (m > 0 && !msg_tokens)) return set_err(CL_E_LIMIT, "%lld messages exceed msg_cap", (long long)m);
   std::vector<uint32_t> hv;
   if (g->hist && m) {
     hv.resize(E * (size_t)g->hist);
-    GHIP(hipMemcpy(hv.data(), g->d_histv.p, hv.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hv.data(), g->d_histv.p, hv.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
   }
   for (size_t c = 0; c < E; ++c) {
     const size_t k = (size_t)g->ch_inpos[c];
@@ -1403,7 +1341,7 @@ int cl_graph_collect_snapshot(cl_graph* g, int32_t sid, int64_t* tokens, int64_t
 
 int cl_graph_trace_enable(cl_graph* g, int32_t capacity) {
   G_CHECK(g);
-  if (capacity < 0) return gerr(CL_E_INVALID, "negative trace capacity");
+  if (capacity < 0) return set_err(CL_E_INVALID, "negative trace capacity");
   g->trace_cap = capacity;
   g->state_valid = false;  // the next flush replays the program with tracing on (or off)
   return CL_OK;
@@ -1411,17 +1349,17 @@ int cl_graph_trace_enable(cl_graph* g, int32_t capacity) {
 
 int cl_graph_trace_read(cl_graph* g, cl_log_event* out, int32_t cap, int32_t* n_events) {
   G_CHECK(g);
-  if (!n_events) return gerr(CL_E_INVALID, "null output");
-  if (g->trace_cap <= 0) return gerr(CL_E_INVALID, "tracing is off (cl_graph_trace_enable)");
+  if (!n_events) return set_err(CL_E_INVALID, "null output");
+  if (g->trace_cap <= 0) return set_err(CL_E_INVALID, "tracing is off (cl_graph_trace_enable)");
   int rc = g->flush();
   if (rc) return rc;
   uint32_t cnt = 0;
-  GHIP(hipMemcpy(&cnt, g->d_trace_cnt.p, sizeof cnt, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&cnt, g->d_trace_cnt.p, sizeof cnt, hipMemcpyDeviceToHost));
   const uint32_t have = std::min<uint32_t>(cnt, (uint32_t)g->trace_cap);
   std::vector<GTraceRec> r(have);
-  if (have) GHIP(hipMemcpy(r.data(), g->d_trace.p, have * sizeof(GTraceRec), hipMemcpyDeviceToHost));
+  if (have) HIP_TRY(hipMemcpy(r.data(), g->d_trace.p, have * sizeof(GTraceRec), hipMemcpyDeviceToHost));
   if (cnt > (uint32_t)g->trace_cap)
-    return gerr(CL_E_LIMIT, "trace overflowed: %u records, capacity %d", cnt, g->trace_cap);
+    return set_err(CL_E_LIMIT, "trace overflowed: %u records, capacity %d", cnt, g->trace_cap);
   // EndSnapshotRecord (sim.go:127) follows the delivery that completed the local snapshot:
   // the last marker of that snapshot delivered to the node in that tick, in sender order
   // (the device counts completions in whatever order the atomics land).
@@ -1458,18 +1396,18 @@ int cl_graph_trace_read(cl_graph* g, cl_log_event* out, int32_t cap, int32_t* n_
 
 int cl_graph_get_counters(cl_graph* g, int64_t* out) {
   G_CHECK(g);
-  if (!out) return gerr(CL_E_INVALID, "null output");
+  if (!out) return set_err(CL_E_INVALID, "null output");
   int rc = g->flush();
   if (rc) return rc;
-  GHIP(hipMemsetAsync(g->d_scratch.p, 0, sizeof(unsigned long long), g->stream));
+  HIP_TRY(hipMemsetAsync(g->d_scratch.p, 0, sizeof(unsigned long long), g->stream));
   if ((rc = g->k_err(cg_launch_finish(g->P, g->n_sids, g->d_scratch.p, g->stream)))) return rc;
   GScal sc;
   unsigned long long open = 0;
   uint64_t cnt[kNumCnt];
   if ((rc = g->counter_totals(cnt))) return rc;
-  GHIP(hipMemcpyAsync(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost, g->stream));
-  GHIP(hipMemcpyAsync(&open, g->d_scratch.p, sizeof open, hipMemcpyDeviceToHost, g->stream));
-  GHIP(hipStreamSynchronize(g->stream));
+  HIP_TRY(hipMemcpyAsync(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipMemcpyAsync(&open, g->d_scratch.p, sizeof open, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
   out[CL_CNT_PUSH] = (int64_t)cnt[GC_PUSH];
   out[CL_CNT_PEEK] = (int64_t)cnt[GC_PEEK];
   out[CL_CNT_POP_TOKEN] = (int64_t)cnt[GC_POP_TOK];
@@ -1483,20 +1421,20 @@ int cl_graph_get_counters(cl_graph* g, int64_t* out) {
 
 int cl_graph_get_checksums(cl_graph* g, int64_t* out) {
   G_CHECK(g);
-  if (!out) return gerr(CL_E_INVALID, "null output");
+  if (!out) return set_err(CL_E_INVALID, "null output");
   int rc = g->flush();
   if (rc) return rc;
   const size_t ns = 3 + (size_t)g->n_sids;
-  GHIP(hipMemsetAsync(g->d_scratch.p, 0, ns * sizeof(unsigned long long), g->stream));
+  HIP_TRY(hipMemsetAsync(g->d_scratch.p, 0, ns * sizeof(unsigned long long), g->stream));
   if ((rc = g->k_err(cg_launch_checks(g->P, g->n_sids, g->d_scratch.p, g->stream)))) return rc;
   std::vector<unsigned long long> r(ns);
   std::vector<int32_t> ct((size_t)std::max(g->n_sids, 1));
   GScal sc;
-  GHIP(hipMemcpyAsync(r.data(), g->d_scratch.p, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipMemcpyAsync(r.data(), g->d_scratch.p, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, g->stream));
   if (g->n_sids)
-    GHIP(hipMemcpyAsync(ct.data(), g->d_ctick.p, (size_t)g->n_sids * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-  GHIP(hipMemcpyAsync(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost, g->stream));
-  GHIP(hipStreamSynchronize(g->stream));
+    HIP_TRY(hipMemcpyAsync(ct.data(), g->d_ctick.p, (size_t)g->n_sids * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipMemcpyAsync(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
   int64_t cut = 0, completed = 0;
   for (int32_t s = 0; s < g->n_sids; ++s) {
     if (ct[s] < 0) continue;
@@ -1521,36 +1459,31 @@ int cl_graph_snapshot_table(cl_graph* g, int32_t sid_lo, int32_t sid_hi, cl_grap
   G_CHECK(g);
   static_assert(sizeof(cl_graph_snap_row) == 16 * sizeof(int64_t), "cl_graph_snap_row is 16 x int64");
   if (sid_lo < 0 || sid_lo > sid_hi || sid_hi > g->n_sids)
-    return gerr(CL_E_INVALID, "snapshot range [%d, %d) outside [0, %d]", sid_lo, sid_hi, g->n_sids);
+    return set_err(CL_E_INVALID, "snapshot range [%d, %d) outside [0, %d]", sid_lo, sid_hi, g->n_sids);
   const int32_t ns = sid_hi - sid_lo;
   if (ns == 0) return CL_OK;
-  if (!rows) return gerr(CL_E_INVALID, "null output");
+  if (!rows) return set_err(CL_E_INVALID, "null output");
   int rc = g->flush();
   if (rc) return rc;
   if ((rc = g->d_table.ensure((size_t)ns * 16))) return rc;
-  for (auto& e : g->tb_ev)
-    if (!e) GHIP(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-  g->tb_timed = false;
-  GHIP(hipEventRecord(g->tb_ev[0], g->stream));
+  g->tb.done = 0;
+  if ((rc = g->tb.mark(0, g->stream))) return rc;
   // the in-CSR range of the owned nodes (all of them outside the partitioned mode)
   const int32_t k_lo = g->in_off[(size_t)g->P.part_lo], k_hi = g->in_off[(size_t)g->P.part_hi];
   if ((rc = g->k_err(cg_launch_table(g->P, g->d_in_ch.p, k_lo, k_hi, sid_lo, ns, g->d_table.p, g->n_cus, g->stream))))
     return rc;
-  GHIP(hipEventRecord(g->tb_ev[1], g->stream));
-  GHIP(hipMemcpyAsync(rows, g->d_table.p, (size_t)ns * sizeof(cl_graph_snap_row), hipMemcpyDeviceToHost, g->stream));
-  GHIP(hipStreamSynchronize(g->stream));
-  g->tb_timed = true;
+  if ((rc = g->tb.mark(1, g->stream))) return rc;
+  HIP_TRY(hipMemcpyAsync(rows, g->d_table.p, (size_t)ns * sizeof(cl_graph_snap_row), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  g->tb.done = 1;
   return CL_OK;
 }
 
 int cl_graph_table_time(cl_graph* g, double* ms) {
   G_CHECK(g);
-  if (!ms) return gerr(CL_E_INVALID, "null output");
-  if (!g->tb_timed) return gerr(CL_E_STATE, "no snapshot table has been computed");
-  float f = 0.f;
-  GHIP(hipEventElapsedTime(&f, g->tb_ev[0], g->tb_ev[1]));
-  *ms = f;
-  return CL_OK;
+  if (!ms) return set_err(CL_E_INVALID, "null output");
+  if (!g->tb.done) return set_err(CL_E_STATE, "no snapshot table has been computed");
+  return g->tb.ms(0, 1, ms);
 }
 
 int cl_graph_collect_sparse(cl_graph* g, int32_t sid_lo, int32_t sid_hi, int32_t* complete, int64_t* row_offsets,
@@ -1558,11 +1491,11 @@ int cl_graph_collect_sparse(cl_graph* g, int32_t sid_lo, int32_t sid_hi, int32_t
                             int64_t msg_cap, int32_t* tokens, cl_graph_sparse_info* info) {
   G_CHECK(g);
   static_assert(sizeof(cl_graph_sparse_info) == 8 * sizeof(int64_t), "cl_graph_sparse_info is 8 x int64");
-  if (!info) return gerr(CL_E_INVALID, "null info");
+  if (!info) return set_err(CL_E_INVALID, "null info");
   if (sid_lo < 0 || sid_lo > sid_hi || sid_hi > g->n_sids)
-    return gerr(CL_E_INVALID, "snapshot range [%d, %d) outside [0, %d]", sid_lo, sid_hi, g->n_sids);
-  if (ent_cap < 0 || msg_cap < 0) return gerr(CL_E_INVALID, "negative capacity");
-  if (ent_cap > 0 && (!ent_channel || !ent_count)) return gerr(CL_E_INVALID, "null entry arrays with ent_cap > 0");
+    return set_err(CL_E_INVALID, "snapshot range [%d, %d) outside [0, %d]", sid_lo, sid_hi, g->n_sids);
+  if (ent_cap < 0 || msg_cap < 0) return set_err(CL_E_INVALID, "negative capacity");
+  if (ent_cap > 0 && (!ent_channel || !ent_count)) return set_err(CL_E_INVALID, "null entry arrays with ent_cap > 0");
   const int32_t ns = sid_hi - sid_lo;
   *info = cl_graph_sparse_info{};
   info->node_lo = g->part ? g->part_lo : 0;
@@ -1583,19 +1516,17 @@ int cl_graph_collect_sparse(cl_graph* g, int32_t sid_lo, int32_t sid_hi, int32_t
   long long* d_off = g->d_sp_head.p;
   long long* d_moff = d_off + (nsz + 1);
   int32_t* d_complete = reinterpret_cast<int32_t*>(d_moff + (nsz + 1));
-  for (auto& e : g->sp_ev)
-    if (!e) GHIP(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-  g->sp_timed = g->sp_wrote = false;
-  GHIP(hipEventRecord(g->sp_ev[0], g->stream));
+  g->sp.done = 0;
+  if ((rc = g->sp.mark(0, g->stream))) return rc;
   if ((rc = g->k_err(cg_launch_sparse_scan(P, sid_lo, ns, g->d_sp_tiles.p, g->d_sp_rows.p, d_off, d_moff, d_complete,
                                            g->stream))))
     return rc;
-  GHIP(hipEventRecord(g->sp_ev[1], g->stream));
+  if ((rc = g->sp.mark(1, g->stream))) return rc;
   // the totals decide the sizes: the host reads the head between scan and write
   std::vector<long long> head(head_words);
-  GHIP(hipMemcpyAsync(head.data(), d_off, head_words * sizeof(long long), hipMemcpyDeviceToHost, g->stream));
-  GHIP(hipStreamSynchronize(g->stream));
-  g->sp_timed = true;
+  HIP_TRY(hipMemcpyAsync(head.data(), d_off, head_words * sizeof(long long), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  g->sp.done = 1;
   const int32_t* h_complete = reinterpret_cast<const int32_t*>(head.data() + 2 * (nsz + 1));
   const int64_t n_entries = head[nsz], n_msgs = head[2 * nsz + 1];
   info->n_sids = ns;
@@ -1606,71 +1537,71 @@ int cl_graph_collect_sparse(cl_graph* g, int32_t sid_lo, int32_t sid_hi, int32_t
   if (complete) std::copy(h_complete, h_complete + ns, complete);
   if (row_offsets) std::copy(head.begin(), head.begin() + (ns + 1), row_offsets);
   if (n_entries > ent_cap)
-    return gerr(CL_E_LIMIT, "%lld entries exceed ent_cap %lld", (long long)n_entries, (long long)ent_cap);
+    return set_err(CL_E_LIMIT, "%lld entries exceed ent_cap %lld", (long long)n_entries, (long long)ent_cap);
   if (msg_tokens && n_msgs > msg_cap)
-    return gerr(CL_E_LIMIT, "%lld messages exceed msg_cap %lld", (long long)n_msgs, (long long)msg_cap);
+    return set_err(CL_E_LIMIT, "%lld messages exceed msg_cap %lld", (long long)n_msgs, (long long)msg_cap);
   // unit payloads are all 1: no history on the device, nothing to pack or copy
   const bool dev_msgs = msg_tokens && g->hist > 0 && n_msgs > 0;
   const int64_t width = info->node_hi - info->node_lo;
   if ((rc = g->d_sp_chan.ensure((size_t)n_entries)) || (rc = g->d_sp_cnt.ensure((size_t)n_entries))) return rc;
   if (dev_msgs && (rc = g->d_sp_msg.ensure((size_t)n_msgs))) return rc;
   if (tokens && (rc = g->d_sp_tok.ensure(nsz * (size_t)width))) return rc;
-  GHIP(hipEventRecord(g->sp_ev[2], g->stream));
+  if ((rc = g->sp.mark(2, g->stream))) return rc;
   if (n_entries > 0 &&
       (rc = g->k_err(cg_launch_sparse_write(P, sid_lo, ns, g->d_sp_tiles.p, g->d_sp_rows.p, d_off, d_moff,
                                             g->d_sp_chan.p, g->d_sp_cnt.p, dev_msgs ? g->d_sp_msg.p : nullptr,
                                             g->stream))))
     return rc;
   if (tokens && (rc = g->k_err(cg_launch_sparse_tokens(P, sid_lo, ns, g->d_sp_tok.p, g->stream)))) return rc;
-  GHIP(hipEventRecord(g->sp_ev[3], g->stream));
+  if ((rc = g->sp.mark(3, g->stream))) return rc;
   if (n_entries > 0) {
-    GHIP(hipMemcpyAsync(ent_channel, g->d_sp_chan.p, (size_t)n_entries * sizeof(int32_t), hipMemcpyDeviceToHost,
+    HIP_TRY(hipMemcpyAsync(ent_channel, g->d_sp_chan.p, (size_t)n_entries * sizeof(int32_t), hipMemcpyDeviceToHost,
                         g->stream));
-    GHIP(hipMemcpyAsync(ent_count, g->d_sp_cnt.p, (size_t)n_entries * sizeof(int32_t), hipMemcpyDeviceToHost,
+    HIP_TRY(hipMemcpyAsync(ent_count, g->d_sp_cnt.p, (size_t)n_entries * sizeof(int32_t), hipMemcpyDeviceToHost,
                         g->stream));
   }
   if (dev_msgs)
-    GHIP(hipMemcpyAsync(msg_tokens, g->d_sp_msg.p, (size_t)n_msgs * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(msg_tokens, g->d_sp_msg.p, (size_t)n_msgs * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
   if (tokens && width > 0)
-    GHIP(hipMemcpyAsync(tokens, g->d_sp_tok.p, nsz * (size_t)width * sizeof(int32_t), hipMemcpyDeviceToHost,
+    HIP_TRY(hipMemcpyAsync(tokens, g->d_sp_tok.p, nsz * (size_t)width * sizeof(int32_t), hipMemcpyDeviceToHost,
                         g->stream));
-  GHIP(hipStreamSynchronize(g->stream));
-  g->sp_wrote = true;
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  g->sp.done = 2;
   if (msg_tokens && !dev_msgs) std::fill(msg_tokens, msg_tokens + n_msgs, 1);
   return CL_OK;
 }
 
 int cl_graph_sparse_time(cl_graph* g, double* ms) {
   G_CHECK(g);
-  if (!ms) return gerr(CL_E_INVALID, "null output");
-  if (!g->sp_timed) return gerr(CL_E_STATE, "no sparse collect has run");
-  float a = 0.f, b = 0.f;
-  GHIP(hipEventElapsedTime(&a, g->sp_ev[0], g->sp_ev[1]));
-  if (g->sp_wrote) GHIP(hipEventElapsedTime(&b, g->sp_ev[2], g->sp_ev[3]));
-  *ms = (double)a + (double)b;
-  return CL_OK;
+  if (!ms) return set_err(CL_E_INVALID, "null output");
+  if (!g->sp.done) return set_err(CL_E_STATE, "no sparse collect has run");
+  double a = 0, b = 0;
+  int rc = g->sp.ms(0, 1, &a);
+  if (!rc && g->sp.done > 1) rc = g->sp.ms(2, 3, &b);
+  *ms = a + b;
+  return rc;
 }
 
 // ---- graph-partitioned mode ---------------------------------------------
 #define G_PART(g)                                                                           \
   do {                                                                                       \
-    if (!(g)->part) return gerr(CL_E_STATE, "not a partitioned run (cl_graph_part_begin)");  \
+    if (!(g)->part) return set_err(CL_E_STATE, "not a partitioned run (cl_graph_part_begin)");  \
   } while (0)
 
 int cl_graph_part_begin(cl_graph* g, int32_t node_lo, int32_t node_hi) {
   G_CHECK(g);
   int rc = g->freeze();
   if (rc) return rc;
-  if (g->part) return gerr(CL_E_STATE, "the partitioned run has begun");
-  if (!g->prog.empty()) return gerr(CL_E_STATE, "a partitioned run starts from an empty program");
-  if (g->trace_cap > 0) return gerr(CL_E_STATE, "the event trace is not available in the partitioned mode");
-  if (g->go_seed) return gerr(CL_E_STATE, "the partitioned mode takes the counter hash or an explicit delay schedule");
+  if (g->part) return set_err(CL_E_STATE, "the partitioned run has begun");
+  if (!g->prog.empty()) return set_err(CL_E_STATE, "a partitioned run starts from an empty program");
+  if (g->trace_cap > 0) return set_err(CL_E_STATE, "the event trace is not available in the partitioned mode");
+  if (g->go_seed) return set_err(CL_E_STATE, "the partitioned mode takes the counter hash or an explicit delay schedule");
   if (node_lo < 0 || node_lo > node_hi || node_hi > g->n || node_lo % kGThreads ||
       (node_hi != g->n && node_hi % kGThreads))
-    return gerr(CL_E_INVALID, "node range [%d, %d) must be block-aligned (%d) within [0, %d)", node_lo, node_hi,
+    return set_err(CL_E_INVALID, "node range [%d, %d) must be block-aligned (%d) within [0, %d)", node_lo, node_hi,
                 kGThreads, g->n);
   if ((rc = g->ensure_device())) return rc;
-  GHIP(hipSetDevice(g->device));
+  HIP_TRY(hipSetDevice(g->device));
   bool realloc = false;
   if ((rc = g->ensure_state(&realloc)) || (rc = g->ensure_sched()) || (rc = g->upload_ops())) return rc;
   const size_t N = (size_t)g->n;
@@ -1683,8 +1614,8 @@ int cl_graph_part_begin(cl_graph* g, int32_t node_lo, int32_t node_hi) {
   g->part_hi = node_hi;
   g->fill_params();
   if ((rc = g->k_err(cg_launch_reset(g->P, g->d_init_tok.p, g->stream)))) return rc;
-  GHIP(hipMemsetAsync(g->d_trigv.p, 0, N * sizeof(int32_t), g->stream));
-  GHIP(hipStreamSynchronize(g->stream));
+  HIP_TRY(hipMemsetAsync(g->d_trigv.p, 0, N * sizeof(int32_t), g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
   g->time = 0;
   g->hang = false;
   g->executed = g->prog.size();
@@ -1695,18 +1626,18 @@ int cl_graph_part_begin(cl_graph* g, int32_t node_lo, int32_t node_hi) {
 int cl_graph_part_snapshot(cl_graph* g, int32_t node, int32_t* out_sid) {
   G_CHECK(g);
   G_PART(g);
-  if (node < 0 || node >= g->n) return gerr(CL_E_UNKNOWN_NODE, "snapshot at unknown rank %d", node);
-  if (g->n_sids >= g->s_cap) return gerr(CL_E_LIMIT, "more than %d snapshots (cl_graph_set_limits)", g->s_cap);
+  if (node < 0 || node >= g->n) return set_err(CL_E_UNKNOWN_NODE, "snapshot at unknown rank %d", node);
+  if (g->n_sids >= g->s_cap) return set_err(CL_E_LIMIT, "more than %d snapshots (cl_graph_set_limits)", g->s_cap);
   const GOp op{GOP_SNAP, node, g->n_sids, 0};
   // stream-ordered: a k_hostops of an earlier call may still be queued on g->stream and read
   // d_pop (a null-stream hipMemcpy does not wait for the non-blocking stream: two snapshots
   // started back to back raced here)
-  GHIP(hipMemcpyAsync(g->d_pop.p, &op, sizeof op, hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(hipMemcpyAsync(g->d_pop.p, &op, sizeof op, hipMemcpyHostToDevice, g->stream));
   GParams q = g->P;
   q.ops = g->d_pop.p;
   int rc = g->k_err(cg_launch_hostops(q, (int32_t)g->time, 0, 1, g->stream));
   if (rc) return rc;
-  GHIP(hipStreamSynchronize(g->stream));  // (`op` is a stack copy)
+  HIP_TRY(hipStreamSynchronize(g->stream));  // (`op` is a stack copy)
   if (out_sid) *out_sid = g->n_sids;
   g->n_sids++;
   return CL_OK;
@@ -1715,17 +1646,17 @@ int cl_graph_part_snapshot(cl_graph* g, int32_t node, int32_t* out_sid) {
 int cl_graph_part_pick(cl_graph* g, int32_t* rows, int64_t cap, int64_t* n_rows) {
   G_CHECK(g);
   G_PART(g);
-  if (!n_rows || (cap > 0 && !rows)) return gerr(CL_E_INVALID, "null output");
-  if (g->time + 1 > kMaxGraphTime) return gerr(CL_E_LIMIT, "simulated time would exceed %lld ticks", (long long)kMaxGraphTime);
+  if (!n_rows || (cap > 0 && !rows)) return set_err(CL_E_INVALID, "null output");
+  if (g->time + 1 > kMaxGraphTime) return set_err(CL_E_LIMIT, "simulated time would exceed %lld ticks", (long long)kMaxGraphTime);
   ++g->time;
   int rc = g->k_err(cg_launch_part_pick(g->P, (int32_t)g->time, g->stream));
   if (rc) return rc;
   uint32_t cnt[4];
-  GHIP(hipMemcpyAsync(cnt, g->d_out_n.p, sizeof cnt, hipMemcpyDeviceToHost, g->stream));
-  GHIP(hipStreamSynchronize(g->stream));
+  HIP_TRY(hipMemcpyAsync(cnt, g->d_out_n.p, sizeof cnt, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
   *n_rows = cnt[0];
-  if ((int64_t)cnt[0] > cap) return gerr(CL_E_LIMIT, "%u outgoing deliveries exceed cap %lld", cnt[0], (long long)cap);
-  if (cnt[0]) GHIP(hipMemcpy(rows, g->d_outbox.p, cnt[0] * sizeof(PDel), hipMemcpyDeviceToHost));
+  if ((int64_t)cnt[0] > cap) return set_err(CL_E_LIMIT, "%u outgoing deliveries exceed cap %lld", cnt[0], (long long)cap);
+  if (cnt[0]) HIP_TRY(hipMemcpy(rows, g->d_outbox.p, cnt[0] * sizeof(PDel), hipMemcpyDeviceToHost));
   return CL_OK;
 }
 
@@ -1733,41 +1664,41 @@ int cl_graph_part_receive(cl_graph* g, const int32_t* rows, int64_t n, int32_t* 
                           int64_t* n_reports) {
   G_CHECK(g);
   G_PART(g);
-  if (!n_reports || (n > 0 && !rows) || (cap > 0 && !reports)) return gerr(CL_E_INVALID, "null array");
-  if (n < 0 || n > g->n) return gerr(CL_E_INVALID, "%lld incoming deliveries", (long long)n);
+  if (!n_reports || (n > 0 && !rows) || (cap > 0 && !reports)) return set_err(CL_E_INVALID, "null array");
+  if (n < 0 || n > g->n) return set_err(CL_E_INVALID, "%lld incoming deliveries", (long long)n);
   int rc = g->d_inbox.ensure((size_t)n);
   if (rc) return rc;
   for (int64_t i = 0; i < n; ++i) {
     const int32_t* r = rows + 4 * i;
     if (r[1] < g->part_lo || r[1] >= g->part_hi || r[0] < 0 || r[0] >= g->n || r[2] < 0 || r[2] >= g->e)
-      return gerr(CL_E_INVALID, "delivery %lld is not addressed to this device's nodes", (long long)i);
+      return set_err(CL_E_INVALID, "delivery %lld is not addressed to this device's nodes", (long long)i);
   }
-  if (n) GHIP(hipMemcpyAsync(g->d_inbox.p, rows, (size_t)n * sizeof(PDel), hipMemcpyHostToDevice, g->stream));
+  if (n) HIP_TRY(hipMemcpyAsync(g->d_inbox.p, rows, (size_t)n * sizeof(PDel), hipMemcpyHostToDevice, g->stream));
   if ((rc = g->k_err(cg_launch_part_receive(g->P, (int32_t)g->time, g->d_inbox.p, (int32_t)n, g->stream)))) return rc;
   uint32_t cnt[4];
-  GHIP(hipMemcpyAsync(cnt, g->d_out_n.p, sizeof cnt, hipMemcpyDeviceToHost, g->stream));
-  GHIP(hipStreamSynchronize(g->stream));
+  HIP_TRY(hipMemcpyAsync(cnt, g->d_out_n.p, sizeof cnt, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
   *n_reports = cnt[2];
-  if ((int64_t)cnt[2] > cap) return gerr(CL_E_LIMIT, "%u reports exceed cap %lld", cnt[2], (long long)cap);
-  if (cnt[2]) GHIP(hipMemcpy(reports, g->d_reports.p, cnt[2] * sizeof(int2), hipMemcpyDeviceToHost));
+  if ((int64_t)cnt[2] > cap) return set_err(CL_E_LIMIT, "%u reports exceed cap %lld", cnt[2], (long long)cap);
+  if (cnt[2]) HIP_TRY(hipMemcpy(reports, g->d_reports.p, cnt[2] * sizeof(int2), hipMemcpyDeviceToHost));
   return CL_OK;
 }
 
 int cl_graph_part_tally(cl_graph* g, int32_t step, const int32_t* reports, int64_t n, int64_t* totals) {
   G_CHECK(g);
   G_PART(g);
-  if (!totals || (n > 0 && !reports)) return gerr(CL_E_INVALID, "null array");
-  if (n < 0 || n > g->n) return gerr(CL_E_INVALID, "%lld reports", (long long)n);
+  if (!totals || (n > 0 && !reports)) return set_err(CL_E_INVALID, "null array");
+  if (n < 0 || n > g->n) return set_err(CL_E_INVALID, "%lld reports", (long long)n);
   for (int64_t i = 0; i < n; ++i)
     if (reports[2 * i] < g->part_lo || reports[2 * i] >= g->part_hi || reports[2 * i + 1] < 0)
-      return gerr(CL_E_INVALID, "report %lld is not about this device's senders", (long long)i);
+      return set_err(CL_E_INVALID, "report %lld is not about this device's senders", (long long)i);
   int rc = g->d_rep_in.ensure((size_t)n);
   if (rc) return rc;
-  if (n) GHIP(hipMemcpyAsync(g->d_rep_in.p, reports, (size_t)n * sizeof(int2), hipMemcpyHostToDevice, g->stream));
+  if (n) HIP_TRY(hipMemcpyAsync(g->d_rep_in.p, reports, (size_t)n * sizeof(int2), hipMemcpyHostToDevice, g->stream));
   if ((rc = g->k_err(cg_launch_part_tally(g->P, step, g->d_rep_in.p, (int32_t)n, g->stream)))) return rc;
   GScal sc;
-  GHIP(hipMemcpyAsync(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost, g->stream));
-  GHIP(hipStreamSynchronize(g->stream));
+  HIP_TRY(hipMemcpyAsync(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
   totals[0] = (int64_t)sc.tot_trig;
   totals[1] = (int64_t)sc.tot_send;
   totals[2] = sc.status;
@@ -1777,47 +1708,47 @@ int cl_graph_part_tally(cl_graph* g, int32_t step, const int32_t* reports, int64
 int cl_graph_part_freeze(cl_graph* g, int32_t status) {
   G_CHECK(g);
   G_PART(g);
-  if (status <= 0) return gerr(CL_E_INVALID, "freeze needs a nonzero status");
+  if (status <= 0) return set_err(CL_E_INVALID, "freeze needs a nonzero status");
   GScal sc;
-  GHIP(hipMemcpyAsync(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost, g->stream));
-  GHIP(hipStreamSynchronize(g->stream));
+  HIP_TRY(hipMemcpyAsync(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
   if (sc.status) return CL_OK;
-  GHIP(hipMemcpyAsync(&g->d_sc.p->status, &status, sizeof status, hipMemcpyHostToDevice, g->stream));
-  GHIP(hipStreamSynchronize(g->stream));
+  HIP_TRY(hipMemcpyAsync(&g->d_sc.p->status, &status, sizeof status, hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
   return CL_OK;
 }
 
 int cl_graph_part_bases(cl_graph* g, const int64_t* bases, const int32_t* s0, int64_t n, int64_t* draw0) {
   G_CHECK(g);
   G_PART(g);
-  if (!bases || (n > 0 && (!s0 || !draw0))) return gerr(CL_E_INVALID, "null array");
-  if (n < 0 || n > g->n) return gerr(CL_E_INVALID, "%lld reports", (long long)n);
+  if (!bases || (n > 0 && (!s0 || !draw0))) return set_err(CL_E_INVALID, "null array");
+  if (n < 0 || n > g->n) return set_err(CL_E_INVALID, "%lld reports", (long long)n);
   for (int64_t i = 0; i < n; ++i)
-    if (s0[i] < g->part_lo || s0[i] >= g->part_hi) return gerr(CL_E_INVALID, "sender %d is not this device's", s0[i]);
+    if (s0[i] < g->part_lo || s0[i] >= g->part_hi) return set_err(CL_E_INVALID, "sender %d is not this device's", s0[i]);
   int rc;
   if ((rc = g->d_s0.ensure((size_t)n)) || (rc = g->d_draw0.ensure((size_t)n))) return rc;
-  if (n) GHIP(hipMemcpyAsync(g->d_s0.p, s0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+  if (n) HIP_TRY(hipMemcpyAsync(g->d_s0.p, s0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
   if ((rc = g->k_err(cg_launch_part_bases(g->P, bases[0], bases[1], bases[2], bases[3], g->d_s0.p, (int32_t)n,
                                           g->d_draw0.p, g->stream))))
     return rc;
-  if (n) GHIP(hipMemcpyAsync(draw0, g->d_draw0.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-  GHIP(hipStreamSynchronize(g->stream));
+  if (n) HIP_TRY(hipMemcpyAsync(draw0, g->d_draw0.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
   return CL_OK;
 }
 
 int cl_graph_part_push(cl_graph* g, int32_t step, const int64_t* replies, int64_t n) {
   G_CHECK(g);
   G_PART(g);
-  if (n > 0 && !replies) return gerr(CL_E_INVALID, "null array");
-  if (n < 0 || n > g->n) return gerr(CL_E_INVALID, "%lld replies", (long long)n);
+  if (n > 0 && !replies) return set_err(CL_E_INVALID, "null array");
+  if (n < 0 || n > g->n) return set_err(CL_E_INVALID, "%lld replies", (long long)n);
   for (int64_t i = 0; i < n; ++i)
     if (replies[2 * i] < 0 || replies[2 * i] >= g->n || (replies[2 * i] >= g->part_lo && replies[2 * i] < g->part_hi))
-      return gerr(CL_E_INVALID, "reply %lld names sender %lld", (long long)i, (long long)replies[2 * i]);
+      return set_err(CL_E_INVALID, "reply %lld names sender %lld", (long long)i, (long long)replies[2 * i]);
   int rc = g->d_replies.ensure(2 * (size_t)n);
   if (rc) return rc;
-  if (n) GHIP(hipMemcpyAsync(g->d_replies.p, replies, 2 * (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
+  if (n) HIP_TRY(hipMemcpyAsync(g->d_replies.p, replies, 2 * (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
   if ((rc = g->k_err(cg_launch_part_push(g->P, (int32_t)g->time, step, g->d_replies.p, (int32_t)n, g->stream)))) return rc;
-  GHIP(hipStreamSynchronize(g->stream));  // (the staged rows must outlive the launch)
+  HIP_TRY(hipStreamSynchronize(g->stream));  // (the staged rows must outlive the launch)
   return CL_OK;
 }
 
@@ -1826,8 +1757,8 @@ int cl_graph_set_stream(cl_graph* g, void* stream) {
   G_CHECK(g);
   int rc = g->ensure_device();
   if (rc) return rc;
-  GHIP(hipSetDevice(g->device));
-  GHIP(hipStreamSynchronize(g->stream));
+  HIP_TRY(hipSetDevice(g->device));
+  HIP_TRY(hipStreamSynchronize(g->stream));
   g->stream = stream ? (hipStream_t)stream : g->own_stream;
   return CL_OK;
 }
@@ -1836,7 +1767,7 @@ int cl_graph_set_stream(cl_graph* g, void* stream) {
   do {                                                                                            \
     G_CHECK(g);                                                                                   \
     G_PART(g);                                                                                    \
-    if (!(g)->bk_send) return gerr(CL_E_STATE, "no device exchange buffers (cl_graph_part_dev_bind)"); \
+    if (!(g)->bk_send) return set_err(CL_E_STATE, "no device exchange buffers (cl_graph_part_dev_bind)"); \
   } while (0)
 
 int cl_graph_part_dev_bind(cl_graph* g, int32_t world, int32_t rank, int32_t span, int64_t cap, void* send,
@@ -1844,18 +1775,18 @@ int cl_graph_part_dev_bind(cl_graph* g, int32_t world, int32_t rank, int32_t spa
   G_CHECK(g);
   G_PART(g);
   if (world < 1 || rank < 0 || rank >= world || span <= 0 || span % kGThreads)
-    return gerr(CL_E_INVALID, "rank %d of %d, span %d (a positive multiple of %d)", rank, world, span, kGThreads);
+    return set_err(CL_E_INVALID, "rank %d of %d, span %d (a positive multiple of %d)", rank, world, span, kGThreads);
   if (g->part_lo != rank * span || g->part_hi != std::min<int64_t>((int64_t)(rank + 1) * span, g->n))
-    return gerr(CL_E_INVALID, "rank %d x span %d is not this device's range [%d, %d)", rank, span, g->part_lo,
+    return set_err(CL_E_INVALID, "rank %d x span %d is not this device's range [%d, %d)", rank, span, g->part_lo,
                 g->part_hi);
-  if ((int64_t)world * span < g->n) return gerr(CL_E_INVALID, "%d ranks x %d nodes do not cover %d", world, span, g->n);
-  if (cap < 1 || cap > g->n) return gerr(CL_E_INVALID, "bucket capacity %lld", (long long)cap);
-  if (!send || !recv || !tot_send || !tot_recv) return gerr(CL_E_INVALID, "null exchange buffer");
-  GHIP(hipSetDevice(g->device));
+  if ((int64_t)world * span < g->n) return set_err(CL_E_INVALID, "%d ranks x %d nodes do not cover %d", world, span, g->n);
+  if (cap < 1 || cap > g->n) return set_err(CL_E_INVALID, "bucket capacity %lld", (long long)cap);
+  if (!send || !recv || !tot_send || !tot_recv) return set_err(CL_E_INVALID, "null exchange buffer");
+  HIP_TRY(hipSetDevice(g->device));
   int rc = g->d_bk_cnt.ensure((size_t)world);
   if (rc) return rc;
-  GHIP(hipMemsetAsync(g->d_bk_cnt.p, 0, (size_t)world * sizeof(uint32_t), g->stream));
-  GHIP(hipStreamSynchronize(g->stream));
+  HIP_TRY(hipMemsetAsync(g->d_bk_cnt.p, 0, (size_t)world * sizeof(uint32_t), g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
   g->bk_world = world;
   g->bk_rank = rank;
   g->bk_span = span;
@@ -1875,7 +1806,7 @@ int cl_graph_part_dev_seal(cl_graph* g) {
 
 int cl_graph_part_dev_pick(cl_graph* g) {
   G_DEV(g);
-  if (g->time + 1 > kMaxGraphTime) return gerr(CL_E_LIMIT, "simulated time would exceed %lld ticks", (long long)kMaxGraphTime);
+  if (g->time + 1 > kMaxGraphTime) return set_err(CL_E_LIMIT, "simulated time would exceed %lld ticks", (long long)kMaxGraphTime);
   ++g->time;
   return g->k_err(cg_launch_part_dev_pick(g->P, (int32_t)g->time, g->stream));
 }

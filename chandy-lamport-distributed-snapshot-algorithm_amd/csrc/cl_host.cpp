@@ -31,6 +31,7 @@
 #include "../../include/clsnap.h"
 #include "cl_engine.h"
 #include "cl_gorand.h"
+#include "cl_host.h"
 #include "cl_text.h"
 
 using namespace clsnap;
@@ -44,6 +45,13 @@ int set_error_v(int code, const char* fmt, va_list ap) {
   vsnprintf(buf, sizeof buf, fmt, ap);
   g_last_error = buf;
   return code;
+}
+int set_err(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  const int rc = set_error_v(code, fmt, ap);
+  va_end(ap);
+  return rc;
 }
 const char* last_error() { return g_last_error.c_str(); }
 }  // namespace clsnap
@@ -63,14 +71,6 @@ constexpr int64_t kMapMinInstances = 4096;
 constexpr int64_t kMapPct = 92;
 
 namespace {
-
-int set_err(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  const int rc = set_error_v(code, fmt, ap);
-  va_end(ap);
-  return rc;
-}
 
 // ---------------------------------------------------------------------------
 // Go math/rand (Go 1.22, go.mod:3): rngSource seeded as in rng.go, Intn -> Int31n.
@@ -183,33 +183,6 @@ int64_t go_schedule_jump(int64_t seed_base, const int64_t* seeds, int64_t n, int
   return rejected.load();
 }
 
-#define HIP_TRY(expr)                                                                     \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) return set_err(CL_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  int ensure(size_t count) {
-    if (count <= n && p) return CL_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    if (count == 0) count = 1;
-    HIP_TRY(hipMalloc((void**)&p, count * sizeof(T)));
-    n = count;
-    return CL_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
-
 // ---- the device generator (cl_gorand.hip) and its host-side patching ---------------------------
 // Shapes it takes: rows up to the documented cap, a plane of fewer than 2^31 dwords.
 bool delaygen_fits(int64_t n, int64_t row) {
@@ -224,10 +197,10 @@ struct DeviceGen {
 
 // Generate the [n][row] plane at d_plane on `stream` (seeds: d_seeds, a device array, or
 // seed_base + i), wait, and regenerate the rows that met a rejection among their first `draws`
-// outputs with the sequential generator.  d_flag has 1 + kDelayGenFlagCap words; ev two events.
+// outputs with the sequential generator.  d_flag has 1 + kDelayGenFlagCap words; `tm` times the kernel.
 int device_generate(int device, hipStream_t stream, int32_t n_cus, int64_t seed_base, const long long* d_seeds,
                     int64_t n, int64_t row, int64_t draws, uint8_t* d_plane, unsigned long long* d_flag,
-                    hipEvent_t* ev, DeviceGen* g) {
+                    DevTimer<2>* tm, DeviceGen* g) {
   const void* tables = nullptr;
   int e = gorand::delaygen_tables(device, &tables);
   if (e) return set_err(CL_E_DEVICE, "delay generator tables: %s", hipGetErrorString((hipError_t)e));
@@ -243,10 +216,10 @@ int device_generate(int device, hipStream_t stream, int32_t n_cus, int64_t seed_
   p.flagged = d_flag;
   p.flag_cap = gorand::kDelayGenFlagCap;
   p.tables = tables;
-  HIP_TRY(hipEventRecord(ev[0], stream));
+  if (int rc = tm->mark(0, stream)) return rc;
   e = gorand::launch_delaygen(p, n_cus, stream);
   if (e) return set_err(CL_E_DEVICE, "delay generator launch failed: %s", hipGetErrorString((hipError_t)e));
-  HIP_TRY(hipEventRecord(ev[1], stream));
+  if (int rc = tm->mark(1, stream)) return rc;
   unsigned long long cnt = 0;
   HIP_TRY(hipMemcpyAsync(&cnt, d_flag, sizeof cnt, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
@@ -270,26 +243,10 @@ int device_generate(int device, hipStream_t stream, int32_t n_cus, int64_t seed_
     g->patched = (int64_t)rows.size();
   }
   g->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-  g->device_ms = ms;
-  return CL_OK;
+  return tm->ms(0, 1, &g->device_ms);
 }
 
 }  // namespace
-
-// ---------------------------------------------------------------------------
-// cl_iset: a device-resident set of instances of one sim (cl_iset.hip)
-// ---------------------------------------------------------------------------
-// Only a set of indices: nothing in it refers to a run, an engine or a record layout.  The bitmap
-// (stride / 64 words, the bits from n_instances on 0) is allocated on the first call that needs it
-// on the device; until then a set made from a list keeps the list (`pending`; empty: the empty set).
-struct cl_iset {
-  cl_sim* sim = nullptr;
-  DevBuf<unsigned long long> bits;
-  bool resident = false;          // bits holds the set
-  std::vector<int64_t> pending;   // the list to scatter when the bitmap is made
-};
 
 // ---------------------------------------------------------------------------
 // cl_sim
@@ -433,7 +390,7 @@ struct cl_sim {
   DevBuf<uint8_t> d_sched;
   DevBuf<long long> d_seeds;              // [n_inst] the seed list, once the device generator ran with it
   DevBuf<unsigned long long> d_dg_flag;   // device generator: count, then the rows that met a rejection
-  hipEvent_t dg_ev[2] = {nullptr, nullptr};
+  DevTimer<2> dg_tm;
   DevBuf<uint32_t> d_state;
   DevBuf<int32_t> d_regs;
   DevBuf<uint32_t> d_snap_nod;  // [s_cap][stride][n][lay.rw] node snapshot records
@@ -463,7 +420,7 @@ struct cl_sim {
   // and the spill-free half on `stream` touch disjoint instances, so consecutive replays need
   // no cross-stream wait between them -- a replay's halves overlap the previous replay's
   // tail.  s2_live: stream2 may hold work `stream` has not waited for; every other ABI call
-  // joins it first (join_stream2, SIM_CHECK).  s_dirty: `stream` got work since the last
+  // joins it first (join_stream2, SimCall).  s_dirty: `stream` got work since the last
   // fork, so the next replay's stream2 half must wait for it.
   bool s2_live = false, s_dirty = true;
   int join_stream2() {
@@ -510,76 +467,28 @@ struct cl_sim {
   DevBuf<long long> d_pk_cnt, d_pk_bsum, d_pk_off;
   DevBuf<unsigned long long> d_rec2;
   DevBuf<unsigned long long> d_ihash;  // per-instance snapshot hashes (cl_instance_hashes)
-  hipEvent_t pk_ev[2] = {nullptr, nullptr};
-  bool pk_timed = false;
-  // per-snapshot batch statistics (cl_snapshot_stats, cl_stats.hip)
+  DevTimer<2> pk_tm;  // around the latest pack's kernels (cl_collect_time)
+  // the record tables next to the planes, for readers that walk the record words (cl_sample.h)
   std::vector<int32_t> word_ch;     // [N * rw] record word -> channel, -2 token word, -1 padding
   DevBuf<int32_t> d_word_ch;
   DevBuf<long long> d_hist_pre;     // int64 prefix of each channel's token history (upload_hist)
-  DevBuf<long long> d_stats;
-  hipEvent_t st_ev[2] = {nullptr, nullptr};
-  bool st_timed = false;
   int32_t n_cus = 0;
-  // snapshot outcome census (cl_snapshot_census, cl_census.hip)
-  DevBuf<CensusEntry> d_cs_table, d_cs_out;
-  DevBuf<uint32_t> d_cs_list;
-  DevBuf<unsigned long long> d_cs_info, d_cs_keys;
-  DevBuf<int32_t> d_cs_class, d_cs_rank;
   DevBuf<long long> d_pk_list;  // instance list of cl_collect_snapshot_list
-  hipEvent_t cs_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  int32_t cs_timed = 0;  // event pairs of the latest census (0: none has run)
-  // instance selection (cl_select_instances, cl_select.hip): verdict bitmap, block sums, output
-  DevBuf<unsigned long long> d_sel_bits, d_sel_info;
-  DevBuf<long long> d_sel_bsum, d_sel_out;
-  DevBuf<int32_t> d_sel_ticks;
-  hipEvent_t sel_ev[3] = {nullptr, nullptr, nullptr};  // start, evaluated, compacted
-  bool sel_timed = false;
-  // instance sets (cl_iset, cl_iset.hip): the sets alive (freed with the sim), the list upload and
-  // the count's scalar; the listing borrows the selection's compaction scratch
-  std::vector<cl_iset*> isets;
-  DevBuf<long long> d_is_list;
-  DevBuf<unsigned long long> d_is_count;
-  hipEvent_t is_ev[2] = {nullptr, nullptr};
-  bool is_timed = false;
-  // joint distribution of two snapshot quantities (cl_snapshot_crosstab, cl_crosstab.hip): the result words
-  DevBuf<long long> d_xt;
-  hipEvent_t xt_ev[2] = {nullptr, nullptr};
-  bool xt_timed = false;
+  // the batch analytics' scratch, timers and instance sets (cl_analytics.cpp)
+  Analytics* analytics = analytics_new(this);
   size_t hist_uploaded = (size_t)-1;  // history entries on the device
 
+  // What has an order: the streams drain, then the analytics go (a kernel may still read a set's
+  // bitmap before that), the launch events and the streams.  The buffers and timers free themselves
+  // after this body.
   ~cl_sim() {
     if (dev_ready) {
       (void)hipSetDevice(device);
       if (stream2) (void)hipStreamSynchronize(stream2);
       (void)hipStreamSynchronize(stream);
-      d_ops.release(); d_topo.release(); d_sched.release(); d_state.release(); d_regs.release();
-      d_snap_nod.release(); d_ch_slot.release(); d_snap_tick.release(); d_ovf.release(); d_fin_tok.release();
-      d_ovh.release(); d_spill_inst.release(); d_map.release(); d_rec_slot.release(); d_sched_pk.release(); d_hist.release();
-      d_sums.release();
-      d_trace.release(); d_trace_cnt.release(); d_ch_dest.release();
-      d_pk_tok.release(); d_pk_done.release(); d_pk_msg.release(); d_pk_cnt.release(); d_pk_bsum.release();
-      d_pk_off.release(); d_rec2.release(); d_ihash.release();
-      d_word_ch.release(); d_hist_pre.release(); d_stats.release();
-      d_cs_table.release(); d_cs_out.release(); d_cs_list.release(); d_cs_info.release(); d_cs_keys.release();
-      d_cs_class.release(); d_cs_rank.release(); d_pk_list.release();
-      d_sel_bits.release(); d_sel_info.release(); d_sel_bsum.release(); d_sel_out.release(); d_sel_ticks.release();
-      d_seeds.release(); d_dg_flag.release();
-      d_is_list.release(); d_is_count.release(); d_xt.release();
-      for (cl_iset* s : isets) s->bits.release();
-      for (auto& e : xt_ev)
-        if (e) (void)hipEventDestroy(e);
-      for (auto& e : is_ev)
-        if (e) (void)hipEventDestroy(e);
-      for (auto& e : dg_ev)
-        if (e) (void)hipEventDestroy(e);
-      for (auto& e : sel_ev)
-        if (e) (void)hipEventDestroy(e);
-      for (auto& e : cs_ev)
-        if (e) (void)hipEventDestroy(e);
-      for (auto& e : pk_ev)
-        if (e) (void)hipEventDestroy(e);
-      for (auto& e : st_ev)
-        if (e) (void)hipEventDestroy(e);
+    }
+    analytics_delete(analytics);  // (the sets still alive go with their sim)
+    if (dev_ready) {
       for (auto& e : ev_pool) {
         (void)hipEventDestroy(e.start);
         (void)hipEventDestroy(e.stop);
@@ -591,7 +500,6 @@ struct cl_sim {
       if (ev_join) (void)hipEventDestroy(ev_join);
       (void)hipStreamDestroy(stream);
     }
-    for (cl_iset* s : isets) delete s;  // (the sets still alive go with their sim)
   }
 
   int node_of(const char* id) const {
@@ -682,6 +590,12 @@ struct cl_sim {
     return CL_OK;
   }
 
+  // n_cus, asked of the device once (the delay generator's and the analytics' grids)
+  int cu_count() {
+    if (!n_cus) HIP_TRY(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device));
+    return CL_OK;
+  }
+
   int upload_topology() {
     const int n = (int)ids.size();
     const int W = 3 + max_in;
@@ -732,12 +646,10 @@ struct cl_sim {
       std::vector<int64_t>().swap(h_seeds);
       seeds_on_dev = true;
     }
-    for (auto& e : dg_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-    if (!n_cus) HIP_TRY(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device));
+    if ((rc = cu_count())) return rc;
     DeviceGen g;
     if ((rc = device_generate(device, stream, n_cus, seed_base, seed_list ? d_seeds.p : nullptr, n_inst, D, D,
-                              d_sched.p, d_dg_flag.p, dg_ev, &g)))
+                              d_sched.p, d_dg_flag.p, &dg_tm, &g)))
       return rc;
     *done = !g.overflow;
     if (g.overflow) return CL_OK;
@@ -1182,7 +1094,7 @@ struct cl_sim {
     HIP_TRY(hipSetDevice(device));
     // a pipelined replay's stream2 half (s2_live) writes results too: `stream` waits for it
     // first, whichever path reached here (cl_wait_snapshot took the lock without
-    // SIM_CHECK and could read snap_tick while the spill-capable half still ran)
+    // SimCall and could read snap_tick while the spill-capable half still ran)
     if (s2_live) {
       const int jrc = join_stream2();
       if (jrc) return jrc;
@@ -1386,8 +1298,6 @@ struct cl_sim {
         (rc = d_pk_cnt.ensure((size_t)n + 1)) || (rc = d_pk_bsum.ensure((size_t)(n / kScanItems + 1))) ||
         (rc = d_pk_off.ensure((size_t)n * C + 1)))
       return rc;
-    for (auto& e : pk_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
     PackParams p{};
     p.n_nodes = N;
     p.n_ch = C;
@@ -1409,7 +1319,7 @@ struct cl_sim {
     p.count = d_pk_cnt.p;
     p.bsum = d_pk_bsum.p;
     p.offsets = d_pk_off.p;
-    HIP_TRY(hipEventRecord(pk_ev[0], stream));
+    if ((rc = pk_tm.mark(0, stream))) return rc;
     int e = launch_pack_count(p, stream);
     if (e) return set_err(CL_E_DEVICE, "pack kernels: %s", hipGetErrorString((hipError_t)e));
     long long tot = 0;
@@ -1419,433 +1329,34 @@ struct cl_sim {
     p.msgs = d_pk_msg.p;
     e = launch_pack_fill(p, stream);
     if (e) return set_err(CL_E_DEVICE, "pack kernels: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipEventRecord(pk_ev[1], stream));
-    pk_timed = true;
+    if ((rc = pk_tm.mark(1, stream))) return rc;
+    pk_tm.done = 1;
     *total = tot;
     return CL_OK;
   }
 
-  // The opening of the analytics calls (stats, census, select): executes what is pending, makes the
-  // token histories resident, and describes the sample of snapshot sid over [lo, hi) and the planes
-  // its kernels walk (cl_sample.h).  `in` (the conditional calls): the instance set whose members
-  // the sample is taken from, made resident here.
-  int sample_begin(int32_t sid, int64_t lo, int64_t hi, SampleParams* s, cl_iset* in = nullptr) {
+  // The opening of the analytics calls (sim_records, cl_host.h): executes what is pending, makes the
+  // token histories resident, and describes the record planes a sample walk reads (cl_sample.h) and
+  // the tables next to them.
+  int records(SampleParams* s, SimTables* t) {
     int rc = flush();
     if (rc) return rc;
     if (!dev_ready) return set_err(CL_E_STATE, "nothing has run on the device yet");
     HIP_TRY(hipSetDevice(device));
-    if ((rc = upload_hist())) return rc;
-    if (in && (rc = iset_resident(in))) return rc;
-    if (!n_cus) HIP_TRY(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device));
-    *s = SampleParams{};
+    if ((rc = upload_hist()) || (rc = cu_count())) return rc;
     s->n_nodes = (int32_t)ids.size();
     s->n_ch = (int32_t)ch_dst.size();
     s->s_cap = s_cap;
     s->rw = lay.rw;
-    s->sid = sid;
     s->n_inst = n_inst;
     s->stride = stride;
-    s->lo = lo;
-    s->hi = hi;
     s->regs = d_regs.p;
     s->snap_tick = d_snap_tick.p;
     s->snap_nod = d_snap_nod.p;
     s->blocked = rec_blocked ? 1 : 0;
     // (the slot order of the replay that wrote the records; the dbg A/B's is the identity)
     s->inst_map = rec_blocked && rec_slot_gen != -2 ? d_map.p : nullptr;
-    // block-major records are in slot order: a sub-range's instances may sit in any tile
-    s->tile_lo = rec_blocked ? 0 : lo / kWave;
-    s->tile_hi = hi <= lo ? s->tile_lo : rec_blocked ? stride / kWave : (hi + kWave - 1) / kWave;
-    s->where = in ? in->bits.p : nullptr;  // (the conditional calls: only the set's members)
-    return CL_OK;
-  }
-
-  // Workgroups of a sample walk over `tiles` tiles whose workgroups need lds_bytes of LDS: a
-  // grid-stride grid sized to the chip, as many workgroups per CU as its LDS holds (up to 8).
-  // (one tile per wave where the batch is small: at 2^17 instances of C3, 4 tiles per wave --
-  // a quarter of the workgroups and of their closing atomics -- measured 0.117 against 0.069 ms)
-  int32_t sample_grid(int64_t tiles, int32_t lds_bytes) const {
-    return (int32_t)std::min<int64_t>((tiles + kWavesPerBlock - 1) / kWavesPerBlock,
-                                      (int64_t)stats_blocks_per_cu(lds_bytes) * std::max(n_cus, 1));
-  }
-
-  // cl_snapshot_stats: the statistics of snapshot sid over [lo, hi) into out[L.total_words]
-  // (arguments checked by the caller).  One kernel pass when the topology's N * rw record
-  // words fit the LDS accumulator budget (stats_pass_words), else one pass per range of chunks;
-  // the first pass also takes the per-instance totals.
-  int stats(int32_t sid, int64_t lo, int64_t hi, const StatsLayout& L, int64_t* out, cl_iset* in = nullptr) {
-    StatsParams p{};
-    int rc = sample_begin(sid, lo, hi, &p.s, in);
-    if (rc) return rc;
-    for (auto& e : st_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-    std::vector<long long> h((size_t)L.total_words, 0);
-    std::fill(h.begin() + L.min_begin, h.begin() + L.min_end, INT64_MAX);
-    std::fill(h.begin() + L.max_begin, h.begin() + L.max_end, INT64_MIN);
-    if ((rc = d_stats.ensure(h.size()))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_stats.p, h.data(), h.size() * sizeof(long long), hipMemcpyHostToDevice, stream));
-    p.word_ch = d_word_ch.p;
-    p.hist_off = d_hist.p;
-    p.hist_pre = d_hist_pre.p;
-    p.lay = L;
-    p.out = d_stats.p;
-    const int64_t tiles = p.s.tile_hi - p.s.tile_lo;
-    const int32_t budget = stats_pass_words((int32_t)L.tick_bins, (int32_t)L.msg_bins);
-    const int32_t n_chunks = stats_chunks(p.s.n_nodes, p.s.rw);
-    // the grid for the LDS of the largest pass (two workgroups per CU at the full budget)
-    const int32_t pass_words = std::min(budget, p.s.n_nodes * p.s.rw);
-    const int32_t blocks =
-        sample_grid(tiles, stats_lds_bytes(pass_words, (int32_t)L.tick_bins, (int32_t)L.msg_bins));
-    HIP_TRY(hipEventRecord(st_ev[0], stream));
-    for (int32_t c0 = 0; c0 < n_chunks && tiles > 0;) {
-      int32_t c1 = c0, words = 0;
-      while (c1 < n_chunks) {
-        const StatsChunk ch = stats_chunk(p.s.n_nodes, p.s.rw, c1);
-        if (words + ch.nv * ch.kw > budget) break;
-        words += ch.nv * ch.kw;
-        ++c1;
-      }
-      if (c1 == c0) return set_err(CL_E_LIMIT, "statistics accumulators of one chunk exceed the LDS budget");
-      p.chunk_lo = c0;
-      p.chunk_hi = c1;
-      p.totals = c0 == 0 ? 1 : 0;
-      p.acc_words = words;
-      const int e = launch_stats(p, blocks, stream);
-      if (e) return set_err(CL_E_DEVICE, "statistics kernel: %s", hipGetErrorString((hipError_t)e));
-      c0 = c1;
-    }
-    HIP_TRY(hipEventRecord(st_ev[1], stream));
-    st_timed = true;
-    HIP_TRY(hipMemcpyAsync(out, d_stats.p, h.size() * sizeof(long long), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return CL_OK;
-  }
-
-  // cl_snapshot_census (arguments checked by the caller): the classes of snapshot sid over
-  // [lo, hi), sorted, into *out; class_of[hi - lo] when asked for.  lds_slots: the workgroup
-  // table's entries, 0 for none.
-  int census(int32_t sid, int64_t lo, int64_t hi, int32_t lds_slots, std::vector<CensusEntry>* out,
-             int32_t* class_of, cl_census_info* info, cl_iset* in = nullptr) {
-    CensusParams p{};
-    int rc = sample_begin(sid, lo, hi, &p.s, in);
-    if (rc) return rc;
-    for (auto& e : cs_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-    const int64_t n = hi - lo;
-    out->clear();
-    *info = cl_census_info{};
-    if (n == 0) {
-      cs_timed = 0;
-      return CL_OK;
-    }
-    if (n > ((int64_t)1 << 29)) return set_err(CL_E_LIMIT, "census of more than 2^29 instances");
-    p.slots = 16;
-    while (p.slots < 2 * n) p.slots <<= 1;
-    if ((rc = d_cs_table.ensure((size_t)p.slots + 1)) || (rc = d_cs_list.ensure((size_t)n)) ||
-        (rc = d_cs_info.ensure(4)))
-      return rc;
-    if (class_of && ((rc = d_cs_keys.ensure((size_t)n)) || (rc = d_cs_class.ensure((size_t)n)))) return rc;
-    p.ch_slot = d_ch_slot.p;
-    p.hist_off = d_hist.p;
-    p.hist_val = d_hist.p + hist.size() + 1;
-    p.lds_slots = lds_slots;
-    p.staged = p.s.n_nodes * p.s.rw <= kCensusStageWords ? 1 : 0;
-    p.empty_key = kCensusEmptyKey;
-    // (tests move the marker onto a key that occurs, to run the extra entry's path)
-    if (const char* v = std::getenv("CLSNAP_CENSUS_EMPTY_KEY")) p.empty_key = std::strtoull(v, nullptr, 0);
-    p.table = d_cs_table.p;
-    p.list = d_cs_list.p;
-    p.info = d_cs_info.p;
-    p.keys = class_of ? d_cs_keys.p : nullptr;
-    p.class_of = class_of ? d_cs_class.p : nullptr;
-    const int32_t blocks = sample_grid(p.s.tile_hi - p.s.tile_lo, census_lds_bytes(lds_slots, p.staged != 0));
-    HIP_TRY(hipEventRecord(cs_ev[0], stream));
-    HIP_TRY(hipMemsetAsync(d_cs_info.p, 0, 4 * sizeof(unsigned long long), stream));
-    int e = launch_census_init(p, stream);
-    if (!e) e = launch_census_keys(p, blocks, stream);
-    if (e) return set_err(CL_E_DEVICE, "census kernels: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipEventRecord(cs_ev[1], stream));
-    unsigned long long h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, d_cs_info.p, sizeof h, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    cs_timed = 1;
-    const int64_t k = (int64_t)h[3];
-    if (k > n) return set_err(CL_E_DEVICE, "census: %lld classes of %lld instances", (long long)k, (long long)n);
-    info->instances = (int64_t)h[0], info->ok = (int64_t)h[1], info->sample = (int64_t)h[2], info->n_classes = k;
-    // ---- the k classes: compacted on the device, sorted here
-    std::vector<CensusEntry> got((size_t)k);
-    if (k > 0) {
-      if ((rc = d_cs_out.ensure((size_t)k))) return rc;
-      HIP_TRY(hipEventRecord(cs_ev[2], stream));
-      if ((e = launch_census_gather(p, k, d_cs_out.p, stream)))
-        return set_err(CL_E_DEVICE, "census kernels: %s", hipGetErrorString((hipError_t)e));
-      HIP_TRY(hipEventRecord(cs_ev[3], stream));
-      HIP_TRY(hipMemcpyAsync(got.data(), d_cs_out.p, (size_t)k * sizeof(CensusEntry), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      cs_timed = 2;
-    }
-    std::vector<int32_t> order((size_t)k);
-    for (int64_t j = 0; j < k; ++j) order[(size_t)j] = (int32_t)j;
-    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-      const CensusEntry &x = got[(size_t)a], &y = got[(size_t)b];
-      return x.count != y.count ? x.count > y.count : x.key < y.key;
-    });
-    out->resize((size_t)k);
-    for (int64_t j = 0; j < k; ++j) (*out)[(size_t)j] = got[(size_t)order[(size_t)j]];
-    if (!class_of) return CL_OK;
-    // ---- class_of: the ranks go back into the table, a lookup maps key -> rank per instance
-    std::vector<int32_t> rank((size_t)std::max<int64_t>(k, 1));
-    for (int64_t j = 0; j < k; ++j) rank[(size_t)order[(size_t)j]] = (int32_t)j;
-    if ((rc = d_cs_rank.ensure(rank.size()))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_cs_rank.p, rank.data(), rank.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(cs_ev[4], stream));
-    if ((e = launch_census_class_of(p, k, d_cs_rank.p, stream)))
-      return set_err(CL_E_DEVICE, "census kernels: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipEventRecord(cs_ev[5], stream));
-    HIP_TRY(hipMemcpyAsync(class_of, d_cs_class.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    cs_timed = 3;
-    return CL_OK;
-  }
-
-  // The scratch of the bitmap compaction (launch_select_compact) for p.words words and p.cap
-  // entries, shared by the selection and the listing of an instance set.
-  int compact_scratch(SelectParams* p, bool want_ticks) {
-    const int64_t n_blocks = (p->words + kSelBlockWords - 1) / kSelBlockWords;
-    int rc;
-    if ((rc = d_sel_bsum.ensure((size_t)n_blocks)) || (rc = d_sel_info.ensure(4)) ||
-        (rc = d_sel_out.ensure((size_t)std::max<int64_t>(p->cap, 1))))
-      return rc;
-    if (want_ticks && (rc = d_sel_ticks.ensure((size_t)std::max<int64_t>(p->cap, 1)))) return rc;
-    p->info = d_sel_info.p;
-    p->bsum = d_sel_bsum.p;
-    p->out = d_sel_out.p;
-    p->ticks = want_ticks ? d_sel_ticks.p : nullptr;
-    return CL_OK;
-  }
-
-  // cl_select_instances (arguments checked by the caller): the instances of the sample of
-  // snapshot sid over [lo, hi) that satisfy every clause, ascending, the first `cap` of them into
-  // insts (and their completion ticks into ticks).  Both stages are enqueued back to back; the
-  // host waits once, for the info, then copies the n_returned entries.
-  // `in` (cl_select_instances_in): the sample is that of the set's members.  `into`
-  // (cl_iset_from_clauses): the verdicts are written into that set's bitmap and stay there; nothing
-  // is listed (cap 0), the compaction only counts.  The verdict bitmap is never the one filtered on.
-  int select(int32_t sid, int64_t lo, int64_t hi, const cl_select_clause* clauses, int32_t n_clauses, int64_t* insts,
-             int32_t* ticks, int64_t cap, cl_select_info* info, cl_iset* in = nullptr, cl_iset* into = nullptr) {
-    SelectParams p{};
-    int rc = sample_begin(sid, lo, hi, &p.s, in);
-    if (rc) return rc;
-    for (auto& e : sel_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-    *info = cl_select_info{};
-    const int64_t n = hi - lo;
-    if (into && n == 0) return iset_clear(into);
-    if (n == 0) return CL_OK;
-    p.ch_slot = d_ch_slot.p;
-    p.hist_off = d_hist.p;
-    p.hist_val = d_hist.p + hist.size() + 1;
-    p.hist_pre = d_hist_pre.p;
-    p.staged = p.s.n_nodes * p.s.rw <= kCensusStageWords ? 1 : 0;
-    p.n_clauses = n_clauses;
-    for (int32_t q = 0; q < n_clauses; ++q) {
-      std::memcpy(&p.clause[q], &clauses[q], sizeof(SelectClause));
-      const int32_t f = clauses[q].field;
-      p.need_records |= f != SEL_TICK;
-      p.need_totals |= f == SEL_MSGS || f == SEL_INFLIGHT;
-      p.need_key |= f == SEL_KEY;
-    }
-    p.base = lo / kWave * kWave;
-    p.words = (hi - p.base + kWave - 1) / kWave;
-    p.cap = std::min(cap, n);
-    if (!into && (rc = d_sel_bits.ensure((size_t)p.words))) return rc;
-    if ((rc = compact_scratch(&p, ticks != nullptr))) return rc;
-    const int32_t blocks = sample_grid(p.s.tile_hi - p.s.tile_lo, select_lds_bytes(p.staged && p.need_records));
-    HIP_TRY(hipEventRecord(sel_ev[0], stream));
-    HIP_TRY(hipMemsetAsync(d_sel_info.p, 0, 4 * sizeof(unsigned long long), stream));
-    if (into) {
-      // the whole set is cleared: the words of [lo, hi) are a part of it
-      if ((rc = iset_clear(into))) return rc;
-      p.bitmap = into->bits.p + p.base / kWave;
-    } else {
-      p.bitmap = d_sel_bits.p;
-      // block-major: the lanes OR their bits in; instance-major: every word is stored
-      if (rec_blocked) HIP_TRY(hipMemsetAsync(d_sel_bits.p, 0, (size_t)p.words * sizeof(unsigned long long), stream));
-    }
-    int e = launch_select_eval(p, blocks, stream);
-    if (e) return set_err(CL_E_DEVICE, "select kernels: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipEventRecord(sel_ev[1], stream));
-    if ((e = launch_select_compact(p, stream)))
-      return set_err(CL_E_DEVICE, "select kernels: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipEventRecord(sel_ev[2], stream));
-    unsigned long long h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, d_sel_info.p, sizeof h, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    sel_timed = true;
-    if ((int64_t)h[3] > n)
-      return set_err(CL_E_DEVICE, "select: %lld matches of %lld instances", (long long)h[3], (long long)n);
-    info->instances = (int64_t)h[0], info->ok = (int64_t)h[1], info->sample = (int64_t)h[2];
-    info->n_match = (int64_t)h[3];
-    info->n_returned = std::min<int64_t>(info->n_match, cap);
-    if (info->n_returned > 0) {
-      const size_t k = (size_t)info->n_returned;
-      HIP_TRY(hipMemcpyAsync(insts, d_sel_out.p, k * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-      if (ticks) HIP_TRY(hipMemcpyAsync(ticks, d_sel_ticks.p, k * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-    }
-    return CL_OK;
-  }
-
-  // cl_snapshot_crosstab (arguments checked by the caller): the contingency table and joint
-  // moments of axes a and b over [lo, hi) into out[XT_CELLS + a->bins * b->bins].  One kernel; the
-  // walk is that of axis a's snapshot, the kernel takes axis b's planes from the same SampleParams.
-  int crosstab(int64_t lo, int64_t hi, const cl_crosstab_axis* a, const cl_crosstab_axis* b, int64_t* out,
-               cl_iset* in = nullptr) {
-    CrosstabParams p{};
-    int rc = sample_begin(a->sid, lo, hi, &p.s, in);
-    if (rc) return rc;
-    for (auto& e : xt_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-    std::memcpy(&p.a, a, sizeof p.a);
-    std::memcpy(&p.b, b, sizeof p.b);
-    const int32_t cells = a->bins * b->bins;
-    std::vector<long long> h((size_t)XT_CELLS + (size_t)cells, 0);
-    h[XT_MIN_A] = h[XT_MIN_B] = INT64_MAX;
-    h[XT_MAX_A] = h[XT_MAX_B] = INT64_MIN;
-    if ((rc = d_xt.ensure(h.size()))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_xt.p, h.data(), h.size() * sizeof(long long), hipMemcpyHostToDevice, stream));
-    p.ch_slot = d_ch_slot.p;
-    p.hist_off = d_hist.p;
-    p.hist_pre = d_hist_pre.p;
-    p.staged = p.s.n_nodes * p.s.rw <= kCensusStageWords ? 1 : 0;
-    p.out = d_xt.p;
-    const int64_t tiles = p.s.tile_hi - p.s.tile_lo;
-    const bool reads_records = a->field != SEL_TICK || b->field != SEL_TICK;
-    const int32_t blocks = sample_grid(tiles, crosstab_lds_bytes(cells, p.staged && reads_records));
-    HIP_TRY(hipEventRecord(xt_ev[0], stream));
-    if (tiles > 0) {
-      const int e = launch_crosstab(p, blocks, stream);
-      if (e) return set_err(CL_E_DEVICE, "crosstab kernel: %s", hipGetErrorString((hipError_t)e));
-    }
-    HIP_TRY(hipEventRecord(xt_ev[1], stream));
-    xt_timed = true;
-    HIP_TRY(hipMemcpyAsync(out, d_xt.p, h.size() * sizeof(long long), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return CL_OK;
-  }
-
-  // ---- instance sets (cl_iset) -------------------------------------------------------------------
-  int64_t iset_words() const { return stride / kWave; }
-
-  // The set as an all-zero bitmap on the device (allocated now if it never was).
-  int iset_clear(cl_iset* s) {
-    int rc = ensure_device();
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(device));
-    if ((rc = s->bits.ensure((size_t)iset_words()))) return rc;
-    HIP_TRY(hipMemsetAsync(s->bits.p, 0, (size_t)iset_words() * sizeof(unsigned long long), stream));
-    s->pending.clear();
-    s->resident = true;
-    return CL_OK;
-  }
-
-  int iset_time_begin() {
-    for (auto& e : is_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(is_ev[0], stream));
-    return CL_OK;
-  }
-  int iset_time_end() {
-    HIP_TRY(hipEventRecord(is_ev[1], stream));
-    is_timed = true;
-    return CL_OK;
-  }
-
-  // The first device use of a set: its bitmap is made, the list it was built from scattered into
-  // it (`timed`: as the kernels of cl_iset_time).
-  int iset_resident(cl_iset* s, bool timed = false) {
-    if (s->resident) return CL_OK;
-    std::vector<int64_t> list = std::move(s->pending);
-    const int rc = iset_scatter(s, list, timed);
-    if (rc) {  // (still the list it was: the next use tries again)
-      s->resident = false;
-      s->pending = std::move(list);
-    }
-    return rc;
-  }
-  int iset_scatter(cl_iset* s, const std::vector<int64_t>& list, bool timed) {
-    int rc = iset_clear(s);
-    if (rc || list.empty()) return rc;
-    if ((rc = d_is_list.ensure(list.size()))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_is_list.p, list.data(), list.size() * sizeof(long long), hipMemcpyHostToDevice, stream));
-    if (timed && (rc = iset_time_begin())) return rc;
-    const int e = launch_iset_scatter(d_is_list.p, (int64_t)list.size(), n_inst, s->bits.p, stream);
-    if (e) return set_err(CL_E_DEVICE, "instance set kernels: %s", hipGetErrorString((hipError_t)e));
-    if (timed && (rc = iset_time_end())) return rc;
-    HIP_TRY(hipStreamSynchronize(stream));  // (the list is the host's until the copy is done)
-    return CL_OK;
-  }
-
-  int iset_combine(cl_iset* dst, cl_iset* a, cl_iset* b, int32_t op) {
-    int rc;
-    if ((rc = iset_resident(a)) || (rc = iset_resident(b))) return rc;
-    // (dst is overwritten: only its bitmap is needed, unless it is an operand)
-    if (dst != a && dst != b && (rc = iset_clear(dst))) return rc;
-    if ((rc = iset_time_begin())) return rc;
-    const int e = launch_iset_combine(dst->bits.p, a->bits.p, b->bits.p, op, iset_words(), stream);
-    if (e) return set_err(CL_E_DEVICE, "instance set kernels: %s", hipGetErrorString((hipError_t)e));
-    if ((rc = iset_time_end())) return rc;
-    HIP_TRY(hipStreamSynchronize(stream));
-    return CL_OK;
-  }
-
-  int iset_count(cl_iset* s, int64_t lo, int64_t hi, int64_t* n) {
-    int rc = iset_resident(s);
-    if (rc) return rc;
-    *n = 0;
-    if (hi == lo) return CL_OK;
-    if ((rc = d_is_count.ensure(1))) return rc;
-    HIP_TRY(hipMemsetAsync(d_is_count.p, 0, sizeof(unsigned long long), stream));
-    if ((rc = iset_time_begin())) return rc;
-    const int e = launch_iset_count(s->bits.p, lo, hi, d_is_count.p, stream);
-    if (e) return set_err(CL_E_DEVICE, "instance set kernels: %s", hipGetErrorString((hipError_t)e));
-    if ((rc = iset_time_end())) return rc;
-    unsigned long long h = 0;
-    HIP_TRY(hipMemcpyAsync(&h, d_is_count.p, sizeof h, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if ((int64_t)h > hi - lo)
-      return set_err(CL_E_DEVICE, "instance set: %lld members of %lld instances", (long long)h, (long long)(hi - lo));
-    *n = (int64_t)h;
-    return CL_OK;
-  }
-
-  // The members in [lo, hi), ascending, the first `cap` of them: the words of the range, clipped
-  // to it, through the selection's compaction.
-  int iset_read(cl_iset* s, int64_t lo, int64_t hi, int64_t* insts, int64_t cap, int64_t* n_match) {
-    int rc = iset_resident(s);
-    if (rc) return rc;
-    *n_match = 0;
-    if (hi == lo) return CL_OK;
-    SelectParams p{};
-    p.base = lo / kWave * kWave;
-    p.words = (hi - p.base + kWave - 1) / kWave;
-    p.cap = std::min(cap, hi - lo);
-    if ((rc = d_sel_bits.ensure((size_t)p.words)) || (rc = compact_scratch(&p, false))) return rc;
-    p.bitmap = d_sel_bits.p;
-    HIP_TRY(hipMemsetAsync(d_sel_info.p, 0, 4 * sizeof(unsigned long long), stream));
-    if ((rc = iset_time_begin())) return rc;
-    int e = launch_iset_clip(d_sel_bits.p, s->bits.p, lo, hi, stream);
-    if (!e) e = launch_select_compact(p, stream);
-    if (e) return set_err(CL_E_DEVICE, "instance set kernels: %s", hipGetErrorString((hipError_t)e));
-    if ((rc = iset_time_end())) return rc;
-    unsigned long long h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, d_sel_info.p, sizeof h, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if ((int64_t)h[3] > hi - lo)
-      return set_err(CL_E_DEVICE, "instance set: %lld members of %lld instances", (long long)h[3], (long long)(hi - lo));
-    *n_match = (int64_t)h[3];
-    const int64_t k = std::min<int64_t>(*n_match, cap);
-    if (k > 0) HIP_TRY(hipMemcpy(insts, d_sel_out.p, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost));
+    *t = SimTables{d_ch_slot.p, d_word_ch.p, d_hist.p, d_hist.p + hist.size() + 1, d_hist_pre.p};
     return CL_OK;
   }
 
@@ -1871,6 +1382,49 @@ struct cl_sim {
 };
 
 // ---------------------------------------------------------------------------
+// What the analytics host layer reads a sim through (cl_host.h)
+// ---------------------------------------------------------------------------
+namespace clsnap {
+
+// Every ABI call but cl_rerun first joins a pipelined replay's stream2 half (cl_sim::s2_live).
+SimCall::SimCall(const cl_sim* sim, bool join) : rc(CL_OK) {
+  if (!sim) {
+    rc = set_err(CL_E_INVALID, "null cl_sim handle");
+    return;
+  }
+  sim->mu.lock();
+  locked_ = sim;
+  if (join && sim->s2_live) rc = const_cast<cl_sim*>(sim)->join_stream2();
+}
+SimCall::~SimCall() {
+  if (locked_) locked_->mu.unlock();
+}
+
+SimFacts sim_facts(const cl_sim* sim) {
+  return SimFacts{sim->n_inst, sim->stride, (int64_t)sim->ids.size(), (int64_t)sim->links.size(),
+                  sim->n_sids, sim->dev_ready, !sim->ops.empty() || sim->dev_ready};
+}
+
+int sim_device(cl_sim* sim, SimDevice* out) {
+  int rc = sim->ensure_device();
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(sim->device));
+  if ((rc = sim->cu_count())) return rc;
+  *out = SimDevice{sim->device, sim->stream, sim->n_cus};
+  return CL_OK;
+}
+
+int sim_records(cl_sim* sim, SimDevice* dev, SampleParams* s, SimTables* t) {
+  const int rc = sim->records(s, t);
+  if (!rc) *dev = SimDevice{sim->device, sim->stream, sim->n_cus};
+  return rc;
+}
+
+Analytics* sim_analytics(const cl_sim* sim) { return sim->analytics; }
+
+}  // namespace clsnap
+
+// ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
 extern "C" {
@@ -1889,17 +1443,6 @@ const char* cl_status_string(int32_t code) {
     default: return "unknown";
   }
 }
-
-// Every ABI call but cl_rerun first joins a pipelined replay's stream2 half (cl_sim::s2_live).
-#define SIM_CHECK_NOJOIN(s)                                         \
-  if (!(s)) return set_err(CL_E_INVALID, "null cl_sim handle");  \
-  std::lock_guard<std::recursive_mutex> sim_lock_((s)->mu)
-#define SIM_CHECK(s)                                                \
-  SIM_CHECK_NOJOIN(s);                                              \
-  if ((s)->s2_live) {                                               \
-    const int jrc_ = const_cast<cl_sim*>(s)->join_stream2();        \
-    if (jrc_) return jrc_;                                          \
-  }
 
 int cl_sim_create(int64_t n_instances, cl_sim** out) {
   if (!out || n_instances <= 0) return set_err(CL_E_INVALID, "n_instances must be > 0");
@@ -1925,7 +1468,7 @@ int cl_sim_destroy(cl_sim* sim) {
 }
 
 int cl_add_node(cl_sim* sim, const char* id, int64_t tokens) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!id) return set_err(CL_E_INVALID, "null id");
   if (sim->frozen) return set_err(CL_E_STATE, "AddNode after events started is not supported");
   if (sim->node_of(id) >= 0) return set_err(CL_E_DUPLICATE_NODE, "node %s already exists", id);
@@ -1940,7 +1483,7 @@ int cl_add_node(cl_sim* sim, const char* id, int64_t tokens) {
 }
 
 int cl_add_link(cl_sim* sim, const char* src, const char* dest) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   const int a = sim->node_of(src), b = sim->node_of(dest);
   if (a < 0) return set_err(CL_E_UNKNOWN_NODE, "Node %s does not exist", src ? src : "(null)");
   if (b < 0) return set_err(CL_E_UNKNOWN_NODE, "Node %s does not exist", dest ? dest : "(null)");
@@ -1953,7 +1496,7 @@ int cl_add_link(cl_sim* sim, const char* src, const char* dest) {
 }
 
 int cl_read_topology_text(cl_sim* sim, const char* text) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!text) return set_err(CL_E_INVALID, "null text");
   int64_t left = -1;
   for (const std::string& line : go_lines(text)) {
@@ -1978,21 +1521,21 @@ int cl_read_topology_text(cl_sim* sim, const char* text) {
 }
 
 int cl_read_topology_file(cl_sim* sim, const char* path) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   std::string text;
   if (!path || !read_file(path, &text)) return set_err(CL_E_IO, "cannot read %s", path ? path : "(null)");
   return cl_read_topology_text(sim, text.c_str());
 }
 
 int cl_set_device(cl_sim* sim, int32_t device_ordinal) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (sim->dev_ready) return set_err(CL_E_STATE, "device already selected");
   sim->device = device_ordinal;
   return CL_OK;
 }
 
 int cl_set_limits(cl_sim* sim, int32_t fifo_lds_slots, int64_t max_drain_ticks) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (max_drain_ticks < 0) return set_err(CL_E_INVALID, "max_drain_ticks must be >= 0");
   sim->max_drain = max_drain_ticks;
   if (fifo_lds_slots == 0) {  // automatic
@@ -2011,7 +1554,7 @@ int cl_set_limits(cl_sim* sim, int32_t fifo_lds_slots, int64_t max_drain_ticks) 
 }
 
 int cl_set_delay_go_seeds(cl_sim* sim, int64_t seed_base) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   sim->plan_ops = sim->plan_tried = -1;
   sim->go_seeds = true;
   sim->seed_base = seed_base;
@@ -2022,7 +1565,7 @@ int cl_set_delay_go_seeds(cl_sim* sim, int64_t seed_base) {
 }
 
 int cl_set_delay_go_seed_list(cl_sim* sim, const int64_t* seeds, int64_t n) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!seeds || n != sim->n_inst) return set_err(CL_E_INVALID, "the seed list must have one seed per instance");
   sim->plan_ops = sim->plan_tried = -1;
   sim->drop_seed_list();
@@ -2035,7 +1578,7 @@ int cl_set_delay_go_seed_list(cl_sim* sim, const int64_t* seeds, int64_t n) {
 }
 
 int cl_set_delay_generator(cl_sim* sim, int32_t mode) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (mode != CL_DELAYGEN_HOST && mode != CL_DELAYGEN_DEVICE) return set_err(CL_E_INVALID, "unknown delay generator %d", mode);
   if (mode == sim->delaygen) return CL_OK;
   sim->delaygen = mode;
@@ -2046,14 +1589,14 @@ int cl_set_delay_generator(cl_sim* sim, int32_t mode) {
 }
 
 int cl_delay_generator(cl_sim* sim, int32_t* mode) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!mode) return set_err(CL_E_INVALID, "null output");
   *mode = sim->go_seeds && sim->dev_draws >= 0 ? sim->dev_gen : -1;
   return CL_OK;
 }
 
 int cl_delay_gen_time(cl_sim* sim, double* device_ms, double* host_ms, int64_t* patched_rows) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!sim->dg_timed) return set_err(CL_E_STATE, "no delay generation has run");
   if (device_ms) *device_ms = sim->dg_device_ms;
   if (host_ms) *host_ms = sim->dg_host_ms;
@@ -2062,7 +1605,7 @@ int cl_delay_gen_time(cl_sim* sim, double* device_ms, double* host_ms, int64_t* 
 }
 
 int cl_set_delay_schedule(cl_sim* sim, const uint8_t* delays, int64_t draws_per_instance) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   sim->plan_ops = sim->plan_tried = -1;
   if (!delays || draws_per_instance <= 0) return set_err(CL_E_INVALID, "empty schedule");
   const size_t n = (size_t)(draws_per_instance * sim->n_inst);
@@ -2078,7 +1621,7 @@ int cl_set_delay_schedule(cl_sim* sim, const uint8_t* delays, int64_t draws_per_
 }
 
 int cl_send_tokens(cl_sim* sim, const char* src, const char* dest, int64_t n) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   int rc = sim->freeze();
   if (rc) return rc;
   const int a = sim->node_of(src);
@@ -2100,7 +1643,7 @@ int cl_send_tokens(cl_sim* sim, const char* src, const char* dest, int64_t n) {
 }
 
 int cl_start_snapshot(cl_sim* sim, const char* node, int32_t* out_sid) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   int rc = sim->freeze();
   if (rc) return rc;
   const int a = sim->node_of(node);
@@ -2114,7 +1657,7 @@ int cl_start_snapshot(cl_sim* sim, const char* node, int32_t* out_sid) {
 }
 
 int cl_tick(cl_sim* sim, int32_t n) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   int rc = sim->freeze();
   if (rc) return rc;
   if (n <= 0) return CL_OK;  // for i := 0; i < numTicks; ... (test_common.go:115)
@@ -2131,7 +1674,7 @@ int cl_tick(cl_sim* sim, int32_t n) {
 }
 
 int cl_drain(cl_sim* sim) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   int rc = sim->freeze();
   if (rc) return rc;
   const int64_t extra = 6;  // maxDelay + 1 (test_common.go:135-137)
@@ -2145,7 +1688,7 @@ int cl_drain(cl_sim* sim) {
 }
 
 int cl_read_events_text(cl_sim* sim, const char* text, int32_t* n_snapshots) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!text) return set_err(CL_E_INVALID, "null text");
   int32_t snaps = 0;
   for (const std::string& line : go_lines(text)) {
@@ -2176,26 +1719,26 @@ int cl_read_events_text(cl_sim* sim, const char* text, int32_t* n_snapshots) {
 }
 
 int cl_read_events_file(cl_sim* sim, const char* path, int32_t* n_snapshots) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   std::string text;
   if (!path || !read_file(path, &text)) return set_err(CL_E_IO, "cannot read %s", path ? path : "(null)");
   return cl_read_events_text(sim, text.c_str(), n_snapshots);
 }
 
 int cl_flush(cl_sim* sim) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   return sim->flush();
 }
 
 int cl_rerun(cl_sim* sim) {
-  SIM_CHECK_NOJOIN(sim);
+  SIM_CALL(sim, false);
   const int rc = sim->launch(true, false);
   if (rc == CL_OK) sim->notify_waiters();  // a blocked collector re-checks against the new run
   return rc;
 }
 
 int cl_replay_spill_free(cl_sim* sim, int32_t* on) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!on) return set_err(CL_E_INVALID, "null output");
   int rc = sim->sync();
   if (rc) return rc;
@@ -2204,7 +1747,7 @@ int cl_replay_spill_free(cl_sim* sim, int32_t* on) {
 }
 
 int cl_replay_split(cl_sim* sim, int64_t* spill_instances, int64_t* split_slot) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!spill_instances || !split_slot) return set_err(CL_E_INVALID, "null output");
   int rc = sim->sync();  // (a pending probe is evaluated here)
   if (rc) return rc;
@@ -2215,14 +1758,14 @@ int cl_replay_split(cl_sim* sim, int64_t* spill_instances, int64_t* split_slot) 
 }
 
 int cl_records_blocked(cl_sim* sim, int32_t* on) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!on) return set_err(CL_E_INVALID, "null output");
   *on = sim->rec_blocked ? 1 : 0;
   return CL_OK;
 }
 
 int cl_replay_mapped(cl_sim* sim, int32_t* on) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!on) return set_err(CL_E_INVALID, "null output");
   int rc = sim->sync();  // (a pending map probe is evaluated here)
   if (rc) return rc;
@@ -2231,12 +1774,12 @@ int cl_replay_mapped(cl_sim* sim, int32_t* on) {
 }
 
 int cl_synchronize(cl_sim* sim) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   return sim->sync();
 }
 
 int cl_set_exec_engine(cl_sim* sim, int32_t engine) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (engine != CL_ENGINE_AUTO && engine != CL_ENGINE_NODES && engine != CL_ENGINE_LANES)
     return set_err(CL_E_INVALID, "unknown exec engine %d", engine);
   if (engine != sim->engine) {
@@ -2249,14 +1792,14 @@ int cl_set_exec_engine(cl_sim* sim, int32_t engine) {
 }
 
 int cl_exec_engine(cl_sim* sim, int32_t* engine) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!engine) return set_err(CL_E_INVALID, "null output");
   *engine = sim->last_engine;
   return CL_OK;
 }
 
 int cl_lanes_compile_check(cl_sim* sim, double* compile_ms, char* log, int64_t log_cap) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   int rc = sim->freeze();
   if (rc) return rc;
   if (sim->ids.empty()) return set_err(CL_E_STATE, "the topology has no nodes");
@@ -2284,7 +1827,7 @@ int cl_jit_stats(double* compile_ms, int64_t* compiles) {
 }
 
 int cl_debug_poison_outputs(cl_sim* sim) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!sim->dev_ready || !sim->d_regs.p) return CL_OK;
   HIP_TRY(hipSetDevice(sim->device));
   const int n = (int)sim->ids.size();
@@ -2298,7 +1841,7 @@ int cl_debug_poison_outputs(cl_sim* sim) {
 }
 
 int cl_last_kernel_ms(cl_sim* sim, double* ms) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!ms) return set_err(CL_E_INVALID, "null output");
   if (!sim->timed) return set_err(CL_E_STATE, "no kernel has run");
   int rc = sim->sync();
@@ -2310,7 +1853,7 @@ int cl_last_kernel_ms(cl_sim* sim, double* ms) {
 }
 
 int cl_kernel_time(cl_sim* sim, double* total_ms, int64_t* launches) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!total_ms || !launches) return set_err(CL_E_INVALID, "null output");
   int rc = sim->sync();
   if (rc) return rc;
@@ -2323,13 +1866,13 @@ int cl_kernel_time(cl_sim* sim, double* total_ms, int64_t* launches) {
 }
 
 int cl_num_nodes(const cl_sim* sim, int32_t* n) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   *n = (int32_t)sim->ids.size();
   return CL_OK;
 }
 
 int cl_node_id(const cl_sim* sim, int32_t rank, const char** id) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!sim->frozen) {
     int rc = const_cast<cl_sim*>(sim)->freeze();
     if (rc) return rc;
@@ -2340,13 +1883,13 @@ int cl_node_id(const cl_sim* sim, int32_t rank, const char** id) {
 }
 
 int cl_num_channels(const cl_sim* sim, int32_t* n) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   *n = (int32_t)sim->links.size();
   return CL_OK;
 }
 
 int cl_channel(const cl_sim* sim, int32_t ch, int32_t* src_rank, int32_t* dest_rank) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!sim->frozen) {
     int rc = const_cast<cl_sim*>(sim)->freeze();
     if (rc) return rc;
@@ -2358,41 +1901,37 @@ int cl_channel(const cl_sim* sim, int32_t ch, int32_t* src_rank, int32_t* dest_r
 }
 
 int cl_num_snapshots(const cl_sim* sim, int32_t* n) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   *n = sim->n_sids;
   return CL_OK;
 }
 
 int cl_num_instances(const cl_sim* sim, int64_t* n) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   *n = sim->n_inst;
   return CL_OK;
 }
 
 int cl_delay_draws_needed(const cl_sim* sim, int64_t* draws) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   *draws = sim->draws_needed();
   return CL_OK;
 }
 
 int cl_device_bytes(const cl_sim* sim, int64_t* bytes) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   int64_t b = 0;
   b += sim->d_ops.n * sizeof(Op) + sim->d_topo.n * 4 + sim->d_sched.n + sim->d_sched_pk.n * 4 + sim->d_state.n * 4 + sim->d_regs.n * 4;
   b += sim->d_snap_nod.n * 4 + sim->d_snap_tick.n * 4 + sim->d_ovf.n * 4;
   b += sim->d_ovh.n * 4 + sim->d_hist.n * 4 + sim->d_sums.n * 8 + sim->d_fin_tok.n * 4;
-  b += sim->d_sel_bits.n * 8 + sim->d_sel_info.n * 8 + sim->d_sel_bsum.n * 8 + sim->d_sel_out.n * 8 +
-       sim->d_sel_ticks.n * 4;  // (the selection's scratch, once a selection has run)
   b += sim->d_seeds.n * 8 + sim->d_dg_flag.n * 8;  // (the seed list and the device generator's flagged rows)
-  for (const cl_iset* s : sim->isets) b += s->bits.n * 8;  // (the instance sets alive, and their list upload)
-  b += sim->d_is_list.n * 8 + sim->d_is_count.n * 8;
-  b += sim->d_xt.n * 8;  // (the crosstab's result words, once a crosstab has run)
+  b += analytics_device_bytes(sim->analytics);  // (selection scratch, sets alive, crosstab words)
   *bytes = b;
   return CL_OK;
 }
 
 int cl_get_status(cl_sim* sim, int32_t* out) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   int rc = sim->fetch();
   if (rc) return rc;
   for (int64_t i = 0; i < sim->n_inst; ++i) out[i] = sim->reg(i, R_STATUS);
@@ -2400,7 +1939,7 @@ int cl_get_status(cl_sim* sim, int32_t* out) {
 }
 
 int cl_get_time(cl_sim* sim, int32_t* out) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   int rc = sim->fetch();
   if (rc) return rc;
   for (int64_t i = 0; i < sim->n_inst; ++i) out[i] = sim->reg(i, R_TIME);
@@ -2408,7 +1947,7 @@ int cl_get_time(cl_sim* sim, int32_t* out) {
 }
 
 int cl_node_tokens(cl_sim* sim, int64_t inst, int64_t* out) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (inst < 0 || inst >= sim->n_inst) return set_err(CL_E_INVALID, "instance out of range");
   int rc = sim->fetch();
   if (rc) return rc;
@@ -2418,7 +1957,7 @@ int cl_node_tokens(cl_sim* sim, int64_t inst, int64_t* out) {
 }
 
 int cl_snapshot_tick(cl_sim* sim, int32_t sid, int64_t inst, int32_t* tick) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (inst < 0 || inst >= sim->n_inst || sid < 0 || sid >= sim->n_sids)
     return set_err(CL_E_INVALID, "snapshot/instance out of range");
   int rc = sim->fetch();
@@ -2429,7 +1968,7 @@ int cl_snapshot_tick(cl_sim* sim, int32_t sid, int64_t inst, int32_t* tick) {
 
 int cl_collect_snapshot(cl_sim* sim, int32_t sid, int64_t inst, int64_t* tokens, int64_t* msg_offsets,
                         int64_t* msg_tokens, int64_t msg_cap) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (inst < 0 || inst >= sim->n_inst || sid < 0 || sid >= sim->n_sids)
     return set_err(CL_E_INVALID, "snapshot/instance out of range");
   int rc = sim->fetch();
@@ -2456,7 +1995,7 @@ int cl_collect_snapshot(cl_sim* sim, int32_t sid, int64_t inst, int64_t* tokens,
 }
 
 int cl_poll_snapshot(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, int64_t* n_complete) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!n_complete) return set_err(CL_E_INVALID, "null output");
   if (sid < 0 || sid >= sim->n_sids || inst_lo < 0 || inst_hi > sim->n_inst || inst_lo > inst_hi)
     return set_err(CL_E_INVALID, "snapshot/instance range out of range");
@@ -2505,7 +2044,7 @@ int cl_wait_snapshot(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi,
 
 int cl_collect_snapshot_range(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, int64_t* tokens,
                               int32_t* complete, int64_t* msg_offsets, int64_t* msg_tokens, int64_t msg_cap) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (sid < 0 || sid >= sim->n_sids || inst_lo < 0 || inst_hi > sim->n_inst || inst_lo > inst_hi)
     return set_err(CL_E_INVALID, "snapshot/instance range out of range");
   int64_t tot = 0;
@@ -2553,7 +2092,7 @@ static int copy_packed(cl_sim* sim, int64_t rows, int64_t tot, int32_t* tokens, 
 int cl_collect_snapshot_packed(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, int32_t* tokens,
                                int32_t* complete, int64_t* msg_offsets, int32_t* msg_tokens, int64_t msg_cap,
                                int64_t* n_msgs) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (sid < 0 || sid >= sim->n_sids || inst_lo < 0 || inst_hi > sim->n_inst || inst_lo > inst_hi)
     return set_err(CL_E_INVALID, "snapshot/instance range out of range");
   int64_t tot = 0;
@@ -2565,7 +2104,7 @@ int cl_collect_snapshot_packed(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_
 int cl_collect_snapshot_list(cl_sim* sim, int32_t sid, const int64_t* insts, int64_t n, int32_t* tokens,
                              int32_t* complete, int64_t* msg_offsets, int32_t* msg_tokens, int64_t msg_cap,
                              int64_t* n_msgs) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (sid < 0 || sid >= sim->n_sids || n < 0 || (n > 0 && !insts))
     return set_err(CL_E_INVALID, "snapshot id or instance list out of range");
   for (int64_t r = 0; r < n; ++r)
@@ -2579,389 +2118,22 @@ int cl_collect_snapshot_list(cl_sim* sim, int32_t sid, const int64_t* insts, int
 }
 
 int cl_collect_time(cl_sim* sim, double* device_ms) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!device_ms) return set_err(CL_E_INVALID, "null output");
-  if (!sim->pk_timed) return set_err(CL_E_STATE, "no packed collect has run");
+  if (!sim->pk_tm.done) return set_err(CL_E_STATE, "no packed collect has run");
   HIP_TRY(hipStreamSynchronize(sim->stream));
-  float f = 0.f;
-  HIP_TRY(hipEventElapsedTime(&f, sim->pk_ev[0], sim->pk_ev[1]));
-  *device_ms = f;
-  return CL_OK;
-}
-
-// The arguments every call over a sample shares (after the call's own): the instance range, a sim
-// that has run something, the snapshot id.
-static int sample_args_ok(const cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi) {
-  if (inst_lo < 0 || inst_hi > sim->n_inst || inst_lo > inst_hi)
-    return set_err(CL_E_INVALID, "instance range out of range");
-  if (sim->ops.empty() && !sim->dev_ready) return set_err(CL_E_STATE, "nothing has run yet: no event was issued");
-  if (sid < 0 || sid >= sim->n_sids) return set_err(CL_E_INVALID, "snapshot id out of range");
-  return CL_OK;
-}
-
-// The set of a conditional call (cl_*_in): given, and this sim's.
-static int iset_arg_ok(const cl_sim* sim, const cl_iset* in) {
-  if (!in) return set_err(CL_E_INVALID, "null instance set");
-  if (in->sim != sim) return set_err(CL_E_INVALID, "the instance set belongs to another sim");
-  return CL_OK;
-}
-
-static_assert(sizeof(cl_stats_layout) == sizeof(StatsLayout), "cl_stats_layout mirrors StatsLayout");
-
-static int stats_spec_ok(const cl_stats_spec* spec) {
-  if (!spec) return set_err(CL_E_INVALID, "null statistics spec");
-  if (spec->tick_bins < 1 || spec->tick_bins > CL_STATS_MAX_TICK_BINS || spec->msg_bins < 1 ||
-      spec->msg_bins > CL_STATS_MAX_MSG_BINS)
-    return set_err(CL_E_INVALID, "statistics spec: 1 <= tick_bins <= %d, 1 <= msg_bins <= %d", CL_STATS_MAX_TICK_BINS,
-                   CL_STATS_MAX_MSG_BINS);
-  return CL_OK;
-}
-
-int cl_stats_layout_of(const cl_sim* sim, const cl_stats_spec* spec, cl_stats_layout* out) {
-  SIM_CHECK_NOJOIN(sim);
-  if (!out) return set_err(CL_E_INVALID, "null output");
-  int rc = stats_spec_ok(spec);
-  if (rc) return rc;
-  const StatsLayout L = stats_layout((int64_t)sim->ids.size(), (int64_t)sim->links.size(), spec->tick_lo,
-                                     spec->tick_bins, spec->msg_bins);
-  std::memcpy(out, &L, sizeof L);
-  return CL_OK;
-}
-
-// cl_snapshot_stats, and cl_snapshot_stats_in with its set (`conditional`).
-static int stats_call(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, bool conditional, const cl_iset* in,
-                      const cl_stats_spec* spec, int64_t* out, int64_t out_words) {
-  SIM_CHECK(sim);
-  // every argument is checked before any device work
-  int rc = conditional ? iset_arg_ok(sim, in) : CL_OK;
-  if (rc) return rc;
-  if ((rc = stats_spec_ok(spec))) return rc;
-  if (!out) return set_err(CL_E_INVALID, "null output");
-  if ((rc = sample_args_ok(sim, sid, inst_lo, inst_hi))) return rc;
-  const StatsLayout L = stats_layout((int64_t)sim->ids.size(), (int64_t)sim->links.size(), spec->tick_lo,
-                                     spec->tick_bins, spec->msg_bins);
-  if (out_words < L.total_words)
-    return set_err(CL_E_LIMIT, "out_words %lld < %lld words of the statistics layout", (long long)out_words,
-                   (long long)L.total_words);
-  return sim->stats(sid, inst_lo, inst_hi, L, out, const_cast<cl_iset*>(in));
-}
-
-int cl_snapshot_stats(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_stats_spec* spec,
-                      int64_t* out, int64_t out_words) {
-  return stats_call(sim, sid, inst_lo, inst_hi, false, nullptr, spec, out, out_words);
-}
-
-int cl_snapshot_stats_in(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_iset* in,
-                         const cl_stats_spec* spec, int64_t* out, int64_t out_words) {
-  return stats_call(sim, sid, inst_lo, inst_hi, true, in, spec, out, out_words);
-}
-
-int cl_stats_time(cl_sim* sim, double* device_ms) {
-  SIM_CHECK(sim);
-  if (!device_ms) return set_err(CL_E_INVALID, "null output");
-  if (!sim->st_timed) return set_err(CL_E_STATE, "no statistics call has run");
-  HIP_TRY(hipStreamSynchronize(sim->stream));
-  float f = 0.f;
-  HIP_TRY(hipEventElapsedTime(&f, sim->st_ev[0], sim->st_ev[1]));
-  *device_ms = f;
-  return CL_OK;
-}
-
-static_assert(sizeof(cl_census_class) == sizeof(CensusEntry) && sizeof(CensusEntry) == 32,
-              "cl_census_class mirrors CensusEntry");
-
-// cl_snapshot_census, and cl_snapshot_census_in with its set (`conditional`).
-static int census_call(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, bool conditional,
-                       const cl_iset* in, const cl_census_spec* spec, cl_census_class* classes, int32_t* class_of,
-                       cl_census_info* info) {
-  SIM_CHECK(sim);
-  // every argument is checked before any device work
-  if (conditional)
-    if (const int rc = iset_arg_ok(sim, in)) return rc;
-  if (!spec || !info) return set_err(CL_E_INVALID, "null census spec or info");
-  const int32_t ls = spec->lds_slots;
-  if (spec->max_classes < 0 ||
-      !(ls == 0 || ls == -1 || (ls >= kCensusMinLdsSlots && ls <= kCensusMaxLdsSlots && (ls & (ls - 1)) == 0)))
-    return set_err(CL_E_INVALID, "census spec: max_classes >= 0; lds_slots 0, -1 or a power of two in [%d, %d]",
-                   kCensusMinLdsSlots, kCensusMaxLdsSlots);
-  if (spec->max_classes > 0 && !classes) return set_err(CL_E_INVALID, "null classes with max_classes > 0");
-  if (const int rc = sample_args_ok(sim, sid, inst_lo, inst_hi)) return rc;
-  std::vector<CensusEntry> got;
-  const int32_t lds_slots = ls == 0 ? kCensusAutoLdsSlots : ls < 0 ? 0 : ls;
-  const int rc = sim->census(sid, inst_lo, inst_hi, lds_slots, &got, class_of, info, const_cast<cl_iset*>(in));
-  if (rc) return rc;
-  info->n_returned = std::min<int64_t>(info->n_classes, spec->max_classes);
-  if (info->n_returned > 0) std::memcpy(classes, got.data(), (size_t)info->n_returned * sizeof(cl_census_class));
-  return CL_OK;
-}
-
-int cl_snapshot_census(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_census_spec* spec,
-                       cl_census_class* classes, int32_t* class_of, cl_census_info* info) {
-  return census_call(sim, sid, inst_lo, inst_hi, false, nullptr, spec, classes, class_of, info);
-}
-
-int cl_snapshot_census_in(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_iset* in,
-                          const cl_census_spec* spec, cl_census_class* classes, int32_t* class_of,
-                          cl_census_info* info) {
-  return census_call(sim, sid, inst_lo, inst_hi, true, in, spec, classes, class_of, info);
-}
-
-int cl_census_time(cl_sim* sim, double* device_ms) {
-  SIM_CHECK(sim);
-  if (!device_ms) return set_err(CL_E_INVALID, "null output");
-  if (!sim->cs_timed) return set_err(CL_E_STATE, "no census call has run");
-  HIP_TRY(hipStreamSynchronize(sim->stream));
-  double ms = 0;
-  for (int32_t q = 0; q < sim->cs_timed; ++q) {  // key pass, gather, class_of: the host's sort lies between
-    float f = 0.f;
-    HIP_TRY(hipEventElapsedTime(&f, sim->cs_ev[2 * q], sim->cs_ev[2 * q + 1]));
-    ms += f;
-  }
-  *device_ms = ms;
-  return CL_OK;
-}
-
-static_assert(sizeof(cl_select_clause) == sizeof(SelectClause) && sizeof(SelectClause) == 32,
-              "cl_select_clause mirrors SelectClause");
-static_assert(CL_SELECT_MAX_CLAUSES == kSelMaxClauses && CL_SEL_KEY == SEL_KEY && CL_SEL_NOT == kSelNot,
-              "CL_SEL_* mirror cl_engine.h");
-
-// cl_select_instances; cl_select_instances_in with its set (`conditional`); cl_iset_from_clauses
-// with the set that takes the matches (`into`: no list, cap 0).
-static int select_call(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, bool conditional, const cl_iset* in,
-                       const cl_select_clause* clauses, int32_t n_clauses, int64_t* insts, int32_t* ticks,
-                       int64_t cap, cl_select_info* info, cl_iset* into) {
-  // every argument is checked before any device work
-  if (conditional)
-    if (const int rc = iset_arg_ok(sim, in)) return rc;
-  if (!info) return set_err(CL_E_INVALID, "null select info");
-  if (n_clauses < 0 || n_clauses > CL_SELECT_MAX_CLAUSES || (n_clauses > 0 && !clauses))
-    return set_err(CL_E_INVALID, "select: 0 <= n_clauses <= %d, with a clause array", CL_SELECT_MAX_CLAUSES);
-  const int64_t N = (int64_t)sim->ids.size(), Cn = (int64_t)sim->links.size();
-  for (int32_t q = 0; q < n_clauses; ++q) {
-    const cl_select_clause& z = clauses[q];
-    if (z.field < 0 || z.field >= SEL_NUM_FIELDS || (z.flags & ~CL_SEL_NOT) || z.reserved)
-      return set_err(CL_E_INVALID, "select clause %d: unknown field or flag bits, or non-zero reserved", q);
-    const int64_t bound = z.field == CL_SEL_NODE ? N : z.field == CL_SEL_CH_MSGS || z.field == CL_SEL_CH_TOK ? Cn : 1;
-    if (z.index < 0 || z.index >= bound) return set_err(CL_E_INVALID, "select clause %d: index %d out of range", q, z.index);
-  }
-  if (cap < 0 || (cap > 0 && !insts)) return set_err(CL_E_INVALID, "select: cap >= 0, with an index array when cap > 0");
-  if (const int rc = sample_args_ok(sim, sid, inst_lo, inst_hi)) return rc;
-  return sim->select(sid, inst_lo, inst_hi, clauses, n_clauses, insts, ticks, cap, info, const_cast<cl_iset*>(in), into);
-}
-
-int cl_select_instances(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_select_clause* clauses,
-                        int32_t n_clauses, int64_t* insts, int32_t* ticks, int64_t cap, cl_select_info* info) {
-  SIM_CHECK(sim);
-  return select_call(sim, sid, inst_lo, inst_hi, false, nullptr, clauses, n_clauses, insts, ticks, cap, info, nullptr);
-}
-
-int cl_select_instances_in(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_iset* in,
-                           const cl_select_clause* clauses, int32_t n_clauses, int64_t* insts, int32_t* ticks,
-                           int64_t cap, cl_select_info* info) {
-  SIM_CHECK(sim);
-  return select_call(sim, sid, inst_lo, inst_hi, true, in, clauses, n_clauses, insts, ticks, cap, info, nullptr);
-}
-
-static_assert(sizeof(cl_crosstab_axis) == sizeof(CrosstabAxis) && sizeof(CrosstabAxis) == 32,
-              "cl_crosstab_axis mirrors CrosstabAxis");
-static_assert(CL_CROSSTAB_MAX_BINS == kXtMaxBins && CL_CROSSTAB_MAX_CELLS == kXtMaxCells && CL_XT_SUM_A == XT_SUM_A &&
-                  CL_XT_MIN_A == XT_MIN_A && CL_XT_MAX_A == XT_MAX_A && CL_XT_CELLS == XT_CELLS,
-              "CL_CROSSTAB_* and CL_XT_* mirror cl_engine.h");
-
-static int crosstab_axis_ok(const cl_sim* sim, const cl_crosstab_axis* z, const char* name) {
-  if (!z) return set_err(CL_E_INVALID, "crosstab: null axis %s", name);
-  // (CL_SEL_KEY is a select field only: a hash is not binnable)
-  if (z->field < CL_SEL_TICK || z->field > CL_SEL_CH_TOK)
-    return set_err(CL_E_INVALID, "crosstab axis %s: field %d is not one of CL_SEL_TICK .. CL_SEL_CH_TOK", name, z->field);
-  const int64_t N = (int64_t)sim->ids.size(), Cn = (int64_t)sim->links.size();
-  const int64_t bound = z->field == CL_SEL_NODE ? N : z->field == CL_SEL_CH_MSGS || z->field == CL_SEL_CH_TOK ? Cn : 1;
-  if (z->index < 0 || z->index >= bound) return set_err(CL_E_INVALID, "crosstab axis %s: index %d out of range", name, z->index);
-  if (z->bins < 1 || z->bins > CL_CROSSTAB_MAX_BINS || z->width < 1)
-    return set_err(CL_E_INVALID, "crosstab axis %s: 1 <= bins <= %d, width >= 1", name, CL_CROSSTAB_MAX_BINS);
-  return CL_OK;
-}
-
-// cl_snapshot_crosstab, and cl_snapshot_crosstab_in with its set (`conditional`).
-static int crosstab_call(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, bool conditional, const cl_iset* in,
-                         const cl_crosstab_axis* a, const cl_crosstab_axis* b, int64_t* out, int64_t out_words) {
-  SIM_CHECK(sim);
-  // every argument is checked before any device work
-  int rc = conditional ? iset_arg_ok(sim, in) : CL_OK;
-  if (rc) return rc;
-  if ((rc = crosstab_axis_ok(sim, a, "a")) || (rc = crosstab_axis_ok(sim, b, "b"))) return rc;
-  const int64_t cells = (int64_t)a->bins * (int64_t)b->bins;
-  if (cells > CL_CROSSTAB_MAX_CELLS)
-    return set_err(CL_E_INVALID, "crosstab: %lld cells, bins_a * bins_b <= %d", (long long)cells, CL_CROSSTAB_MAX_CELLS);
-  if (!out) return set_err(CL_E_INVALID, "null output");
-  if ((rc = sample_args_ok(sim, a->sid, inst_lo, inst_hi))) return rc;
-  if (b->sid < 0 || b->sid >= sim->n_sids) return set_err(CL_E_INVALID, "snapshot id out of range");
-  if (out_words < CL_XT_CELLS + cells)
-    return set_err(CL_E_LIMIT, "out_words %lld < %lld words of the crosstab", (long long)out_words,
-                   (long long)(CL_XT_CELLS + cells));
-  return sim->crosstab(inst_lo, inst_hi, a, b, out, const_cast<cl_iset*>(in));
-}
-
-int cl_snapshot_crosstab(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_crosstab_axis* a,
-                         const cl_crosstab_axis* b, int64_t* out, int64_t out_words) {
-  return crosstab_call(sim, inst_lo, inst_hi, false, nullptr, a, b, out, out_words);
-}
-
-int cl_snapshot_crosstab_in(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_iset* in, const cl_crosstab_axis* a,
-                            const cl_crosstab_axis* b, int64_t* out, int64_t out_words) {
-  return crosstab_call(sim, inst_lo, inst_hi, true, in, a, b, out, out_words);
-}
-
-int cl_crosstab_time(cl_sim* sim, double* device_ms) {
-  SIM_CHECK(sim);
-  if (!device_ms) return set_err(CL_E_INVALID, "null output");
-  if (!sim->xt_timed) return set_err(CL_E_STATE, "no crosstab call has run");
-  HIP_TRY(hipStreamSynchronize(sim->stream));
-  float f = 0.f;
-  HIP_TRY(hipEventElapsedTime(&f, sim->xt_ev[0], sim->xt_ev[1]));
-  *device_ms = f;
-  return CL_OK;
-}
-
-// ---- instance sets ------------------------------------------------------------------------------
-static_assert(CL_ISET_AND == ISET_AND && CL_ISET_OR == ISET_OR && CL_ISET_ANDNOT == ISET_ANDNOT,
-              "CL_ISET_* mirror cl_engine.h");
-
-static cl_iset* iset_new(cl_sim* sim) {
-  cl_iset* s = new cl_iset();
-  s->sim = sim;
-  sim->isets.push_back(s);
-  return s;
-}
-
-static void iset_delete(cl_iset* s) {
-  cl_sim* sim = s->sim;
-  sim->isets.erase(std::remove(sim->isets.begin(), sim->isets.end(), s), sim->isets.end());
-  if (s->bits.p) {
-    (void)hipSetDevice(sim->device);
-    (void)hipStreamSynchronize(sim->stream);  // (a kernel may still read the bitmap)
-    s->bits.release();
-  }
-  delete s;
-}
-
-int cl_iset_from_clauses(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_select_clause* clauses,
-                         int32_t n_clauses, cl_iset** out, cl_select_info* info) {
-  SIM_CHECK(sim);
-  if (!out) return set_err(CL_E_INVALID, "null instance set output");
-  cl_iset* s = iset_new(sim);
-  const int rc = select_call(sim, sid, inst_lo, inst_hi, false, nullptr, clauses, n_clauses, nullptr, nullptr, 0, info, s);
-  if (rc) {
-    iset_delete(s);
-    return rc;
-  }
-  *out = s;
-  return CL_OK;
-}
-
-int cl_iset_from_list(cl_sim* sim, const int64_t* insts, int64_t n, cl_iset** out) {
-  SIM_CHECK(sim);
-  if (!out || n < 0 || (n > 0 && !insts)) return set_err(CL_E_INVALID, "instance list or set output out of range");
-  for (int64_t r = 0; r < n; ++r)
-    if (insts[r] < 0 || insts[r] >= sim->n_inst)
-      return set_err(CL_E_INVALID, "instance list entry %lld: instance %lld out of range", (long long)r,
-                     (long long)insts[r]);
-  cl_iset* s = iset_new(sim);
-  s->pending.assign(insts, insts + n);
-  // the scatter runs now when the sim already has its device, else with the set's first device use
-  if (sim->dev_ready) {
-    const int rc = sim->iset_resident(s, true);
-    if (rc) {
-      iset_delete(s);
-      return rc;
-    }
-  }
-  *out = s;
-  return CL_OK;
-}
-
-int cl_iset_combine(cl_iset* dst, const cl_iset* a, const cl_iset* b, int32_t op) {
-  if (!dst || !a || !b) return set_err(CL_E_INVALID, "null instance set");
-  cl_sim* sim = dst->sim;
-  SIM_CHECK(sim);
-  if (a->sim != sim || b->sim != sim) return set_err(CL_E_INVALID, "the instance sets belong to different sims");
-  if (op < 0 || op >= ISET_NUM_OPS) return set_err(CL_E_INVALID, "unknown instance set operation %d", op);
-  return sim->iset_combine(dst, const_cast<cl_iset*>(a), const_cast<cl_iset*>(b), op);
-}
-
-static int iset_range_ok(const cl_iset* s, int64_t lo, int64_t hi) {
-  if (lo < 0 || hi > s->sim->n_inst || lo > hi) return set_err(CL_E_INVALID, "instance range out of range");
-  return CL_OK;
-}
-
-int cl_iset_count(cl_iset* set, int64_t inst_lo, int64_t inst_hi, int64_t* n) {
-  if (!set) return set_err(CL_E_INVALID, "null instance set");
-  cl_sim* sim = set->sim;
-  SIM_CHECK(sim);
-  if (!n) return set_err(CL_E_INVALID, "null output");
-  if (const int rc = iset_range_ok(set, inst_lo, inst_hi)) return rc;
-  return sim->iset_count(set, inst_lo, inst_hi, n);
-}
-
-int cl_iset_read(cl_iset* set, int64_t inst_lo, int64_t inst_hi, int64_t* insts, int64_t cap, int64_t* n_match) {
-  if (!set) return set_err(CL_E_INVALID, "null instance set");
-  cl_sim* sim = set->sim;
-  SIM_CHECK(sim);
-  if (!n_match) return set_err(CL_E_INVALID, "null output");
-  if (cap < 0 || (cap > 0 && !insts)) return set_err(CL_E_INVALID, "iset read: cap >= 0, with an index array when cap > 0");
-  if (const int rc = iset_range_ok(set, inst_lo, inst_hi)) return rc;
-  return sim->iset_read(set, inst_lo, inst_hi, insts, cap, n_match);
-}
-
-int cl_iset_destroy(cl_iset* set) {
-  if (!set) return CL_OK;
-  cl_sim* sim = set->sim;
-  SIM_CHECK(sim);
-  iset_delete(set);
-  return CL_OK;
-}
-
-int cl_iset_time(cl_sim* sim, double* device_ms) {
-  SIM_CHECK(sim);
-  if (!device_ms) return set_err(CL_E_INVALID, "null output");
-  if (!sim->is_timed) return set_err(CL_E_STATE, "no instance set kernel has run");
-  HIP_TRY(hipStreamSynchronize(sim->stream));
-  float f = 0.f;
-  HIP_TRY(hipEventElapsedTime(&f, sim->is_ev[0], sim->is_ev[1]));
-  *device_ms = f;
-  return CL_OK;
-}
-
-int cl_select_stage_times(cl_sim* sim, double* evaluate_ms, double* compact_ms) {
-  SIM_CHECK(sim);
-  if (!sim->sel_timed) return set_err(CL_E_STATE, "no select call has run");
-  HIP_TRY(hipStreamSynchronize(sim->stream));
-  float a = 0.f, b = 0.f;
-  HIP_TRY(hipEventElapsedTime(&a, sim->sel_ev[0], sim->sel_ev[1]));
-  HIP_TRY(hipEventElapsedTime(&b, sim->sel_ev[1], sim->sel_ev[2]));
-  if (evaluate_ms) *evaluate_ms = a;
-  if (compact_ms) *compact_ms = b;
-  return CL_OK;
-}
-
-int cl_select_time(cl_sim* sim, double* device_ms) {
-  if (!device_ms) return set_err(CL_E_INVALID, "null output");
-  double a = 0, b = 0;
-  const int rc = cl_select_stage_times(sim, &a, &b);
-  if (rc) return rc;
-  *device_ms = a + b;
-  return CL_OK;
+  return sim->pk_tm.ms(0, 1, device_ms);
 }
 
 int cl_snapshot_ticks(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, int32_t* out) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!out && inst_hi > inst_lo) return set_err(CL_E_INVALID, "null output");
   if (const int rc = sample_args_ok(sim, sid, inst_lo, inst_hi)) return rc;
   return sim->ticks_of(sid, inst_lo, inst_hi, out);
 }
 
 int cl_get_counters(cl_sim* sim, int32_t only_ok, int64_t* out) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   int rc = sim->fetch();
   if (rc) return rc;
   for (int k = 0; k < CL_NUM_COUNTERS; ++k) out[k] = 0;
@@ -2991,7 +2163,7 @@ int cl_get_counters(cl_sim* sim, int32_t only_ok, int64_t* out) {
 }
 
 int cl_get_checksums(cl_sim* sim, int64_t* out) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   int rc = sim->flush();
   if (rc) return rc;
   if (!sim->dev_ready) return set_err(CL_E_STATE, "nothing has run on the device yet");
@@ -3011,7 +2183,7 @@ int cl_get_checksums(cl_sim* sim, int64_t* out) {
 }
 
 int cl_instance_hashes(cl_sim* sim, int64_t lo, int64_t n, uint64_t* out) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!out || lo < 0 || n < 0 || lo + n > sim->n_inst) return set_err(CL_E_INVALID, "bad instance range");
   int rc = sim->flush();
   if (rc) return rc;
@@ -3066,16 +2238,13 @@ int cl_go_delay_schedule_device(int32_t device, int64_t seed_base, const int64_t
     go_schedule(seed_base, seeds, n, draws, out);
     return CL_OK;
   }
-  struct Scratch {  // (freed on every return path)
+  struct Scratch {  // (the buffers and the timer free themselves on every return path)
     DevBuf<uint8_t> plane;
     DevBuf<long long> seeds;
     DevBuf<unsigned long long> flag;
+    DevTimer<2> tm;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
     ~Scratch() {
-      plane.release(), seeds.release(), flag.release();
-      for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
       if (stream) (void)hipStreamDestroy(stream);
     }
   } s;
@@ -3086,10 +2255,9 @@ int cl_go_delay_schedule_device(int32_t device, int64_t seed_base, const int64_t
     HIP_TRY(hipMemcpy(s.seeds.p, seeds, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
   }
   HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-  for (auto& e : s.ev) HIP_TRY(hipEventCreate(&e));
   DeviceGen g;
   if ((rc = device_generate(device, s.stream, prop.multiProcessorCount, seed_base, seeds ? s.seeds.p : nullptr, n, row,
-                            draws, s.plane.p, s.flag.p, s.ev, &g)))
+                            draws, s.plane.p, s.flag.p, &s.tm, &g)))
     return rc;
   if (g.overflow) {  // more flagged rows than the list holds: the host generator, as in the engine
     go_schedule(seed_base, seeds, n, draws, out);
@@ -3119,7 +2287,7 @@ int cl_go_intn(int64_t seed, int32_t bound, int64_t n, int32_t* out) {
 
 // ---- device event trace (logger.go) ------------------------------------------------
 int cl_trace_enable(cl_sim* sim, int64_t inst_lo, int32_t n_inst, int32_t cap) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (n_inst < 0 || inst_lo < 0 || (n_inst > 0 && (inst_lo + n_inst > sim->n_inst || cap <= 0)))
     return set_err(CL_E_INVALID, "trace range outside the batch");
   sim->trace_lo = inst_lo;
@@ -3130,7 +2298,7 @@ int cl_trace_enable(cl_sim* sim, int64_t inst_lo, int32_t n_inst, int32_t cap) {
 }
 
 int cl_trace_read(cl_sim* sim, int64_t inst, cl_log_event* out, int32_t cap, int32_t* n_events) {
-  SIM_CHECK(sim);
+  SIM_CALL(sim);
   if (!n_events) return set_err(CL_E_INVALID, "null output");
   if (sim->trace_n <= 0 || inst < sim->trace_lo || inst >= sim->trace_lo + sim->trace_n)
     return set_err(CL_E_INVALID, "instance %lld is not traced", (long long)inst);

@@ -350,6 +350,19 @@ def test_sets_outlive_reruns_and_die_with_their_sim():
     assert tmp._h is None
     # the sim goes with sets alive (listed, and two more); their handles are dead, closing them is not
     more = [sim.instance_set(1, []), sim.instance_set_from([1, 2, 3])]
+    # ... and with every analytics buffer and timer in use: each call once, then each timing getter
+    census = sim.snapshot_census(3, class_of=True)
+    assert census.class_of.shape == (N,) and census.n_classes > 0
+    assert sim.select_instances(3, [], ticks=True).insts.size == census.sample > 0
+    xt = sim.snapshot_crosstab((0, "tick", None, 0, 4, 16), (3, "msgs", None, 0, 1, 8))
+    assert xt.raw.size == cl.XT_CELLS + 16 * 8
+    packed = sim.collect_snapshot_packed(3)
+    by_list = sim.collect_snapshot_list(3, members(mask))
+    assert packed[0].shape[0] == N and by_list[0].shape[0] == int(mask.sum())
+    assert more[1].count(0, N) == 3
+    for ms in (sim.stats_time(), sim.census_time(), sim.select_time(), *sim.select_time(stages=True),
+               sim.crosstab_time(), sim.iset_time(), sim.collect_time()):
+        assert ms >= 0
     sim.__del__()
     for s in [listed] + more:
         s.close()
