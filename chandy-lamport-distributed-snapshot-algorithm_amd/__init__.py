@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 __all__ = ["ChandyLamportSim", "SnapshotStats", "STATS_LAYOUT_FIELDS", "SnapshotSelection", "SELECT_CLAUSE_DTYPE",
-           "InstanceSet", "SnapshotCrosstab", "CROSSTAB_AXIS_DTYPE",
+           "InstanceSet", "SnapshotCrosstab", "CROSSTAB_AXIS_DTYPE", "SnapshotGroups", "GROUP_TERM_DTYPE", "group_key",
 "GlobalSnapshot", "MsgSnapshot", "PassTokenEvent", "SnapshotEvent",
            "ClSnapError", "lib", "go_delay_schedule", "go_delay_schedule_device", "go_delay_schedule_jump",
            "DELAYGEN_MAX_DRAWS", "go_int63", "go_intn", "REFERENCE_SEED",
@@ -149,6 +149,10 @@ def lib():
         "cl_snapshot_crosstab": [vp, i64, i64, vp, vp, vp, i64],
         "cl_snapshot_crosstab_in": [vp, i64, i64, vp, vp, vp, vp, i64],
         "cl_crosstab_time": [vp, vp],
+        "cl_snapshot_groups": [vp, i64, i64, vp, i32, vp, vp, vp, vp, vp],
+        "cl_snapshot_groups_in": [vp, i64, i64, vp, vp, i32, vp, vp, vp, vp, vp],
+        "cl_groups_time": [vp, vp],
+        "cl_groups_stage_times": [vp, vp],
         "cl_set_delay_go_seed_list": [vp, vp, i64],
         "cl_set_delay_generator": [vp, i32],
         "cl_delay_generator": [vp, vp],
@@ -163,6 +167,8 @@ def lib():
         f.restype, f.argtypes = C.c_int, args
     L.cl_status_string.restype, L.cl_status_string.argtypes = cp, [i32]
     L.cl_last_error.restype, L.cl_last_error.argtypes = cp, []
+    if hasattr(L, "cl_group_key"):
+        L.cl_group_key.restype, L.cl_group_key.argtypes = C.c_uint64, [vp, i32]
     _lib = L
     return L
 
@@ -526,6 +532,125 @@ def _select_clauses(where, ids, chans):
             lo, hi = i64.min if lo is None else int(lo), i64.max if hi is None else int(hi)
         out[q] = (SELECT_FIELDS.index(field), int(index), SELECT_NOT if len(clause) == 5 else 0, 0, lo, hi)
     return out
+
+
+# cl_group_term (include/clsnap.h): a term of snapshot_groups
+GROUP_TERM_DTYPE = np.dtype([("sid", np.int32), ("field", np.int32), ("index", np.int32), ("reserved", np.int32)])
+GROUPS_MAX_TERMS = 8
+
+
+def _group_terms(terms, ids, chans):
+    """`terms` of ChandyLamportSim.snapshot_groups, each (sid, field, index) or (sid, field), as a
+    GROUP_TERM_DTYPE array; ValueError for anything the C call would have to refuse by shape."""
+    if isinstance(terms, np.ndarray) and terms.dtype == GROUP_TERM_DTYPE:
+        terms = [(int(t["sid"]), SELECT_FIELDS[int(t["field"])], int(t["index"])) for t in terms.ravel()]
+    if isinstance(terms, (str, bytes)) or not hasattr(terms, "__iter__"):
+        raise ValueError("group terms: a sequence of (sid, field, index)")
+    terms = list(terms)
+    if not 1 <= len(terms) <= GROUPS_MAX_TERMS:
+        raise ValueError(f"group terms: 1 to {GROUPS_MAX_TERMS} terms")
+    out = np.zeros(len(terms), dtype=GROUP_TERM_DTYPE)
+    for k, term in enumerate(terms):
+        what = f"group term {k}"
+        if not isinstance(term, (tuple, list)) or len(term) not in (2, 3):
+            raise ValueError(f"{what}: (sid, field, index)")
+        sid, field = term[:2]
+        if isinstance(sid, bool) or not isinstance(sid, (int, np.integer)) or not 0 <= sid <= np.iinfo(np.int32).max:
+            raise ValueError(f"{what}: sid must be an integer >= 0")
+        if not isinstance(field, str) or field not in SELECT_FIELDS:
+            raise ValueError(f"{what}: field must be one of {SELECT_FIELDS}")
+        index = _field_index(what, field, term[2] if len(term) == 3 else None, ids, chans)
+        if not 0 <= index <= np.iinfo(np.int32).max:
+            raise ValueError(f"{what}: index {index} out of range")
+        out[k] = (sid, SELECT_FIELDS.index(field), index, 0)
+    return out
+
+
+def group_key(values):
+    """The 64-bit key of a tuple of int64 term values (cl_group_key): what SnapshotGroups.groups["key"]
+    holds for the group with these values.  Host only."""
+    v = np.ascontiguousarray(values, dtype=np.int64).ravel()
+    return int(lib().cl_group_key(_p(v) if v.size else None, v.size))
+
+
+class SnapshotGroups:
+    """The result of ``ChandyLamportSim.snapshot_groups``: GROUP BY over a tuple of snapshot quantities.
+
+    ``terms`` is the GROUP_TERM_DTYPE array of the call.  ``groups`` is a structured array
+    (CENSUS_CLASS_DTYPE: key, count, first_inst, and the min / max completion tick of terms[0]'s
+    snapshot) of the returned groups, ordered by count descending, then key ascending;
+    ``values[g]`` is group g's tuple (int64; a "key" term's value is the uint64 hash's bit pattern).
+    ``n_groups`` counts all groups, also those beyond ``max_groups``.  ``group_of`` (or None) maps
+    each instance of the range to its group index, -1 outside the sample.  Groups are keyed by the
+    64-bit ``group_key`` of the tuple: equal keys mean the same group."""
+
+    def __init__(self, terms, instances, ok, sample, n_groups, groups, values, group_of=None):
+        self.terms = np.ascontiguousarray(terms, dtype=GROUP_TERM_DTYPE).ravel()
+        self.instances, self.ok, self.sample, self.n_groups = int(instances), int(ok), int(sample), int(n_groups)
+        self.groups = np.ascontiguousarray(groups, dtype=CENSUS_CLASS_DTYPE)
+        self.values = np.ascontiguousarray(values, dtype=np.int64).reshape(self.groups.shape[0], self.terms.size)
+        self.group_of = group_of
+
+    @property
+    def n_returned(self):
+        return int(self.groups.shape[0])
+
+    def frequency(self, g):
+        """Share of the sample in returned group g; nan on an empty sample."""
+        return float(self.groups["count"][g]) / self.sample if self.sample else float("nan")
+
+    def merge(self, other, offset=0):
+        """The groups of the union of two disjoint instance sets (other ranks, other ranges);
+        ``offset`` is added to ``other``'s instance indices.  Same key: counts add, first_inst and
+        min_tick take the minimum, max_tick the maximum, the values ride along.  Re-sorted; group_of
+        is dropped.  Raises ValueError when either side was truncated (n_returned < n_groups) or
+        the terms differ."""
+        if not isinstance(other, SnapshotGroups) or other.terms.tobytes() != self.terms.tobytes():
+            raise ValueError("SnapshotGroups.merge: not the groups of the same terms")
+        if self.n_returned < self.n_groups or other.n_returned < other.n_groups:
+            raise ValueError("SnapshotGroups.merge: truncated groups (n_returned < n_groups) cannot be merged")
+        b = other.groups.copy()
+        b["first_inst"] += offset
+        both = np.concatenate([self.groups, b])
+        vals = np.concatenate([self.values, other.values])
+        keys, at, inv = np.unique(both["key"], return_index=True, return_inverse=True)
+        out = np.zeros(keys.size, dtype=CENSUS_CLASS_DTYPE)
+        out["key"] = keys
+        out["first_inst"] = np.iinfo(np.int64).max
+        out["min_tick"] = np.iinfo(np.int32).max
+        out["max_tick"] = np.iinfo(np.int32).min
+        np.add.at(out["count"], inv, both["count"])
+        np.minimum.at(out["first_inst"], inv, both["first_inst"])
+        np.minimum.at(out["min_tick"], inv, both["min_tick"])
+        np.maximum.at(out["max_tick"], inv, both["max_tick"])
+        order = np.lexsort((out["key"], -out["count"]))
+        return SnapshotGroups(self.terms.copy(), self.instances + other.instances, self.ok + other.ok,
+                              self.sample + other.sample, keys.size, out[order], vals[at][order])
+
+    def instance_set(self, sim, g, inst_lo=0, inst_hi=None):
+        """The InstanceSet of the instances of [inst_lo, inst_hi) whose tuple is that of returned
+        group g: one sim.instance_set(sid, equality clauses) per distinct snapshot id of the terms,
+        intersected.  For groups taken over the same range (and no set) its size is the group's count."""
+        by_sid = {}
+        for term, v in zip(self.terms, self.values[g]):
+            field, v = SELECT_FIELDS[int(term["field"])], int(v)
+            if field == "key":
+                v &= 2**64 - 1
+            by_sid.setdefault(int(term["sid"]), []).append((field, int(term["index"]), v, v))
+        out = None
+        for sid, where in by_sid.items():
+            s = sim.instance_set(sid, where, inst_lo, inst_hi)
+            out = s if out is None else out & s
+        return out
+
+    def __eq__(self, other):
+        return (isinstance(other, SnapshotGroups) and self.terms.tobytes() == other.terms.tobytes()
+                and (self.instances, self.ok, self.sample, self.n_groups)
+                == (other.instances, other.ok, other.sample, other.n_groups)
+                and self.groups.tobytes() == other.groups.tobytes()
+                and self.values.tobytes() == other.values.tobytes())
+
+    __hash__ = None
 
 
 class SnapshotSelection:
@@ -1095,6 +1220,54 @@ class ChandyLamportSim:
         """Device ms of the latest snapshot_crosstab kernel."""
         ms = C.c_double(0)
         _check(self._L.cl_crosstab_time(self._h, C.byref(ms)))
+        return ms.value
+
+    def group_terms(self, terms):
+        """`terms` of snapshot_groups, each (sid, field, index), as a GROUP_TERM_DTYPE array (host
+        only): field one of SELECT_FIELDS, index normalised as in select_clauses."""
+        return _group_terms(terms, self.node_ids(), self.channels())
+
+    def snapshot_groups(self, terms, inst_lo=0, inst_hi=None, max_groups=4096, group_of=False, lds_slots=0):
+        """GROUP BY over the tuple of snapshot quantities `terms` (1 to 8 of (sid, field, index), which
+        may name different snapshot ids) over the OK instances of [inst_lo, inst_hi) in which the
+        snapshot of every term completed, on the GPU (cl_snapshot_groups): a SnapshotGroups of at
+        most `max_groups` groups, most frequent first, each with its tuple of values.
+        group_of=True also returns each instance's group index.  lds_slots as in snapshot_census.
+        Adjacent terms of one snapshot id share one staging of its records: keep them together."""
+        return self._groups(None, terms, inst_lo, inst_hi, max_groups, group_of, lds_slots)
+
+    def _groups(self, iset, terms, inst_lo, inst_hi, max_groups, group_of, lds_slots):
+        hi = self.n_instances if inst_hi is None else inst_hi
+        t = self.group_terms(terms)
+        spec = _CensusSpec(max_groups, lds_slots)
+        groups = np.zeros(max(max_groups, 0), dtype=CENSUS_CLASS_DTYPE)
+        values = np.zeros((max(max_groups, 0), t.size), dtype=np.int64)
+        gof = np.full(max(hi - inst_lo, 0), -1, dtype=np.int32) if group_of else None
+        info = np.zeros(5, dtype=np.int64)
+        tail = (_p(t), t.size, C.byref(spec), _p(groups) if max_groups > 0 else None,
+                _p(values) if max_groups > 0 else None, _p(gof) if group_of else None, _p(info))
+        if iset is None:
+            _check(self._L.cl_snapshot_groups(self._h, inst_lo, hi, *tail))
+        else:
+            _check(self._L.cl_snapshot_groups_in(self._h, inst_lo, hi, iset._handle(), *tail))
+        instances, ok, sample, n_groups, n_returned = info.tolist()
+        return SnapshotGroups(t, instances, ok, sample, n_groups, groups[:n_returned].copy(),
+                              values[:n_returned].copy(), gof)
+
+    def snapshot_groups_in(self, iset, terms, inst_lo=0, inst_hi=None, max_groups=4096, group_of=False, lds_slots=0):
+        """snapshot_groups over the members of the InstanceSet `iset` (cl_snapshot_groups_in);
+        `instances` and `ok` still count the whole range."""
+        return self._groups(iset, terms, inst_lo, inst_hi, max_groups, group_of, lds_slots)
+
+    def groups_time(self, stages=False):
+        """Device ms of the latest snapshot_groups kernels; stages=True: the tuple (table
+        initialisation, key pass, gather, group_of, values) whose sum it is."""
+        if stages:
+            ms = (C.c_double * 5)()
+            _check(self._L.cl_groups_stage_times(self._h, ms))
+            return tuple(ms)
+        ms = C.c_double(0)
+        _check(self._L.cl_groups_time(self._h, C.byref(ms)))
         return ms.value
 
     def instance_set(self, snapshot_id, where=(), inst_lo=0, inst_hi=None):

@@ -1,6 +1,6 @@
 // cl_analytics.cpp -- the host layer of the batch analytics behind include/clsnap.h: statistics
 // (cl_stats.hip), census (cl_census.hip), selection (cl_select.hip), crosstab (cl_crosstab.hip) and
-// the device-resident instance sets (cl_iset.hip).
+// the device-resident instance sets (cl_iset.hip), and the tuple group-by (cl_groups.hip).
 //
 // It owns its scratch, its timers and the sets, and reads a sim through cl_host.h only: the facts
 // its argument checks need, the device and stream, and the record planes and tables of a sample.
@@ -9,6 +9,7 @@
 #include <cstring>
 #include <vector>
 
+#include "cl_groups.h"
 #include "cl_host.h"
 
 using namespace clsnap;
@@ -41,6 +42,13 @@ struct Analytics {
   DevBuf<unsigned long long> d_cs_info, d_cs_keys;
   DevBuf<int32_t> d_cs_class, d_cs_rank;
   DevTimer<6> cs;
+  // group-by over a tuple of snapshot quantities (cl_snapshot_groups, cl_groups.hip): the census's
+  // table scratch above, plus the returned groups' smallest instances and their tuples; gr: the
+  // event pairs of the latest call as cs (mark 6: between the table's initialisation and the key
+  // pass), grv: the values kernel
+  DevBuf<long long> d_gr_first, d_gr_vals;
+  DevTimer<7> gr;
+  DevTimer<2> grv;
   // instance selection (cl_select_instances, cl_select.hip): verdict bitmap, block sums, output
   DevBuf<unsigned long long> d_sel_bits, d_sel_info;
   DevBuf<long long> d_sel_bsum, d_sel_out;
@@ -141,6 +149,86 @@ struct Analytics {
     return CL_OK;
   }
 
+  // The census's table scratch for a range of n instances (shared by the census and the tuple
+  // group-by), and the fields of *p that name it and the tables next to the records.
+  int table_begin(CensusParams* p, const SimTables& t, int64_t n, int32_t lds_slots, bool class_of) {
+    int rc;
+    p->slots = 16;
+    while (p->slots < 2 * n) p->slots <<= 1;
+    if ((rc = d_cs_table.ensure((size_t)p->slots + 1)) || (rc = d_cs_list.ensure((size_t)n)) ||
+        (rc = d_cs_info.ensure(4)))
+      return rc;
+    if (class_of && ((rc = d_cs_keys.ensure((size_t)n)) || (rc = d_cs_class.ensure((size_t)n)))) return rc;
+    p->ch_slot = t.ch_slot;
+    p->hist_off = t.hist_off;
+    p->hist_val = t.hist_val;
+    p->lds_slots = lds_slots;
+    p->staged = p->s.n_nodes * p->s.rw <= kCensusStageWords ? 1 : 0;
+    p->empty_key = kCensusEmptyKey;
+    // (tests move the marker onto a key that occurs, to run the extra entry's path)
+    if (const char* v = std::getenv("CLSNAP_CENSUS_EMPTY_KEY")) p->empty_key = std::strtoull(v, nullptr, 0);
+    p->table = d_cs_table.p;
+    p->list = d_cs_list.p;
+    p->info = d_cs_info.p;
+    p->keys = class_of ? d_cs_keys.p : nullptr;
+    p->class_of = class_of ? d_cs_class.p : nullptr;
+    return CL_OK;
+  }
+
+  // After a key pass (marks 0 and 1 of `tm` around it): the counters into *info, the k classes
+  // compacted on the device and sorted here (count descending, key ascending) into *out, and
+  // class_of[n] when asked for.  tm.done counts the event pairs completed (key pass, gather, class_of).
+  template <int N>
+  int table_finish(const CensusParams& p, int64_t n, DevTimer<N>& tm, const char* what,
+                   std::vector<CensusEntry>* out, int32_t* class_of, cl_census_info* info) {
+    const hipStream_t stream = dev.stream;
+    int rc, e;
+    unsigned long long h[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, d_cs_info.p, sizeof h, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    tm.done = 1;
+    const int64_t k = (int64_t)h[3];
+    if (k > n) return set_err(CL_E_DEVICE, "%s: %lld classes of %lld instances", what, (long long)k, (long long)n);
+    info->instances = (int64_t)h[0], info->ok = (int64_t)h[1], info->sample = (int64_t)h[2], info->n_classes = k;
+    // ---- the k classes: compacted on the device, sorted here
+    std::vector<CensusEntry> got((size_t)k);
+    if (k > 0) {
+      if ((rc = d_cs_out.ensure((size_t)k))) return rc;
+      if ((rc = tm.mark(2, stream))) return rc;
+      if ((e = launch_census_gather(p, k, d_cs_out.p, stream)))
+        return set_err(CL_E_DEVICE, "%s kernels: %s", what, hipGetErrorString((hipError_t)e));
+      if ((rc = tm.mark(3, stream))) return rc;
+      HIP_TRY(hipMemcpyAsync(got.data(), d_cs_out.p, (size_t)k * sizeof(CensusEntry), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));
+      tm.done = 2;
+    } else if (class_of) {
+      // (no gather: an empty pair, so that tm.done below counts recorded pairs only)
+      if ((rc = tm.mark(2, stream)) || (rc = tm.mark(3, stream))) return rc;
+    }
+    std::vector<int32_t> order((size_t)k);
+    for (int64_t j = 0; j < k; ++j) order[(size_t)j] = (int32_t)j;
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+      const CensusEntry &x = got[(size_t)a], &y = got[(size_t)b];
+      return x.count != y.count ? x.count > y.count : x.key < y.key;
+    });
+    out->resize((size_t)k);
+    for (int64_t j = 0; j < k; ++j) (*out)[(size_t)j] = got[(size_t)order[(size_t)j]];
+    if (!class_of) return CL_OK;
+    // ---- class_of: the ranks go back into the table, a lookup maps key -> rank per instance
+    std::vector<int32_t> rank((size_t)std::max<int64_t>(k, 1));
+    for (int64_t j = 0; j < k; ++j) rank[(size_t)order[(size_t)j]] = (int32_t)j;
+    if ((rc = d_cs_rank.ensure(rank.size()))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_cs_rank.p, rank.data(), rank.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    if ((rc = tm.mark(4, stream))) return rc;
+    if ((e = launch_census_class_of(p, k, d_cs_rank.p, stream)))
+      return set_err(CL_E_DEVICE, "%s kernels: %s", what, hipGetErrorString((hipError_t)e));
+    if ((rc = tm.mark(5, stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(class_of, d_cs_class.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    tm.done = 3;
+    return CL_OK;
+  }
+
   // cl_snapshot_census (arguments checked by the caller): the classes of snapshot sid over
   // [lo, hi), sorted, into *out; class_of[hi - lo] when asked for.  lds_slots: the workgroup
   // table's entries, 0 for none.
@@ -159,25 +247,7 @@ struct Analytics {
       return CL_OK;
     }
     if (n > ((int64_t)1 << 29)) return set_err(CL_E_LIMIT, "census of more than 2^29 instances");
-    p.slots = 16;
-    while (p.slots < 2 * n) p.slots <<= 1;
-    if ((rc = d_cs_table.ensure((size_t)p.slots + 1)) || (rc = d_cs_list.ensure((size_t)n)) ||
-        (rc = d_cs_info.ensure(4)))
-      return rc;
-    if (class_of && ((rc = d_cs_keys.ensure((size_t)n)) || (rc = d_cs_class.ensure((size_t)n)))) return rc;
-    p.ch_slot = t.ch_slot;
-    p.hist_off = t.hist_off;
-    p.hist_val = t.hist_val;
-    p.lds_slots = lds_slots;
-    p.staged = p.s.n_nodes * p.s.rw <= kCensusStageWords ? 1 : 0;
-    p.empty_key = kCensusEmptyKey;
-    // (tests move the marker onto a key that occurs, to run the extra entry's path)
-    if (const char* v = std::getenv("CLSNAP_CENSUS_EMPTY_KEY")) p.empty_key = std::strtoull(v, nullptr, 0);
-    p.table = d_cs_table.p;
-    p.list = d_cs_list.p;
-    p.info = d_cs_info.p;
-    p.keys = class_of ? d_cs_keys.p : nullptr;
-    p.class_of = class_of ? d_cs_class.p : nullptr;
+    if ((rc = table_begin(&p, t, n, lds_slots, class_of != nullptr))) return rc;
     const int32_t blocks = sample_grid(p.s.tile_hi - p.s.tile_lo, census_lds_bytes(lds_slots, p.staged != 0));
     if ((rc = cs.mark(0, stream))) return rc;
     HIP_TRY(hipMemsetAsync(d_cs_info.p, 0, 4 * sizeof(unsigned long long), stream));
@@ -185,46 +255,67 @@ struct Analytics {
     if (!e) e = launch_census_keys(p, blocks, stream);
     if (e) return set_err(CL_E_DEVICE, "census kernels: %s", hipGetErrorString((hipError_t)e));
     if ((rc = cs.mark(1, stream))) return rc;
-    unsigned long long h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, d_cs_info.p, sizeof h, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    cs.done = 1;
-    const int64_t k = (int64_t)h[3];
-    if (k > n) return set_err(CL_E_DEVICE, "census: %lld classes of %lld instances", (long long)k, (long long)n);
-    info->instances = (int64_t)h[0], info->ok = (int64_t)h[1], info->sample = (int64_t)h[2], info->n_classes = k;
-    // ---- the k classes: compacted on the device, sorted here
-    std::vector<CensusEntry> got((size_t)k);
-    if (k > 0) {
-      if ((rc = d_cs_out.ensure((size_t)k))) return rc;
-      if ((rc = cs.mark(2, stream))) return rc;
-      if ((e = launch_census_gather(p, k, d_cs_out.p, stream)))
-        return set_err(CL_E_DEVICE, "census kernels: %s", hipGetErrorString((hipError_t)e));
-      if ((rc = cs.mark(3, stream))) return rc;
-      HIP_TRY(hipMemcpyAsync(got.data(), d_cs_out.p, (size_t)k * sizeof(CensusEntry), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      cs.done = 2;
+    return table_finish(p, n, cs, "census", out, class_of, info);
+  }
+
+  // cl_snapshot_groups (arguments checked by the caller): the groups of the term tuples over
+  // [lo, hi), sorted, into *out; group_of[hi - lo] when asked for; the tuples of the first
+  // min(n_groups, max_groups) groups, evaluated on the device for each group's smallest instance,
+  // into values[][n_terms].  The table, its scratch and the order are the census's.
+  int groups(int64_t lo, int64_t hi, const cl_group_term* terms, int32_t n_terms, int32_t lds_slots,
+             int64_t max_groups, std::vector<CensusEntry>* out, int64_t* values, int32_t* group_of,
+             cl_census_info* info, cl_iset* in) {
+    GroupsParams p{};
+    SimTables t{};
+    int rc = sample_begin(terms[0].sid, lo, hi, &p.c.s, &t, in);
+    if (rc) return rc;
+    const hipStream_t stream = dev.stream;
+    const int64_t n = hi - lo;
+    out->clear();
+    *info = cl_census_info{};
+    gr.done = grv.done = 0;
+    if (n == 0) return CL_OK;
+    if ((rc = table_begin(&p.c, t, n, lds_slots, group_of != nullptr))) return rc;
+    p.hist_pre = t.hist_pre;
+    p.n_terms = n_terms;
+    for (int32_t k = 0; k < n_terms; ++k) {
+      std::memcpy(&p.term[k], &terms[k], sizeof(GroupTerm));
+      p.reads_records |= terms[k].field != SEL_TICK;
+      const int32_t sid = terms[k].sid;
+      if (sid != terms[0].sid && std::find(p.other_sid, p.other_sid + p.n_other, sid) == p.other_sid + p.n_other)
+        p.other_sid[p.n_other++] = sid;
     }
-    std::vector<int32_t> order((size_t)k);
-    for (int64_t j = 0; j < k; ++j) order[(size_t)j] = (int32_t)j;
-    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-      const CensusEntry &x = got[(size_t)a], &y = got[(size_t)b];
-      return x.count != y.count ? x.count > y.count : x.key < y.key;
-    });
-    out->resize((size_t)k);
-    for (int64_t j = 0; j < k; ++j) (*out)[(size_t)j] = got[(size_t)order[(size_t)j]];
-    if (!class_of) return CL_OK;
-    // ---- class_of: the ranks go back into the table, a lookup maps key -> rank per instance
-    std::vector<int32_t> rank((size_t)std::max<int64_t>(k, 1));
-    for (int64_t j = 0; j < k; ++j) rank[(size_t)order[(size_t)j]] = (int32_t)j;
-    if ((rc = d_cs_rank.ensure(rank.size()))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_cs_rank.p, rank.data(), rank.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    if ((rc = cs.mark(4, stream))) return rc;
-    if ((e = launch_census_class_of(p, k, d_cs_rank.p, stream)))
-      return set_err(CL_E_DEVICE, "census kernels: %s", hipGetErrorString((hipError_t)e));
-    if ((rc = cs.mark(5, stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(class_of, d_cs_class.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    cs.done = 3;
+    const bool staged = p.c.staged && p.reads_records;
+    int32_t blocks = sample_grid(p.c.s.tile_hi - p.c.s.tile_lo, census_lds_bytes(lds_slots, staged));
+    // A list of completion ticks reads two words per instance and has hundreds of groups and more:
+    // what counts is the closing flush, one global insert per occupied table entry and workgroup,
+    // so one workgroup per CU (C3 at 2^20, tick(0), tick(4): key pass 0.171 ms with the 5 per CU
+    // the LDS admits, 0.108 with 2, 0.090 with 1; the five ticks 0.590 -> 0.443).  Record lists
+    // keep the census's grid: with 1 per CU the 8 node words take 0.133 against 0.112 ms.
+    if (!p.reads_records) blocks = std::min(blocks, std::max(dev.n_cus, 1));
+    if ((rc = gr.mark(0, stream))) return rc;
+    HIP_TRY(hipMemsetAsync(d_cs_info.p, 0, 4 * sizeof(unsigned long long), stream));
+    int e = launch_census_init(p.c, stream);
+    if ((rc = gr.mark(6, stream))) return rc;
+    if (!e) e = launch_groups_keys(p, blocks, stream);
+    if (e) return set_err(CL_E_DEVICE, "groups kernels: %s", hipGetErrorString((hipError_t)e));
+    if ((rc = gr.mark(1, stream))) return rc;
+    if ((rc = table_finish(p.c, n, gr, "groups", out, group_of, info))) return rc;
+    // ---- the tuples of the returned groups, from each group's smallest instance
+    const int64_t k = std::min<int64_t>(info->n_classes, max_groups);
+    if (k == 0) return CL_OK;
+    std::vector<long long> first((size_t)k);
+    for (int64_t g = 0; g < k; ++g) first[(size_t)g] = (*out)[(size_t)g].first;
+    if ((rc = d_gr_first.ensure((size_t)k)) || (rc = d_gr_vals.ensure((size_t)k * (size_t)n_terms))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_gr_first.p, first.data(), (size_t)k * sizeof(long long), hipMemcpyHostToDevice, stream));
+    if ((rc = grv.mark(0, stream))) return rc;
+    if ((e = launch_groups_values(p, t.rec_slot, d_gr_first.p, k, d_gr_vals.p, stream)))
+      return set_err(CL_E_DEVICE, "groups kernels: %s", hipGetErrorString((hipError_t)e));
+    if ((rc = grv.mark(1, stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(values, d_gr_vals.p, (size_t)k * (size_t)n_terms * sizeof(long long), hipMemcpyDeviceToHost,
+                           stream));
+    HIP_TRY(hipStreamSynchronize(stream));  // (also: `first` is the host's until its copy is done)
+    grv.done = 1;
     return CL_OK;
   }
 
@@ -493,12 +584,14 @@ Analytics* analytics_new(cl_sim* sim) { return new Analytics(sim); }
 void analytics_delete(Analytics* a) { delete a; }
 
 // The selection's scratch, the bitmaps of the sets alive and their list upload, the crosstab's
-// result words (the statistics and census scratch are not counted: DESIGN.md §3).
+// result words, the group-by's representatives and tuples (the statistics and census scratch are
+// not counted: DESIGN.md §3).
 int64_t analytics_device_bytes(const Analytics* a) {
   int64_t b = a->d_sel_bits.bytes() + a->d_sel_info.bytes() + a->d_sel_bsum.bytes() + a->d_sel_out.bytes() +
               a->d_sel_ticks.bytes();
   for (const cl_iset* s : a->isets) b += s->bits.bytes();
-  return b + a->d_is_list.bytes() + a->d_is_count.bytes() + a->d_xt.bytes();
+  return b + a->d_is_list.bytes() + a->d_is_count.bytes() + a->d_xt.bytes() + a->d_gr_first.bytes() +
+         a->d_gr_vals.bytes();
 }
 
 int sample_args_ok(const cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi) {
@@ -565,6 +658,15 @@ static int stats_call(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi
   return sim_analytics(sim)->stats(sid, inst_lo, inst_hi, L, out, const_cast<cl_iset*>(in));
 }
 
+static int census_spec_ok(const cl_census_spec* spec, const char* what) {
+  const int32_t ls = spec->lds_slots;
+  if (spec->max_classes < 0 ||
+      !(ls == 0 || ls == -1 || (ls >= kCensusMinLdsSlots && ls <= kCensusMaxLdsSlots && (ls & (ls - 1)) == 0)))
+    return set_err(CL_E_INVALID, "%s spec: max_classes >= 0; lds_slots 0, -1 or a power of two in [%d, %d]", what,
+                   kCensusMinLdsSlots, kCensusMaxLdsSlots);
+  return CL_OK;
+}
+
 static_assert(sizeof(cl_census_class) == sizeof(CensusEntry) && sizeof(CensusEntry) == 32,
               "cl_census_class mirrors CensusEntry");
 
@@ -578,10 +680,7 @@ static int census_call(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_h
     if (const int rc = iset_arg_ok(sim, in)) return rc;
   if (!spec || !info) return set_err(CL_E_INVALID, "null census spec or info");
   const int32_t ls = spec->lds_slots;
-  if (spec->max_classes < 0 ||
-      !(ls == 0 || ls == -1 || (ls >= kCensusMinLdsSlots && ls <= kCensusMaxLdsSlots && (ls & (ls - 1)) == 0)))
-    return set_err(CL_E_INVALID, "census spec: max_classes >= 0; lds_slots 0, -1 or a power of two in [%d, %d]",
-                   kCensusMinLdsSlots, kCensusMaxLdsSlots);
+  if (const int rc = census_spec_ok(spec, "census")) return rc;
   if (spec->max_classes > 0 && !classes) return set_err(CL_E_INVALID, "null classes with max_classes > 0");
   if (const int rc = sample_args_ok(sim, sid, inst_lo, inst_hi)) return rc;
   std::vector<CensusEntry> got;
@@ -591,6 +690,50 @@ static int census_call(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_h
   if (rc) return rc;
   info->n_returned = std::min<int64_t>(info->n_classes, spec->max_classes);
   if (info->n_returned > 0) std::memcpy(classes, got.data(), (size_t)info->n_returned * sizeof(cl_census_class));
+  return CL_OK;
+}
+
+static_assert(sizeof(cl_group_term) == sizeof(GroupTerm) && sizeof(GroupTerm) == 16 &&
+                  CL_GROUPS_MAX_TERMS == kGroupsMaxTerms,
+              "cl_group_term and CL_GROUPS_MAX_TERMS mirror cl_groups.h");
+
+// cl_snapshot_groups, and cl_snapshot_groups_in with its set (`conditional`).
+static int groups_call(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, bool conditional, const cl_iset* in,
+                       const cl_group_term* terms, int32_t n_terms, const cl_census_spec* spec,
+                       cl_census_class* groups, int64_t* values, int32_t* group_of, cl_census_info* info) {
+  SIM_CALL(sim);
+  // every argument is checked before any device work
+  if (conditional)
+    if (const int rc = iset_arg_ok(sim, in)) return rc;
+  if (n_terms < 1 || n_terms > CL_GROUPS_MAX_TERMS || !terms)
+    return set_err(CL_E_INVALID, "groups: 1 <= n_terms <= %d, with a term array", CL_GROUPS_MAX_TERMS);
+  const SimFacts f = sim_facts(sim);
+  for (int32_t k = 0; k < n_terms; ++k) {
+    const cl_group_term& z = terms[k];
+    if (z.field < 0 || z.field >= SEL_NUM_FIELDS || z.reserved)
+      return set_err(CL_E_INVALID, "groups term %d: unknown field or non-zero reserved", k);
+    const int64_t bound =
+        z.field == CL_SEL_NODE ? f.n_nodes : z.field == CL_SEL_CH_MSGS || z.field == CL_SEL_CH_TOK ? f.n_ch : 1;
+    if (z.index < 0 || z.index >= bound) return set_err(CL_E_INVALID, "groups term %d: index %d out of range", k, z.index);
+  }
+  if (!spec || !info) return set_err(CL_E_INVALID, "null groups spec or info");
+  if (const int rc = census_spec_ok(spec, "groups")) return rc;
+  if (spec->max_classes > 0 && (!groups || !values))
+    return set_err(CL_E_INVALID, "null groups or values with max_classes > 0");
+  if (inst_lo < 0 || inst_hi > f.n_inst || inst_lo > inst_hi) return set_err(CL_E_INVALID, "instance range out of range");
+  if (inst_hi - inst_lo > ((int64_t)1 << 29)) return set_err(CL_E_LIMIT, "groups of more than 2^29 instances");
+  if (!f.ran) return set_err(CL_E_STATE, "nothing has run yet: no event was issued");
+  for (int32_t k = 0; k < n_terms; ++k)
+    if (terms[k].sid < 0 || terms[k].sid >= f.n_sids)
+      return set_err(CL_E_INVALID, "groups term %d: snapshot id out of range", k);
+  std::vector<CensusEntry> got;
+  const int32_t ls = spec->lds_slots;
+  const int32_t lds_slots = ls == 0 ? kCensusAutoLdsSlots : ls < 0 ? 0 : ls;
+  const int rc = sim_analytics(sim)->groups(inst_lo, inst_hi, terms, n_terms, lds_slots, spec->max_classes, &got,
+                                            values, group_of, info, const_cast<cl_iset*>(in));
+  if (rc) return rc;
+  info->n_returned = std::min<int64_t>(info->n_classes, spec->max_classes);
+  if (info->n_returned > 0) std::memcpy(groups, got.data(), (size_t)info->n_returned * sizeof(cl_census_class));
   return CL_OK;
 }
 
@@ -724,6 +867,49 @@ int cl_census_time(cl_sim* sim, double* device_ms) {
   }
   *device_ms = sum;
   return CL_OK;
+}
+
+int cl_snapshot_groups(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_group_term* terms, int32_t n_terms,
+                       const cl_census_spec* spec, cl_census_class* groups, int64_t* values, int32_t* group_of,
+                       cl_census_info* info) {
+  return groups_call(sim, inst_lo, inst_hi, false, nullptr, terms, n_terms, spec, groups, values, group_of, info);
+}
+
+int cl_snapshot_groups_in(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_iset* in, const cl_group_term* terms,
+                          int32_t n_terms, const cl_census_spec* spec, cl_census_class* groups, int64_t* values,
+                          int32_t* group_of, cl_census_info* info) {
+  return groups_call(sim, inst_lo, inst_hi, true, in, terms, n_terms, spec, groups, values, group_of, info);
+}
+
+int cl_groups_stage_times(cl_sim* sim, double* stage_ms) {
+  SIM_CALL(sim);
+  if (!stage_ms) return set_err(CL_E_INVALID, "null output");
+  const Analytics* a = sim_analytics(sim);
+  if (!a->gr.done) return set_err(CL_E_STATE, "no groups call has run");
+  int rc = a->marks_done();
+  if (rc) return rc;
+  for (int q = 0; q < 5; ++q) stage_ms[q] = 0;
+  // table initialisation, key pass, gather, group_of (the host's sort lies between), values
+  if ((rc = a->gr.ms(0, 6, &stage_ms[0])) || (rc = a->gr.ms(6, 1, &stage_ms[1]))) return rc;
+  if (a->gr.done >= 2 && (rc = a->gr.ms(2, 3, &stage_ms[2]))) return rc;
+  if (a->gr.done >= 3 && (rc = a->gr.ms(4, 5, &stage_ms[3]))) return rc;
+  if (a->grv.done && (rc = a->grv.ms(0, 1, &stage_ms[4]))) return rc;
+  return CL_OK;
+}
+
+int cl_groups_time(cl_sim* sim, double* device_ms) {
+  if (!device_ms) return set_err(CL_E_INVALID, "null output");
+  double ms[5];
+  const int rc = cl_groups_stage_times(sim, ms);
+  if (rc) return rc;
+  *device_ms = ms[0] + ms[1] + ms[2] + ms[3] + ms[4];
+  return CL_OK;
+}
+
+uint64_t cl_group_key(const int64_t* values, int32_t n) {
+  uint64_t h = group_key_seed(n);
+  for (int32_t k = 0; k < n && values; ++k) h = group_key_fold(h, values[k]);
+  return h;
 }
 
 int cl_select_instances(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_hi, const cl_select_clause* clauses,

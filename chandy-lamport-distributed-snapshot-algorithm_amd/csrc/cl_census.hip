@@ -14,18 +14,17 @@
 // consumes the N token words, then the channels in channel order, so it cannot be split over
 // staging chunks the way the statistics are.
 //
-// Aggregation.  One class usually holds most of the sample, so one global atomic per instance
-// would put the whole grid on one cache line.  Each workgroup first aggregates in an
-// open-addressing LDS table (64-bit CAS on the key, then LDS add / min / max); a lane whose probe
-// sequence finds no room inserts into the global table directly.  At the end every occupied LDS
-// entry issues one global insert.  The global table has >= 2 * (hi - lo) slots and cannot fill;
-// the thread that claims a slot appends it to the class list.  The key value kCensusEmptyKey marks
-// an empty slot; a snapshot with that very key goes to the extra entry behind the hashed slots.
+// Aggregation (cl_census_table.h, shared with the key pass of cl_groups.hip).  Each workgroup first
+// aggregates in an open-addressing LDS table; a lane whose probe sequence finds no room inserts
+// into the global table directly, and at the end every occupied LDS entry issues one global
+// insert.  The key value kCensusEmptyKey marks an empty slot; a snapshot with that very key goes to
+// the extra entry behind the hashed slots.
 //
 // class_of (on request).  The key pass keeps each sample instance's key; after the host's sort the
 // ranks are written into the table entries and a lookup kernel maps key -> rank per instance.
 #include <hip/hip_runtime.h>
 
+#include "cl_census_table.h"
 #include "cl_engine.h"
 #include "cl_sample.h"
 
@@ -46,105 +45,34 @@ __global__ __launch_bounds__(kCensusThreads) void cl_census_init(CensusEntry* ta
   }
 }
 
-// The table slot of `key`: its entry, claimed if new (then appended to the class list).
-__device__ __forceinline__ int64_t census_slot(const CensusParams& p, unsigned long long key, bool claim) {
-  if (key == p.empty_key) return p.slots;
-  const unsigned long long mask = (unsigned long long)p.slots - 1;
-  unsigned long long s = (key >> 16) & mask;
-  for (int64_t probe = 0; probe < p.slots; ++probe, s = (s + 1) & mask) {
-    if (claim) {
-      const unsigned long long old = atomicCAS(&p.table[s].key, p.empty_key, key);
-      if (old == p.empty_key) p.list[atomicAdd(&p.info[3], 1ULL)] = (uint32_t)s;
-      if (old == p.empty_key || old == key) return (int64_t)s;
-    } else {
-      const unsigned long long k = p.table[s].key;
-      if (k == key) return (int64_t)s;
-      if (k == p.empty_key) return -1;
-    }
-  }
-  return -1;  // (unreachable: the table has twice as many slots as the range has instances)
-}
-
-__device__ __forceinline__ void census_global_insert(const CensusParams& p, unsigned long long key,
-                                                     unsigned long long count, long long first, int32_t mn,
-                                                     int32_t mx) {
-  const int64_t s = census_slot(p, key, true);
-  if (s < 0) return;
-  CensusEntry* e = p.table + s;
-  const unsigned long long before = atomicAdd(&e->count, count);
-  // the extra entry has no key to claim: its first adder lists it
-  if (s == p.slots && before == 0) p.list[atomicAdd(&p.info[3], 1ULL)] = (uint32_t)s;
-  atomicMin(&e->first, first);
-  atomicMin(&e->min_tick, mn);
-  atomicMax(&e->max_tick, mx);
-}
-
 __global__ __launch_bounds__(kCensusThreads) void cl_census_keys(CensusParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char census_lds[];
+  extern __shared__ __attribute__((aligned(16))) unsigned char census_lds_mem[];
   const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int32_t S = p.lds_slots;
-  unsigned long long* lkey = reinterpret_cast<unsigned long long*>(census_lds);  // [S]
-  long long* lfirst = reinterpret_cast<long long*>(lkey + S);                    // [S]
-  unsigned long long* scal = reinterpret_cast<unsigned long long*>(lfirst + S);  // [4] (3 used)
-  uint32_t* lcnt = reinterpret_cast<uint32_t*>(scal + 4);                        // [S]
-  int32_t* lmn = reinterpret_cast<int32_t*>(lcnt + S);                           // [S]
-  int32_t* lmx = lmn + S;                                                        // [S]
-  uint32_t* tile = reinterpret_cast<uint32_t*>(lmx + S) + (size_t)wave * kStatsStageWords;  // [64][N * rw | 1]
-
-  for (int32_t i = threadIdx.x; i < S; i += kCensusThreads) {
-    lkey[i] = p.empty_key;
-    lfirst[i] = kI64Max;
-    lcnt[i] = 0;
-    lmn[i] = kI32Max;
-    lmx[i] = kI32Min;
-  }
-  if (threadIdx.x < 4) scal[threadIdx.x] = 0;
-  __syncthreads();
+  const CensusLds L = census_lds(census_lds_mem, p.lds_slots, wave);
+  census_lds_init(L, p.lds_slots, p.empty_key);
 
   SampleCounts counts;
   for (int64_t t = sample_first_tile(p.s, wave); t < p.s.tile_hi; t += sample_tile_stride()) {
     const SampleLane l = sample_lane(p.s, t, lane);
     const int64_t inst = l.inst;
-    const int32_t tick = l.tick;
     counts.add(l);
     if (l.in && p.keys && !l.sample) p.class_of[inst - p.s.lo] = -1;
     if (__ballot(l.sample) == 0) continue;  // (wave-uniform)
-    if (p.staged) stage_tile(p.s, t, whole_record_chunk(p.s), tile, lane);
+    if (p.staged) stage_tile(p.s, t, whole_record_chunk(p.s), L.tile, lane);
     if (!l.sample) continue;
 
     // ---- the key: cl_checksum_kernel's arithmetic for one snapshot id
     const unsigned long long key = snapshot_key(p.s.sid, p.s.n_nodes, p.s.rw, p.s.n_ch, p.ch_slot, p.hist_off,
-                                                p.hist_val, RecordRow(p.s, t, lane, tile, p.staged));
+                                                p.hist_val, RecordRow(p.s, t, lane, L.tile, p.staged));
     if (p.keys) {
       p.keys[inst - p.s.lo] = key;
       p.class_of[inst - p.s.lo] = 0;
     }
-
     // ---- the workgroup's table, else the global one
-    bool placed = false;
-    if (S > 0 && key != p.empty_key) {
-      uint32_t s = (uint32_t)key & (uint32_t)(S - 1);
-      const int32_t probes = S < kCensusLdsProbes ? S : kCensusLdsProbes;
-      for (int32_t probe = 0; probe < probes && !placed; ++probe, s = (s + 1) & (uint32_t)(S - 1)) {
-        const unsigned long long old = atomicCAS(&lkey[s], p.empty_key, key);
-        if (old == p.empty_key || old == key) {
-          atomicAdd(&lcnt[s], 1u);
-          atomicMin(&lfirst[s], (long long)inst);
-          atomicMin(&lmn[s], tick);
-          atomicMax(&lmx[s], tick);
-          placed = true;
-        }
-      }
-    }
-    if (!placed) census_global_insert(p, key, 1, inst, tick, tick);
+    census_insert(p, L, key, inst, l.tick);
   }
-
-  counts.fold_wave(scal, lane);
-  __syncthreads();
-  sample_counts_to_global(scal, &p.info[0], &p.info[1], &p.info[2]);
-  // ---- one global insert per occupied entry of the workgroup's table
-  for (int32_t i = threadIdx.x; i < S; i += kCensusThreads)
-    if (lcnt[i]) census_global_insert(p, lkey[i], lcnt[i], lfirst[i], lmn[i], lmx[i]);
+  // ---- the counters, then one global insert per occupied entry of the workgroup's table
+  census_lds_flush(p, L, counts, lane);
 }
 
 __global__ __launch_bounds__(kCensusThreads) void cl_census_gather(CensusParams p, int64_t n, CensusEntry* out) {

@@ -52,6 +52,9 @@ int sim_device(cl_sim* sim, SimDevice* out);
 struct SimTables {
   const int32_t *ch_slot, *word_ch, *hist_off, *hist_val;
   const long long* hist_pre;
+  // instance -> record slot of block-major records (rec_word; the map the packed collect over a
+  // list uses), nullptr when the records are instance-major
+  const int32_t* rec_slot;
 };
 // Executes what is pending, makes the device current (*dev as from sim_device) and the token
 // histories resident, and fills the plane fields of *s (n_nodes .. snap_nod, blocked, inst_map);

@@ -1,5 +1,5 @@
 // cl_sample.h -- the sample walk shared by the analytics kernels of the batch engine
-// (cl_stats.hip, cl_census.hip, cl_select.hip, cl_crosstab.hip).  Device code: not part of cl_engine.h, which is
+// (cl_stats.hip, cl_census.hip, cl_select.hip, cl_crosstab.hip, cl_groups.hip).  Device code: not part of cl_engine.h, which is
 // also compiled into the run-time lanes kernel.
 //
 // The sample (SampleParams).  Every instance of [lo, hi) with status OK in which snapshot `sid`

@@ -97,6 +97,37 @@ def gather_census(census, first_instance, device):
     return out
 
 
+def gather_groups(groups, first_instance, device):
+    """A rank's SnapshotGroups (ChandyLamportSim.snapshot_groups of its shard, whose instance 0 is
+    global instance `first_instance`) combined over all ranks, in the manner of gather_census: one
+    all_gather of the heads sizes one all_gather of the rows -- the class words plus the values --
+    padded to the longest, and the parts merge with each rank's first instance as offset
+    (SnapshotGroups.merge; truncated groups raise ValueError there).  Every rank passes the same
+    terms.  Returns a new SnapshotGroups, the same on every rank, with global instance indices;
+    without an initialised group, a copy."""
+    cls = type(groups)
+    mine = cls(groups.terms.copy(), groups.instances, groups.ok, groups.sample, groups.n_groups, groups.groups.copy(),
+               groups.values.copy())
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return mine
+    head = allgather_ints([mine.n_returned, first_instance, mine.instances, mine.ok, mine.sample, mine.n_groups],
+                          device)
+    words, n_terms = mine.groups.dtype.itemsize // 8, mine.terms.size
+    rows = np.zeros((max(int(head[:, 0].max()), 1), words + n_terms), dtype=np.int64)
+    rows[:mine.n_returned, :words] = mine.groups.view(np.int64).reshape(-1, words)
+    rows[:mine.n_returned, words:] = mine.values
+    t = torch.from_numpy(rows).to(device)
+    parts = [torch.empty_like(t) for _ in range(dist.get_world_size())]
+    dist.all_gather(parts, t)
+    out = cls(mine.terms.copy(), 0, 0, 0, 0, mine.groups[:0], mine.values[:0])
+    for r, part in enumerate(parts):
+        k, first, instances, ok, sample, n_groups = (int(v) for v in head[r])
+        part = part.cpu().numpy()[:k]
+        rows_g = np.ascontiguousarray(part[:, :words]).reshape(-1).view(mine.groups.dtype)
+        out = out.merge(cls(mine.terms.copy(), instances, ok, sample, n_groups, rows_g, part[:, words:]), offset=first)
+    return out
+
+
 def gather_selection(sel, first_instance, device):
     """A rank's SnapshotSelection (ChandyLamportSim.select_instances of its shard, whose instance 0
     is global instance `first_instance`) combined over all ranks, in the manner of gather_census:

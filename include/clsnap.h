@@ -575,6 +575,68 @@ int cl_snapshot_crosstab_in(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const
                             const cl_crosstab_axis* a, const cl_crosstab_axis* b, int64_t* out, int64_t out_words);
 int cl_crosstab_time(cl_sim* sim, double* device_ms);
 
+/* ---- group-by over a tuple of snapshot quantities: which outcomes occur, and together? --------
+ * The census groups by the hash of one whole snapshot, the crosstab is joint over two binned
+ * quantities; this call is GROUP BY (q1, ..., qk) over the quantities a select clause names, possibly
+ * of different snapshot ids: exact, without bin edges, and sparse -- one row per tuple that occurs.
+ *
+ * Term.  (sid, field, index): `field` is one of CL_SEL_TICK .. CL_SEL_KEY with the meaning and the
+ * `index` rule it has in cl_select_clause; the value of a CL_SEL_KEY term is the snapshot content
+ * hash of `sid` (the census key), a uint64 bit pattern carried in an int64.  A call takes 1 to
+ * CL_GROUPS_MAX_TERMS terms, in the caller's order; they may name different snapshot ids.
+ *
+ * Sample.  The instances of [inst_lo, inst_hi) with status CL_INST_OK in which the snapshot of every
+ * term completed (cl_snapshot_groups_in: that are also members of `in`).  info->instances and
+ * info->ok count the range, as everywhere else.
+ *
+ * Group.  The sample instances with the same tuple of values, keyed by a 64-bit hash:
+ *   group_key(v[0 .. n)) = h, where h = 0x9E3779B97F4A7C15 ^ (uint64)n, then
+ *                          h = mix64(h ^ (uint64)v[k]) for k = 0 .. n - 1   (cl_group_key; mix64 is
+ *                          the finaliser of the snapshot content hash)
+ * Equality of groups here MEANS equality of that key: tuples are not compared, as the census does
+ * not compare snapshot contents.  Every key value, 0 and UINT64_MAX included, is a group.
+ *   groups     one cl_census_class per group: key, count, first_inst (smallest instance), and the min
+ *              and max completion tick OF terms[0].sid; ordered by count descending, then key
+ *              ascending (unsigned); the first n_returned = min(n_classes, max_classes) are written
+ *              (truncation is not an error; info->n_classes counts all groups)
+ *   values     values[g * n_terms + k] = term k evaluated on the device for group g's first_inst
+ *   group_of   (may be NULL) group_of[i - inst_lo] = index of instance i's group in the full order
+ *              (not clamped to n_returned), -1 outside the sample
+ *   spec       a cl_census_spec: max_classes = entries of `groups` and rows of `values`; lds_slots
+ *              as in the census
+ * The result does not depend on the grid, on lds_slots, on the record layout or on the exec kernel.
+ * Staging: adjacent terms of one snapshot id share one staged tile of its records; a term list that
+ * alternates between snapshot ids restages at every change, so keep the terms of one id together
+ * where the order is free.  A list of CL_SEL_TICK terms reads no records.
+ *
+ * Errors, all found before any device work, nothing written:
+ *   CL_E_INVALID  a NULL sim, term array, spec or info; n_terms outside [1, CL_GROUPS_MAX_TERMS]; a
+ *                 field outside CL_SEL_TICK .. CL_SEL_KEY, a non-zero reserved, an index out of range
+ *                 for its field; a bad spec (the census's rules); NULL groups or values with
+ *                 max_classes > 0; the instance range or any term's sid out of bounds; (_in) a NULL
+ *                 set or a set of another sim
+ *   CL_E_LIMIT    more than 2^29 instances in the range
+ *   CL_E_STATE    no event was ever issued
+ * Like the other result queries the call executes pending events and never adds a tick, holds the
+ * sim's lock and waits for a split replay's second half.  It shares the census's table scratch; the
+ * buffers it adds (representatives, values) are counted by cl_device_bytes.  cl_groups_time: device
+ * ms (HIP events) of the latest call's kernels, CL_E_STATE before any call or after an empty range.
+ * cl_group_key: the key of a tuple, host only (no sim). */
+#define CL_GROUPS_MAX_TERMS 8
+typedef struct { int32_t sid, field, index, reserved; } cl_group_term;   /* 16 B */
+int cl_snapshot_groups(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_group_term* terms, int32_t n_terms,
+                       const cl_census_spec* spec, cl_census_class* groups /* [max_classes] */,
+                       int64_t* values /* [max_classes][n_terms] */, int32_t* group_of /* [inst_hi - inst_lo] or NULL */,
+                       cl_census_info* info);
+int cl_snapshot_groups_in(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_iset* in, const cl_group_term* terms,
+                          int32_t n_terms, const cl_census_spec* spec, cl_census_class* groups, int64_t* values,
+                          int32_t* group_of, cl_census_info* info);
+int cl_groups_time(cl_sim* sim, double* device_ms);
+/* cl_groups_time split: stage_ms[5] = table initialisation, key pass, gather, group_of, values (0 for a
+ * stage the latest call did not run); their sum is cl_groups_time. */
+int cl_groups_stage_times(cl_sim* sim, double* stage_ms);
+uint64_t cl_group_key(const int64_t* values, int32_t n);
+
 /* ---- device event trace: the reference's debug Logger (logger.go:12-76) ---- */
 /* One LogEvent (logger.go:18-23) per record, in the Logger's order.  Node ranks refer
  * to cl_node_id; `other` is the peer of a Sent/Received record (-1 for Start/End and
