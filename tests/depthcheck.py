@@ -15,6 +15,9 @@ through send_tokens / start_snapshot / tick and reads queue_depths()
   and D).  Only a program built so that the full channel cannot pop in that tick may ask for
   it (in_tick=True): the walk then stops at the tick that left more than 255 packets queued.
 
+The graph engine's channels hold fifo_slots packets (cg_kernels.hip push_entry / push_q): its tests
+walk with limit=fifo_slots, and may draw their delays from the counter hash (counter_hash=seed).
+
 The walk ends like readEventsFile (test_common.go:123-137): ticks until every started snapshot
 has completed, then maxDelay + 1 more.
 """
@@ -69,10 +72,16 @@ class Walk:
         return int(self.before[event][self.channels.index((src, dest))])
 
 
-def walk(top, events, seed=None, schedule=None, drain=True, max_drain=10000, in_tick=False):
+def walk(top, events, seed=None, schedule=None, drain=True, max_drain=10000, in_tick=False, limit=LIMIT,
+         counter_hash=None):
+    """limit: the packets a channel holds (the graph engine's fifo_slots; default the node-parallel
+    kernel's 255).  Delays: an explicit schedule, the counter hash of seed `counter_hash`
+    (OracleSim.use_counter_hash), else the Go stream of `seed`."""
     ref = O.OracleSim()
     if schedule is not None:
         ref.use_schedule(schedule)
+    elif counter_hash is not None:
+        ref.use_counter_hash(counter_hash)
     else:
         ref.seed_go(seed)
     assert ref.read_topology_text(top) == 0
@@ -91,12 +100,12 @@ def walk(top, events, seed=None, schedule=None, drain=True, max_drain=10000, in_
         return d
 
     def tick(ei):
-        """One tick; True when it left more than 255 packets on a channel (in_tick only)."""
+        """One tick; True when it left more than `limit` packets on a channel (in_tick only)."""
         assert ref.tick() == 0
         d = depths()
-        if in_tick and d.max() > LIMIT:
+        if in_tick and d.max() > limit:
             return True, d
-        assert d.max() <= LIMIT, f"event {ei}: a tick left {d.max()} packets on a channel at time {ref.time}"
+        assert d.max() <= limit, f"event {ei}: a tick left {d.max()} packets on a channel at time {ref.time}"
         return False, d
 
     for ei, ev in enumerate(parse_events(events) if isinstance(events, str) else events):
@@ -104,14 +113,14 @@ def walk(top, events, seed=None, schedule=None, drain=True, max_drain=10000, in_
         before.append(d)
         if ev[0] == "send":
             c = index.get((ev[1], ev[2]))
-            if c is not None and d[c] >= LIMIT:
+            if c is not None and d[c] >= limit:
                 return Walk((ei, ref.time), peak, before, chans, ref)
             assert ref.send_tokens(ev[1], ev[2], ev[3]) == 0, f"event {ei}: send refused"
             if c is not None:
                 peak[c] = max(peak[c], d[c] + 1)
         elif ev[0] == "snapshot":
             mine = out_links.get(ev[1], [])
-            if any(d[c] >= LIMIT for c in mine):
+            if any(d[c] >= limit for c in mine):
                 return Walk((ei, ref.time), peak, before, chans, ref)
             assert ref.start_snapshot(ev[1])[0] == 0
             for c in mine:
