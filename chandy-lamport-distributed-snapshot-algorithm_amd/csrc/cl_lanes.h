@@ -289,7 +289,7 @@ __device__ __forceinline__ void pd_set(State<T>& s, int v, uint32_t sid, uint32_
 // delay exhaustion, then overflow; the node's last failing push sets nf.
 template <class T, bool SPILL>
 __device__ __forceinline__ void push(const Ctx& x, uint32_t& hw, uint32_t ch, bool on, uint32_t pl16, int32_t kd,
-                                     uint32_t delay, int32_t time, uint32_t& npush, int32_t& nf) {
+                                     uint32_t delay, int32_t time, int32_t& nf) {
   using Ld = Lds<T>;
   const uint32_t cnt = hw & 0x7fu;
   const bool dly_ok = kd < x.draws;
@@ -325,9 +325,35 @@ __device__ __forceinline__ void push(const Ctx& x, uint32_t& hw, uint32_t ch, bo
       if (p->spill_flag) p->spill_flag[x.inst] = 1;
     }
   }
-  hw += ok ? 1u : 0u;
-  (void)npush;  // (pushes are derived at the epilogue: pops + packets still queued)
+  hw += ok ? 1u : 0u;  // (the push count is derived at the epilogue: pops + packets still queued)
   nf = (on && !ok) ? (dly_ok ? (int32_t)ST_FIFO_OVERFLOW : (int32_t)ST_DELAY_EXHAUSTED) : nf;
+}
+
+// The guard of a broadcast's fast path.  push() asks two questions per link that are false for
+// almost every trigger: does the row still hold this draw, and is the ring full.  Both can be
+// asked once per trigger: is the broadcast's last draw past the row (k0 + od > draws), and does
+// the OR of the node's out-link head words have a bit of FULL, the count bits at or above the
+// ring's slots (a power of two: some count >= CAP).  On the deep-ring kernel the bound is the
+// layout's ring, so the probe's flag store stays in push().
+template <class T>
+struct Guard {
+  static constexpr uint32_t LIM = 1u << (T::PCAPL < T::CAPL ? T::PCAPL : T::CAPL);
+  static constexpr uint32_t FULL = 0x7fu & ~(LIM - 1u);
+};
+
+// The push that cannot fail (the guard held for every lane of the wave whose trigger is on), in
+// its two parts: the ring slot's per-lane address bits from the head word, and the entry.  No
+// draw or ring test, no status.  The callers store under the trigger's lane mask, so a lane whose
+// trigger is off stores nothing (a select against the scratch word per link, as push() has it,
+// compiled to 44 more VALU in the tick and 168 VGPRs), with the channel's constant
+// ch << (CAPL + 7) in the DS instruction's immediate offset as in phase A's read, and add the
+// trigger as a 0/1 integer to the head word.
+template <class T>
+__device__ __forceinline__ uint32_t sure_slot(const Ctx& x, uint32_t hw) {
+  return x.lb2 | ((hw + (hw << 7)) & Lds<T>::CAPM7);
+}
+__device__ __forceinline__ uint32_t sure_entry(uint32_t pl16, uint32_t delay, int32_t time) {
+  return pl16 | ((uint32_t)(time + 1 + (int32_t)delay) & 0xffu);
 }
 
 // CreateLocalSnapshot (node.go:58-84) at node v: record tokens and open every in-channel except
@@ -538,11 +564,17 @@ __device__ __forceinline__ bool tick(const Ctx& x, State<T>& s, bool act) {
     // gets its pushes in order.  The status: the lowest-ranked failing node's last failing push.
     uint32_t fv = 0xffu;
     int32_t fr = 0;
-    auto one = [&](auto vc) {
+    // A trigger's pushes take one of two paths, chosen for the whole wave by one guard per
+    // trigger (Guard): where no lane's broadcast can fail -- the row holds all its draws and
+    // none of the node's rings is at its bound -- the links run the push that cannot fail, the
+    // stores under the trigger's lane mask; else every lane runs push() with all of Queue.Push's
+    // failure bookkeeping, as before (mixed waves are exact by construction).  The further
+    // passes (FAST = false) always take push().
+    auto one = [&](auto vc, auto fastc) {
       constexpr int v = decltype(vc)::value;
+      constexpr bool FAST = decltype(fastc)::value != 0;
       if constexpr (T::od(v) > 0) {
         if (__ballot(tq[v] != 0)) {
-          int32_t nf = 0;
           const uint32_t q = tq[v];
           const bool on = q != 0;
           const uint32_t lb = q ? (uint32_t)__builtin_ctz(q) & 24u : 0u;  // 8 * in-link
@@ -560,25 +592,52 @@ __device__ __forceinline__ bool tick(const Ctx& x, State<T>& s, bool act) {
           const int32_t k0 = s.draw + (int32_t)o;
           const uint32_t dl = delays8<T>(x, k0);  // delays k0 .. k0 + 7, where they lie
           const uint32_t mpl = opaque(0x8000u | (sid << 8));  // the marker entry's high byte, once
+          bool hard = true;
+          if constexpr (FAST) {
+            uint32_t any = 0;
 #pragma unroll
-          for (int k = 0; k < D; ++k) {
-            if (k >= T::od(v)) continue;
-            push<T, SPILL>(x, s.hw[v][k], T::off(v) + k, on, mpl, k0 + k, (dl >> (4 * k)) & 15u, s.time, s.push,
-                           nf);
+            for (int k = 0; k < D; ++k)
+              if (k < T::od(v)) any |= s.hw[v][k];
+            hard = on && (k0 + T::od(v) > x.draws || (any & Guard<T>::FULL) != 0);
           }
-          const bool take = nf != 0 && (uint32_t)v <= fv;
-          fr = take ? nf : fr;
-          fv = take ? (uint32_t)v : fv;
+          if (!FAST || __builtin_expect(__ballot(hard) != 0, 0)) {
+            int32_t nf = 0;
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+              if (k >= T::od(v)) continue;
+              push<T, SPILL>(x, s.hw[v][k], T::off(v) + k, on, mpl, k0 + k, (dl >> (4 * k)) & 15u, s.time, nf);
+            }
+            const bool take = nf != 0 && (uint32_t)v <= fv;
+            fr = take ? nf : fr;
+            fv = take ? (uint32_t)v : fv;
+          } else {
+            uint32_t sl[D], en[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+              if (k >= T::od(v)) continue;
+              sl[k] = sure_slot<T>(x, s.hw[v][k]);
+              en[k] = sure_entry(mpl, (dl >> (4 * k)) & 15u, s.time);
+            }
+            if (on) {  // (stores only: no register is written under the lane mask)
+#pragma unroll
+              for (int k = 0; k < D; ++k)
+                if (k < T::od(v)) lds16_at(sl[k])[(T::off(v) + k) << (T::CAPL + 6)] = (uint16_t)en[k];
+            }
+            const uint32_t on01 = on ? 1u : 0u;
+#pragma unroll
+            for (int k = 0; k < D; ++k)
+              if (k < T::od(v)) s.hw[v][k] += on01;
+          }
         }
       }
     };
-    sfor<0, N>(one);
+    sfor<0, N>([&](auto vc) { one(vc, IC<1>{}); });
     for (;;) {
       uint32_t rest = 0;
 #pragma unroll
       for (int v = 0; v < N; ++v) rest |= tq[v];
       if (__builtin_expect(!__ballot(rest != 0), 1)) break;
-      sfor<0, N>(one);
+      sfor<0, N>([&](auto vc) { one(vc, IC<0>{}); });
     }
     s.flag = s.flag ? s.flag : fr;
     s.draw += (int32_t)acc;
@@ -627,7 +686,7 @@ __device__ __forceinline__ void send_one(const Ctx& x, State<T>& s, const Op& op
     for (int v = 0; v < T::N; ++v) o = v == a ? T::off(v) : o;
     return o;
   }();
-  push<T, SPILL>(x, hw, ch, go, (uint32_t)op.c << 8, s.draw, delays8<T>(x, s.draw) & 15u, s.time, s.push, nf);
+  push<T, SPILL>(x, hw, ch, go, (uint32_t)op.c << 8, s.draw, delays8<T>(x, s.draw) & 15u, s.time, nf);
   const uint32_t inc = hw - h0;  // 1 where the push landed
 #pragma unroll
   for (int v = 0; v < T::N; ++v) {
@@ -698,19 +757,40 @@ __device__ __forceinline__ void start_snapshot(const Ctx& x, State<T>& s, const 
     }
   }
   // SendToNeighbors (node.go:97-109): one push per out-link, draws in dest order
+  // One guard for the broadcast (Guard): where no lane's can fail, its links take the push that
+  // cannot fail, else push() as before.
   const uint32_t dl = delays8<T>(x, s.draw);
   int32_t nf = 0;
+  uint32_t any = 0;
 #pragma unroll
-  for (int k = 0; k < T::D; ++k) {
-    if (k >= od) continue;  // (uniform)
-    uint32_t hw = pick_hw(s, a, k);
-    const uint32_t h0 = hw;
-    push<T, SPILL>(x, hw, off + (uint32_t)k, on, 0x8000u | (sid << 8), s.draw + k, (dl >> (4 * k)) & 15u, s.time,
-                   s.push, nf);
-    const uint32_t inc = hw - h0;
+  for (int k = 0; k < T::D; ++k)
+    if (k < od) any |= pick_hw(s, a, k);
+  const bool hard = on && (s.draw + od > x.draws || (any & Guard<T>::FULL) != 0);
+  if (__builtin_expect(__ballot(hard) != 0, 0)) {
 #pragma unroll
-    for (int v = 0; v < T::N; ++v)
-      if (k < T::od(v)) s.hw[v][k] += v == a ? inc : 0u;
+    for (int k = 0; k < T::D; ++k) {
+      if (k >= od) continue;  // (uniform)
+      uint32_t hw = pick_hw(s, a, k);
+      const uint32_t h0 = hw;
+      push<T, SPILL>(x, hw, off + (uint32_t)k, on, 0x8000u | (sid << 8), s.draw + k, (dl >> (4 * k)) & 15u, s.time,
+                     nf);
+      const uint32_t inc = hw - h0;
+#pragma unroll
+      for (int v = 0; v < T::N; ++v)
+        if (k < T::od(v)) s.hw[v][k] += v == a ? inc : 0u;
+    }
+  } else {
+    const uint32_t on01 = on ? 1u : 0u;
+#pragma unroll
+    for (int k = 0; k < T::D; ++k) {
+      if (k >= od) continue;  // (uniform)
+      const uint32_t sl = sure_slot<T>(x, pick_hw(s, a, k)) + ((off + (uint32_t)k) << (T::CAPL + 7));
+      const uint32_t en = sure_entry(0x8000u | (sid << 8), (dl >> (4 * k)) & 15u, s.time);
+      if (on) *lds16_at(sl) = (uint16_t)en;
+#pragma unroll
+      for (int v = 0; v < T::N; ++v)
+        if (k < T::od(v)) s.hw[v][k] += v == a ? on01 : 0u;
+    }
   }
   s.flag = nf;
   if (s.alive) s.draw += op.c;
