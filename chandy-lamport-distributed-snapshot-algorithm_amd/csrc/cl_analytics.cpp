@@ -9,7 +9,6 @@
 #include <cstring>
 #include <vector>
 
-#include "cl_groups.h"
 #include "cl_host.h"
 
 using namespace clsnap;
@@ -97,6 +96,18 @@ struct Analytics {
                                       (int64_t)stats_blocks_per_cu(lds_bytes) * std::max(dev.n_cus, 1));
   }
 
+  // The four info words of a call that counted over n instances -- instances, OK, sample, and its
+  // matches or classes -- read back once the stream is idle; *done = 1 then (the call's first
+  // event pair is complete).  More matches or classes than instances are refused.
+  int read_info(const unsigned long long* d_info, int64_t n, const char* what, int* done, unsigned long long (&h)[4]) {
+    HIP_TRY(hipMemcpyAsync(h, d_info, sizeof h, hipMemcpyDeviceToHost, dev.stream));
+    HIP_TRY(hipStreamSynchronize(dev.stream));
+    if (done) *done = 1;
+    if ((int64_t)h[3] > n)
+      return set_err(CL_E_DEVICE, "%s: %lld matches or classes of %lld instances", what, (long long)h[3], (long long)n);
+    return CL_OK;
+  }
+
   // cl_snapshot_stats: the statistics of snapshot sid over [lo, hi) into out[L.total_words]
   // (arguments checked by the caller).  One kernel pass when the topology's N * rw record
   // words fit the LDS accumulator budget (stats_pass_words), else one pass per range of chunks;
@@ -112,9 +123,8 @@ struct Analytics {
     std::fill(h.begin() + L.max_begin, h.begin() + L.max_end, INT64_MIN);
     if ((rc = d_stats.ensure(h.size()))) return rc;
     HIP_TRY(hipMemcpyAsync(d_stats.p, h.data(), h.size() * sizeof(long long), hipMemcpyHostToDevice, stream));
+    p.tab = t;
     p.word_ch = t.word_ch;
-    p.hist_off = t.hist_off;
-    p.hist_pre = t.hist_pre;
     p.lay = L;
     p.out = d_stats.p;
     const int64_t tiles = p.s.tile_hi - p.s.tile_lo;
@@ -159,11 +169,9 @@ struct Analytics {
         (rc = d_cs_info.ensure(4)))
       return rc;
     if (class_of && ((rc = d_cs_keys.ensure((size_t)n)) || (rc = d_cs_class.ensure((size_t)n)))) return rc;
-    p->ch_slot = t.ch_slot;
-    p->hist_off = t.hist_off;
-    p->hist_val = t.hist_val;
+    p->tab = t;
     p->lds_slots = lds_slots;
-    p->staged = p->s.n_nodes * p->s.rw <= kCensusStageWords ? 1 : 0;
+    p->staged = sample_staged(p->s);
     p->empty_key = kCensusEmptyKey;
     // (tests move the marker onto a key that occurs, to run the extra entry's path)
     if (const char* v = std::getenv("CLSNAP_CENSUS_EMPTY_KEY")) p->empty_key = std::strtoull(v, nullptr, 0);
@@ -184,11 +192,8 @@ struct Analytics {
     const hipStream_t stream = dev.stream;
     int rc, e;
     unsigned long long h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, d_cs_info.p, sizeof h, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    tm.done = 1;
+    if ((rc = read_info(d_cs_info.p, n, what, &tm.done, h))) return rc;
     const int64_t k = (int64_t)h[3];
-    if (k > n) return set_err(CL_E_DEVICE, "%s: %lld classes of %lld instances", what, (long long)k, (long long)n);
     info->instances = (int64_t)h[0], info->ok = (int64_t)h[1], info->sample = (int64_t)h[2], info->n_classes = k;
     // ---- the k classes: compacted on the device, sorted here
     std::vector<CensusEntry> got((size_t)k);
@@ -276,7 +281,6 @@ struct Analytics {
     gr.done = grv.done = 0;
     if (n == 0) return CL_OK;
     if ((rc = table_begin(&p.c, t, n, lds_slots, group_of != nullptr))) return rc;
-    p.hist_pre = t.hist_pre;
     p.n_terms = n_terms;
     for (int32_t k = 0; k < n_terms; ++k) {
       std::memcpy(&p.term[k], &terms[k], sizeof(GroupTerm));
@@ -353,11 +357,8 @@ struct Analytics {
     const int64_t n = hi - lo;
     if (into && n == 0) return iset_clear(into);
     if (n == 0) return CL_OK;
-    p.ch_slot = t.ch_slot;
-    p.hist_off = t.hist_off;
-    p.hist_val = t.hist_val;
-    p.hist_pre = t.hist_pre;
-    p.staged = p.s.n_nodes * p.s.rw <= kCensusStageWords ? 1 : 0;
+    p.tab = t;
+    p.staged = sample_staged(p.s);
     p.n_clauses = n_clauses;
     for (int32_t q = 0; q < n_clauses; ++q) {
       std::memcpy(&p.clause[q], &clauses[q], sizeof(SelectClause));
@@ -390,11 +391,7 @@ struct Analytics {
       return set_err(CL_E_DEVICE, "select kernels: %s", hipGetErrorString((hipError_t)e));
     if ((rc = sel.mark(2, stream))) return rc;
     unsigned long long h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, d_sel_info.p, sizeof h, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    sel.done = 1;
-    if ((int64_t)h[3] > n)
-      return set_err(CL_E_DEVICE, "select: %lld matches of %lld instances", (long long)h[3], (long long)n);
+    if ((rc = read_info(d_sel_info.p, n, "select", &sel.done, h))) return rc;
     info->instances = (int64_t)h[0], info->ok = (int64_t)h[1], info->sample = (int64_t)h[2];
     info->n_match = (int64_t)h[3];
     info->n_returned = std::min<int64_t>(info->n_match, cap);
@@ -425,10 +422,8 @@ struct Analytics {
     h[XT_MAX_A] = h[XT_MAX_B] = INT64_MIN;
     if ((rc = d_xt.ensure(h.size()))) return rc;
     HIP_TRY(hipMemcpyAsync(d_xt.p, h.data(), h.size() * sizeof(long long), hipMemcpyHostToDevice, stream));
-    p.ch_slot = t.ch_slot;
-    p.hist_off = t.hist_off;
-    p.hist_pre = t.hist_pre;
-    p.staged = p.s.n_nodes * p.s.rw <= kCensusStageWords ? 1 : 0;
+    p.tab = t;
+    p.staged = sample_staged(p.s);
     p.out = d_xt.p;
     const int64_t tiles = p.s.tile_hi - p.s.tile_lo;
     const bool reads_records = a->field != SEL_TICK || b->field != SEL_TICK;
@@ -563,10 +558,7 @@ struct Analytics {
     if (e) return set_err(CL_E_DEVICE, "instance set kernels: %s", hipGetErrorString((hipError_t)e));
     if ((rc = iset_time_end())) return rc;
     unsigned long long h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h, d_sel_info.p, sizeof h, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if ((int64_t)h[3] > hi - lo)
-      return set_err(CL_E_DEVICE, "instance set: %lld members of %lld instances", (long long)h[3], (long long)(hi - lo));
+    if ((rc = read_info(d_sel_info.p, hi - lo, "instance set", nullptr, h))) return rc;
     *n_match = (int64_t)h[3];
     const int64_t k = std::min<int64_t>(*n_match, cap);
     if (k > 0) HIP_TRY(hipMemcpy(insts, d_sel_out.p, (size_t)k * sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -695,7 +687,7 @@ static int census_call(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_h
 
 static_assert(sizeof(cl_group_term) == sizeof(GroupTerm) && sizeof(GroupTerm) == 16 &&
                   CL_GROUPS_MAX_TERMS == kGroupsMaxTerms,
-              "cl_group_term and CL_GROUPS_MAX_TERMS mirror cl_groups.h");
+              "cl_group_term and CL_GROUPS_MAX_TERMS mirror cl_analytics.h");
 
 // cl_snapshot_groups, and cl_snapshot_groups_in with its set (`conditional`).
 static int groups_call(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, bool conditional, const cl_iset* in,
@@ -710,11 +702,10 @@ static int groups_call(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, bool condi
   const SimFacts f = sim_facts(sim);
   for (int32_t k = 0; k < n_terms; ++k) {
     const cl_group_term& z = terms[k];
-    if (z.field < 0 || z.field >= SEL_NUM_FIELDS || z.reserved)
-      return set_err(CL_E_INVALID, "groups term %d: unknown field or non-zero reserved", k);
-    const int64_t bound =
-        z.field == CL_SEL_NODE ? f.n_nodes : z.field == CL_SEL_CH_MSGS || z.field == CL_SEL_CH_TOK ? f.n_ch : 1;
-    if (z.index < 0 || z.index >= bound) return set_err(CL_E_INVALID, "groups term %d: index %d out of range", k, z.index);
+    if (z.reserved) return set_err(CL_E_INVALID, "groups term %d: non-zero reserved", k);
+    if (!quantity_ok(z.field, z.index, SEL_KEY, f.n_nodes, f.n_ch))
+      return set_err(CL_E_INVALID, "groups term %d: unknown field %d, or index %d out of range", k, z.field,
+                     z.index);
   }
   if (!spec || !info) return set_err(CL_E_INVALID, "null groups spec or info");
   if (const int rc = census_spec_ok(spec, "groups")) return rc;
@@ -740,7 +731,7 @@ static int groups_call(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, bool condi
 static_assert(sizeof(cl_select_clause) == sizeof(SelectClause) && sizeof(SelectClause) == 32,
               "cl_select_clause mirrors SelectClause");
 static_assert(CL_SELECT_MAX_CLAUSES == kSelMaxClauses && CL_SEL_KEY == SEL_KEY && CL_SEL_NOT == kSelNot,
-              "CL_SEL_* mirror cl_engine.h");
+              "CL_SEL_* mirror cl_analytics.h");
 
 // cl_select_instances; cl_select_instances_in with its set (`conditional`); cl_iset_from_clauses
 // with the set that takes the matches (`into`: no list, cap 0).
@@ -756,11 +747,11 @@ static int select_call(cl_sim* sim, int32_t sid, int64_t inst_lo, int64_t inst_h
   const SimFacts f = sim_facts(sim);
   for (int32_t q = 0; q < n_clauses; ++q) {
     const cl_select_clause& z = clauses[q];
-    if (z.field < 0 || z.field >= SEL_NUM_FIELDS || (z.flags & ~CL_SEL_NOT) || z.reserved)
-      return set_err(CL_E_INVALID, "select clause %d: unknown field or flag bits, or non-zero reserved", q);
-    const int64_t bound =
-        z.field == CL_SEL_NODE ? f.n_nodes : z.field == CL_SEL_CH_MSGS || z.field == CL_SEL_CH_TOK ? f.n_ch : 1;
-    if (z.index < 0 || z.index >= bound) return set_err(CL_E_INVALID, "select clause %d: index %d out of range", q, z.index);
+    if ((z.flags & ~CL_SEL_NOT) || z.reserved)
+      return set_err(CL_E_INVALID, "select clause %d: unknown flag bits or non-zero reserved", q);
+    if (!quantity_ok(z.field, z.index, SEL_KEY, f.n_nodes, f.n_ch))
+      return set_err(CL_E_INVALID, "select clause %d: unknown field %d, or index %d out of range", q, z.field,
+                     z.index);
   }
   if (cap < 0 || (cap > 0 && !insts)) return set_err(CL_E_INVALID, "select: cap >= 0, with an index array when cap > 0");
   if (const int rc = sample_args_ok(sim, sid, inst_lo, inst_hi)) return rc;
@@ -772,16 +763,14 @@ static_assert(sizeof(cl_crosstab_axis) == sizeof(CrosstabAxis) && sizeof(Crossta
               "cl_crosstab_axis mirrors CrosstabAxis");
 static_assert(CL_CROSSTAB_MAX_BINS == kXtMaxBins && CL_CROSSTAB_MAX_CELLS == kXtMaxCells && CL_XT_SUM_A == XT_SUM_A &&
                   CL_XT_MIN_A == XT_MIN_A && CL_XT_MAX_A == XT_MAX_A && CL_XT_CELLS == XT_CELLS,
-              "CL_CROSSTAB_* and CL_XT_* mirror cl_engine.h");
+              "CL_CROSSTAB_* and CL_XT_* mirror cl_analytics.h");
 
 static int crosstab_axis_ok(const SimFacts& f, const cl_crosstab_axis* z, const char* name) {
   if (!z) return set_err(CL_E_INVALID, "crosstab: null axis %s", name);
-  // (CL_SEL_KEY is a select field only: a hash is not binnable)
-  if (z->field < CL_SEL_TICK || z->field > CL_SEL_CH_TOK)
-    return set_err(CL_E_INVALID, "crosstab axis %s: field %d is not one of CL_SEL_TICK .. CL_SEL_CH_TOK", name, z->field);
-  const int64_t bound =
-      z->field == CL_SEL_NODE ? f.n_nodes : z->field == CL_SEL_CH_MSGS || z->field == CL_SEL_CH_TOK ? f.n_ch : 1;
-  if (z->index < 0 || z->index >= bound) return set_err(CL_E_INVALID, "crosstab axis %s: index %d out of range", name, z->index);
+  // (CL_SEL_KEY is not an axis: a hash is not binnable)
+  if (!quantity_ok(z->field, z->index, SEL_CH_TOK, f.n_nodes, f.n_ch))
+    return set_err(CL_E_INVALID, "crosstab axis %s: field %d is not one of CL_SEL_TICK .. CL_SEL_CH_TOK, or index %d "
+                   "out of range", name, z->field, z->index);
   if (z->bins < 1 || z->bins > CL_CROSSTAB_MAX_BINS || z->width < 1)
     return set_err(CL_E_INVALID, "crosstab axis %s: 1 <= bins <= %d, width >= 1", name, CL_CROSSTAB_MAX_BINS);
   return CL_OK;
@@ -809,7 +798,7 @@ static int crosstab_call(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, bool con
 }
 
 static_assert(CL_ISET_AND == ISET_AND && CL_ISET_OR == ISET_OR && CL_ISET_ANDNOT == ISET_ANDNOT,
-              "CL_ISET_* mirror cl_engine.h");
+              "CL_ISET_* mirror cl_analytics.h");
 
 static int iset_range_ok(const cl_iset* s, int64_t lo, int64_t hi) {
   if (lo < 0 || hi > sim_facts(s->sim).n_inst || lo > hi) return set_err(CL_E_INVALID, "instance range out of range");

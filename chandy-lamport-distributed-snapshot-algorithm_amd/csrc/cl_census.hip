@@ -25,7 +25,6 @@
 #include <hip/hip_runtime.h>
 
 #include "cl_census_table.h"
-#include "cl_engine.h"
 #include "cl_sample.h"
 
 namespace clsnap {
@@ -62,8 +61,7 @@ __global__ __launch_bounds__(kCensusThreads) void cl_census_keys(CensusParams p)
     if (!l.sample) continue;
 
     // ---- the key: cl_checksum_kernel's arithmetic for one snapshot id
-    const unsigned long long key = snapshot_key(p.s.sid, p.s.n_nodes, p.s.rw, p.s.n_ch, p.ch_slot, p.hist_off,
-                                                p.hist_val, RecordRow(p.s, t, lane, L.tile, p.staged));
+    const unsigned long long key = record_key(p.s, p.tab, p.s.sid, RecordRow(p.s, t, lane, L.tile, p.staged));
     if (p.keys) {
       p.keys[inst - p.s.lo] = key;
       p.class_of[inst - p.s.lo] = 0;
@@ -110,8 +108,7 @@ int launch_census_init(const CensusParams& p, void* stream) {
 
 int launch_census_keys(const CensusParams& p, int32_t blocks, void* stream) {
   const size_t lds = (size_t)census_lds_bytes(p.lds_slots, p.staged != 0);
-  if (lds > (size_t)kMaxLdsBytes || blocks < 1) return (int)hipErrorInvalidValue;
-  if (p.staged && p.s.n_nodes * p.s.rw > kCensusStageWords) return (int)hipErrorInvalidValue;
+  if (lds > (size_t)kMaxLdsBytes || blocks < 1 || !staged_ok(p.s, p.staged)) return (int)hipErrorInvalidValue;
   if (lds > 64 * 1024) {
     const hipError_t e =
         hipFuncSetAttribute((const void*)cl_census_keys, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);

@@ -12,7 +12,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "cl_engine.h"
 #include "cl_sample.h"
 
 namespace clsnap {

@@ -1,17 +1,15 @@
 // cl_crosstab.hip -- joint distribution of two snapshot quantities of the batch engine
 // (cl_snapshot_crosstab).
 //
-// A two-axis contingency table with the five joint moments.  An axis names one of the quantities a
-// select clause names (completion tick, a node's tokenMap entry, a channel's recorded messages or
-// tokens, the instance's totals) of one snapshot id; the two axes may belong to different snapshot
-// ids.  The sample is the instances of [lo, hi) with status OK in which the snapshots of both axes
-// completed -- of the members of an instance set when one is given.  All integer, so the result
-// does not depend on the grid, the record layout or the exec kernel.
+// A two-axis contingency table with the five joint moments.  An axis names a quantity of a snapshot
+// (cl_quantity.h; any field but the key, which is not binnable); the two axes may belong to
+// different snapshot ids.  The sample is the instances of [lo, hi) with status OK in which the
+// snapshots of both axes completed -- of the members of an instance set when one is given.  All
+// integer, so the result does not depend on the grid, the record layout or the exec kernel.
 //
-// One walk (cl_sample.h), lane = slot.  The two axes see the same walk through two views of
-// SampleParams that differ in `sid` only: sample_lane() classifies the slot for axis a's snapshot,
-// the lane then reads the completion tick of axis b's.  The slot -> instance map of block-major
-// records is shared by all snapshot planes, so tile t names the same 64 instances in both.
+// One walk (cl_sample.h), lane = slot.  The two axes see the same walk through two views of it
+// (cl_quantity.h sample_view): sample_lane() classifies the slot for axis a's snapshot, the lane
+// then reads the completion tick of axis b's (view_tick).
 //
 // One staging tile per wave.  An axis that reads records gets its plane's tile staged in LDS when
 // the records have at most kCensusStageWords words (stage_tile), else its lane reads word by word
@@ -27,36 +25,12 @@
 // refuses walks of 2^32 slots or more, so no counter is flushed before the end.
 #include <hip/hip_runtime.h>
 
-#include "cl_engine.h"
-#include "cl_sample.h"
+#include "cl_quantity.h"
 
 namespace clsnap {
 namespace {
 
 __device__ __forceinline__ bool axis_reads_records(const CrosstabAxis& z) { return z.field != SEL_TICK; }
-
-// The value of axis z for the lane's instance: its completion tick, or what the axis names of the
-// record rb reads.
-__device__ __forceinline__ long long axis_value(const CrosstabParams& p, const CrosstabAxis& z, const RecordRow& rb,
-                                                int32_t tick) {
-  switch (z.field) {
-    case SEL_NODE: return (int32_t)rb(z.index * p.s.rw);
-    case SEL_CH_MSGS: return (long long)rec_msgs(rb(p.ch_slot[z.index]));
-    case SEL_CH_TOK: return rec_tokens(rb(p.ch_slot[z.index]), token_prefix(p.hist_pre, p.hist_off, z.index));
-    case SEL_MSGS: {
-      long long msgs = 0;
-      for (int32_t c = 0; c < p.s.n_ch; ++c) msgs += (long long)rec_msgs(rb(p.ch_slot[c]));
-      return msgs;
-    }
-    case SEL_INFLIGHT: {
-      long long infl = 0;
-      for (int32_t c = 0; c < p.s.n_ch; ++c)
-        infl += rec_tokens(rb(p.ch_slot[c]), token_prefix(p.hist_pre, p.hist_off, c));
-      return infl;
-    }
-    default: return tick;
-  }
-}
 
 // bin(v) = v < lo ? 0 : min((uint64)(v - lo) / width, bins - 1); the subtraction only when v >= lo,
 // so it is exact for every int64 lo.  (width is uniform over the grid: width 1 skips the 64-bit divide)
@@ -82,9 +56,7 @@ __global__ __launch_bounds__(kXtThreads) void cl_crosstab_kernel(CrosstabParams 
   for (int32_t i = threadIdx.x; i < n_cells; i += kXtThreads) cells[i] = 0;
   __syncthreads();
 
-  // the view of axis b's snapshot: the same walk, another plane
-  SampleParams sb = p.s;
-  sb.sid = p.b.sid;
+  const SampleParams sb = sample_view(p.s, p.b.sid);  // axis b's snapshot: the same walk, another plane
   const bool same_sid = p.a.sid == p.b.sid;
   const bool rec_a = axis_reads_records(p.a), rec_b = axis_reads_records(p.b);
 
@@ -95,7 +67,7 @@ __global__ __launch_bounds__(kXtThreads) void cl_crosstab_kernel(CrosstabParams 
   for (int64_t t = sample_first_tile(p.s, wave); t < p.s.tile_hi; t += sample_tile_stride()) {
     SampleLane l = sample_lane(p.s, t, lane);
     int32_t tick_b = -1;
-    if (l.sample) tick_b = same_sid ? l.tick : p.s.snap_tick[l.inst * p.s.s_cap + p.b.sid];
+    if (l.sample) tick_b = view_tick(p.s, l, p.b.sid);
     l.sample = l.sample && tick_b >= 0;  // both snapshots completed
     counts.add(l);
     if (__ballot(l.sample) == 0) continue;  // (wave-uniform)
@@ -103,12 +75,16 @@ __global__ __launch_bounds__(kXtThreads) void cl_crosstab_kernel(CrosstabParams 
     long long va = l.tick, vb = tick_b;
     if (rec_a) {
       if (p.staged) stage_tile(p.s, t, whole_record_chunk(p.s), tile, lane);
-      if (l.sample) va = axis_value(p, p.a, RecordRow(p.s, t, lane, tile, p.staged), l.tick);
+      if (l.sample)
+        va = quantity_value<SEL_CH_TOK>(p.s, p.tab, p.a.sid, p.a.field, p.a.index,
+                                        RecordRow(p.s, t, lane, tile, p.staged), l.tick);
     }
     if (rec_b) {
       // (the tile still holds this plane when axis a staged the same snapshot)
       if (p.staged && !(rec_a && same_sid)) stage_tile(sb, t, whole_record_chunk(sb), tile, lane);
-      if (l.sample) vb = axis_value(p, p.b, RecordRow(sb, t, lane, tile, p.staged), tick_b);
+      if (l.sample)
+        vb = quantity_value<SEL_CH_TOK>(sb, p.tab, p.b.sid, p.b.field, p.b.index,
+                                        RecordRow(sb, t, lane, tile, p.staged), tick_b);
     }
 
     if (l.sample) {
@@ -167,14 +143,11 @@ int launch_crosstab(const CrosstabParams& p, int32_t blocks, void* stream) {
   if (blocks < 1 || p.a.bins < 1 || p.b.bins < 1 || p.a.bins > kXtMaxBins || p.b.bins > kXtMaxBins ||
       cells > kXtMaxCells || p.a.width < 1 || p.b.width < 1 || p.s.sid != p.a.sid)
     return (int)hipErrorInvalidValue;
-  const auto axis_ok = [&p](const CrosstabAxis& z) {
-    const int32_t bound = z.field == SEL_NODE ? p.s.n_nodes : z.field == SEL_CH_MSGS || z.field == SEL_CH_TOK ? p.s.n_ch : 1;
-    return z.field >= SEL_TICK && z.field <= SEL_CH_TOK && z.index >= 0 && z.index < bound && z.sid >= 0 &&
-           z.sid < p.s.s_cap;
+  const auto axis_ok = [&p](const CrosstabAxis& z) {  // (a key is not binnable: the fields end at SEL_CH_TOK)
+    return quantity_ok(z.field, z.index, SEL_CH_TOK, p.s.n_nodes, p.s.n_ch) && z.sid >= 0 && z.sid < p.s.s_cap;
   };
-  if (!axis_ok(p.a) || !axis_ok(p.b)) return (int)hipErrorInvalidValue;
+  if (!axis_ok(p.a) || !axis_ok(p.b) || !staged_ok(p.s, p.staged)) return (int)hipErrorInvalidValue;
   const bool staged = p.staged != 0 && (p.a.field != SEL_TICK || p.b.field != SEL_TICK);
-  if (p.staged && p.s.n_nodes * p.s.rw > kCensusStageWords) return (int)hipErrorInvalidValue;
   // the bound that keeps a workgroup's 32-bit cell counters from wrapping
   if (p.s.tile_hi - p.s.tile_lo >= ((int64_t)1 << 32) / 64) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)crosstab_lds_bytes((int32_t)cells, staged);

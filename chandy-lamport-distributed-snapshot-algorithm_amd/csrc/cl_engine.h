@@ -410,182 +410,6 @@ int launch_pack_fill(const PackParams& p, void* stream);
 // out[0] all instances, out[1] status-OK instances.
 int launch_recorded(const SumParams& p, void* stream);
 
-// ---- per-snapshot batch statistics (cl_stats.hip; include/clsnap.h cl_snapshot_stats) ----------
-// Offsets, in int64 words, of every field of the flat result: mirrors cl_stats_layout field by
-// field (cl_host.cpp asserts the sizes agree).
-struct StatsLayout {
-  int64_t n_nodes, n_channels, tick_lo, tick_bins, msg_bins;
-  int64_t total_words, sum_begin, sum_end, min_begin, min_end, max_begin, max_end;
-  int64_t instances, ok, sample, tick_sum, tick_sumsq, tick_hist, msgs_sum, msgs_sumsq, inflight_sum,
-      inflight_sumsq, node_sum, node_sumsq, ch_msgs_sum, ch_msgs_sumsq, ch_tok_sum, ch_tok_sumsq, ch_msg_hist;
-  int64_t min_tick, min_msgs, min_inflight, min_node, min_ch_msgs, min_ch_tok;
-  int64_t max_tick, max_msgs, max_inflight, max_node, max_ch_msgs, max_ch_tok;
-};
-inline StatsLayout stats_layout(int64_t N, int64_t C, int64_t tick_lo, int64_t T, int64_t M) {
-  StatsLayout L{};
-  L.n_nodes = N, L.n_channels = C, L.tick_lo = tick_lo, L.tick_bins = T, L.msg_bins = M;
-  int64_t o = 0;
-  auto take = [&o](int64_t n) { const int64_t at = o; o += n; return at; };
-  L.sum_begin = o;
-  L.instances = take(1), L.ok = take(1), L.sample = take(1);
-  L.tick_sum = take(1), L.tick_sumsq = take(1), L.tick_hist = take(T);
-  L.msgs_sum = take(1), L.msgs_sumsq = take(1), L.inflight_sum = take(1), L.inflight_sumsq = take(1);
-  L.node_sum = take(N), L.node_sumsq = take(N);
-  L.ch_msgs_sum = take(C), L.ch_msgs_sumsq = take(C), L.ch_tok_sum = take(C), L.ch_tok_sumsq = take(C);
-  L.ch_msg_hist = take(C * M);
-  L.sum_end = L.min_begin = o;
-  L.min_tick = take(1), L.min_msgs = take(1), L.min_inflight = take(1);
-  L.min_node = take(N), L.min_ch_msgs = take(C), L.min_ch_tok = take(C);
-  L.min_end = L.max_begin = o;
-  L.max_tick = take(1), L.max_msgs = take(1), L.max_inflight = take(1);
-  L.max_node = take(N), L.max_ch_msgs = take(C), L.max_ch_tok = take(C);
-  L.max_end = L.total_words = o;
-  return L;
-}
-
-// The statistics kernel walks the records in tiles of 64 record slots x one chunk of record
-// words, staged in LDS.  A chunk is at most kStatsChunkWords words of every instance: whole node
-// records (rw <= kStatsChunkWords) or a piece of one node's record.  Chunk i covers the words
-// [word0, word0 + nv * kw) of an instance's N * rw record words.
-constexpr int32_t kStatsChunkWords = 32;
-constexpr int32_t kStatsThreads = 256;
-// LDS budget of one statistics workgroup (dynamic LDS, no opt-in needed; at least two workgroups
-// share a CU's 160 KB, more when the pass needs less): the staging tiles of its 4 waves, the tick histogram, and per record word of
-// the pass 8 int64 accumulators and msg_bins histogram counters.  Topologies whose N * rw
-// words do not fit run as several passes over chunk ranges (cl_host.cpp stats()).
-constexpr int32_t kStatsLdsBytes = 64 * 1024;
-constexpr int32_t kStatsStageWords = kWave * (kStatsChunkWords + 1);  // per wave, rows padded odd
-constexpr int32_t kStatsScalars = 16;                                  // int64 words (15 used)
-struct StatsChunk {
-  int32_t v0, nv, k0, kw;
-};
-#if defined(__HIPCC__)
-__host__ __device__
-#endif
-inline int32_t stats_chunks(int32_t n_nodes, int32_t rw) {
-  if (rw <= kStatsChunkWords) {
-    const int32_t g = kStatsChunkWords / rw;
-    return (n_nodes + g - 1) / g;
-  }
-  return n_nodes * ((rw + kStatsChunkWords - 1) / kStatsChunkWords);
-}
-#if defined(__HIPCC__)
-__host__ __device__
-#endif
-inline StatsChunk stats_chunk(int32_t n_nodes, int32_t rw, int32_t i) {
-  StatsChunk c;
-  if (rw <= kStatsChunkWords) {
-    const int32_t g = kStatsChunkWords / rw;
-    c.v0 = i * g;
-    c.nv = n_nodes - c.v0 < g ? n_nodes - c.v0 : g;
-    c.k0 = 0;
-    c.kw = rw;
-  } else {
-    const int32_t pieces = (rw + kStatsChunkWords - 1) / kStatsChunkWords;
-    c.v0 = i / pieces;
-    c.nv = 1;
-    c.k0 = (i % pieces) * kStatsChunkWords;
-    c.kw = rw - c.k0 < kStatsChunkWords ? rw - c.k0 : kStatsChunkWords;
-  }
-  return c;
-}
-// Record words a pass may accumulate within the LDS budget (>= kStatsChunkWords for every legal
-// spec: 4096 tick bins, 64 message bins leave 47).
-inline int32_t stats_pass_words(int32_t tick_bins, int32_t msg_bins) {
-  const int32_t fixed = kWavesPerBlock * kStatsStageWords * 4 + tick_bins * 4 + kStatsScalars * 8;
-  return (kStatsLdsBytes - fixed) / (8 * 8 + msg_bins * 4);
-}
-// LDS bytes of a workgroup whose pass accumulates acc_words record words.
-inline int32_t stats_lds_bytes(int32_t acc_words, int32_t tick_bins, int32_t msg_bins) {
-  return kWavesPerBlock * kStatsStageWords * 4 + tick_bins * 4 + kStatsScalars * 8 + acc_words * (8 * 8 + msg_bins * 4);
-}
-// Workgroups per CU the grid is sized for: what the CU's LDS holds of them, at most 8 (32 waves).
-inline int32_t stats_blocks_per_cu(int32_t lds_bytes) {
-  const int32_t b = kMaxLdsBytes / (lds_bytes > 0 ? lds_bytes : 1);
-  return b < 1 ? 1 : b > 8 ? 8 : b;
-}
-
-// The sample of the analytics calls (statistics, census, select) and the planes their kernels walk
-// for it: the instances of [lo, hi) with status OK in which snapshot `sid` completed -- and, for the
-// conditional calls (cl_*_in), that are members of the instance set `where`.  The walk itself is
-// cl_sample.h's (device code; this header is also compiled into the run-time lanes kernel and
-// holds declarations only).
-struct SampleParams {
-  int32_t n_nodes, n_ch, s_cap, rw, sid;
-  int64_t n_inst, stride;
-  int64_t lo, hi;            // the sample's instance range
-  int64_t tile_lo, tile_hi;  // 64-slot tiles to walk (instance-major: those overlapping [lo, hi))
-  const int32_t* regs;
-  const int32_t* snap_tick;
-  const uint32_t* snap_nod;
-  int32_t blocked;           // records block-major by slot (rec_word)
-  const int32_t* inst_map;   // slot -> instance of a block-major replay (nullptr: identity)
-  // An instance set's bitmap (cl_iset: bit inst & 63 of word inst >> 6, stride / 64 words): only its
-  // members are in the sample; the instances / OK counters still count the range.  nullptr: no filter.
-  const unsigned long long* where;
-};
-
-struct StatsParams {
-  SampleParams s;
-  const int32_t* word_ch;    // [N * rw] record word -> channel, -2 token word, -1 padding
-  const int32_t* hist_off;   // [C + 1]
-  const long long* hist_pre; // prefix sums of the token histories: channel c at hist_off[c] + c
-  int32_t chunk_lo, chunk_hi;  // chunks whose words this pass accumulates
-  int32_t totals;              // this pass also takes the counts, tick, msgs and inflight
-  int32_t acc_words;           // record words of the pass (LDS accumulator rows)
-  StatsLayout lay;
-  long long* out;  // [lay.total_words], initialised by the host (0 / INT64_MAX / INT64_MIN)
-};
-int launch_stats(const StatsParams& p, int32_t blocks, void* stream);
-
-// ---- snapshot outcome census (cl_census.hip; include/clsnap.h cl_snapshot_census) --------------
-// A group-by of the snapshot content hash over the sample of cl_snapshot_stats.  One entry of the
-// global open-addressing table, and of the compacted class array (the layout of cl_census_class).
-struct CensusEntry {
-  unsigned long long key;
-  unsigned long long count;  // (the class's rank, once the host has sorted: cl_census_rank)
-  long long first;           // smallest instance of the class
-  int32_t min_tick, max_tick;
-};
-// The table's "empty" marker.  A snapshot whose key has this value is a class like any other: it
-// bypasses the hashed slots and lives in the extra entry table[slots] (CensusParams::empty_key).
-constexpr unsigned long long kCensusEmptyKey = ~0ULL;
-constexpr int32_t kCensusThreads = 256;
-constexpr int32_t kCensusMinLdsSlots = 16, kCensusMaxLdsSlots = 4096;
-// The engine's choice of workgroup table: with the staging tiles it stays below 64 KB of LDS, so
-// two workgroups and more share a CU (the scenarios measured have 2 .. 413 classes).
-constexpr int32_t kCensusAutoLdsSlots = 1024;
-// Probes before an LDS insert gives up and goes to the global table (a full or crowded table).
-constexpr int32_t kCensusLdsProbes = 16;
-// Records of at most this many words per instance are staged in LDS tile by tile (address-ordered
-// loads, cl_stats.hip's pattern); longer ones are read word by word by the instance's lane.
-constexpr int32_t kCensusStageWords = kStatsChunkWords;
-constexpr int32_t kCensusLdsEntryBytes = 8 + 8 + 4 + 4 + 4;  // key, first, count, min tick, max tick
-inline int32_t census_lds_bytes(int32_t lds_slots, bool staged) {
-  return lds_slots * kCensusLdsEntryBytes + 4 * 8 + (staged ? kWavesPerBlock * kStatsStageWords * 4 : 0);
-}
-struct CensusParams {
-  SampleParams s;
-  const int32_t* ch_slot;    // [C] record word of channel c
-  const int32_t* hist_off;   // [C + 1]
-  const int32_t* hist_val;
-  int32_t lds_slots;         // workgroup table entries (a power of two), 0: none
-  int32_t staged;            // N * rw <= kCensusStageWords: records staged in LDS
-  unsigned long long empty_key;
-  CensusEntry* table;        // [slots + 1], initialised by launch_census_init
-  int64_t slots;             // a power of two >= 2 * (hi - lo)
-  uint32_t* list;            // [hi - lo] table slots in the order they were claimed
-  unsigned long long* info;  // instances, ok, sample, n_classes
-  unsigned long long* keys;  // [hi - lo] each sample instance's key, or nullptr
-  int32_t* class_of;         // [hi - lo] 0 for sample instances, -1 for the others (with keys)
-};
-int launch_census_init(const CensusParams& p, void* stream);
-int launch_census_keys(const CensusParams& p, int32_t blocks, void* stream);
-// out[j] = table[list[j]], j < n
-int launch_census_gather(const CensusParams& p, int64_t n, CensusEntry* out, void* stream);
-// table[list[j]].count = rank[j], j < n; then class_of[i] = rank of keys[i]'s class
-int launch_census_class_of(const CensusParams& p, int64_t n, const int32_t* rank, void* stream);
-
 // Snapshot content hash (shared definition with oracle/cl_oracle.c orc_snapshot_hash).
 #if defined(__HIPCC__)
 __host__ __device__
@@ -615,100 +439,5 @@ inline uint64_t snapshot_key(int32_t sid, int32_t n_nodes, int32_t rw, int32_t n
   }
   return h;
 }
-
-// ---- instance selection by snapshot predicate (cl_select.hip; include/clsnap.h cl_select_instances) ----
-// A conjunction of range clauses over the per-instance quantities the statistics reduce, evaluated
-// over the sample of cl_snapshot_stats; the matches come back as ascending instance indices.
-enum : int32_t {
-  SEL_TICK = 0, SEL_MSGS = 1, SEL_INFLIGHT = 2, SEL_NODE = 3, SEL_CH_MSGS = 4, SEL_CH_TOK = 5, SEL_KEY = 6,
-  SEL_NUM_FIELDS = 7,
-};
-constexpr int32_t kSelNot = 1;
-constexpr int32_t kSelMaxClauses = 8;
-constexpr int32_t kSelThreads = 256;
-// Words (64 verdict bits each) one workgroup of the compaction counts and fills: one per thread.
-constexpr int32_t kSelBlockWords = kSelThreads;
-struct SelectClause {  // the layout of cl_select_clause
-  int32_t field, index, flags, reserved;
-  int64_t lo, hi;
-};
-struct SelectParams {
-  SampleParams s;
-  const int32_t* ch_slot;    // [C] record word of channel c
-  const int32_t* hist_off;   // [C + 1]
-  const int32_t* hist_val;
-  const long long* hist_pre; // as StatsParams::hist_pre
-  int32_t staged;            // N * rw <= kCensusStageWords: records staged in LDS
-  int32_t n_clauses;
-  int32_t need_records;      // a clause reads the records (any field but SEL_TICK)
-  int32_t need_totals;       // a clause names SEL_MSGS or SEL_INFLIGHT
-  int32_t need_key;          // a clause names SEL_KEY
-  SelectClause clause[kSelMaxClauses];
-  // Verdict bitmap: bit (inst - base) & 63 of word (inst - base) >> 6, base = lo rounded down to a
-  // multiple of 64 (so an instance-major tile is one word).  Block-major: zeroed before the pass.
-  int64_t base, words;
-  unsigned long long* bitmap;  // [words]
-  unsigned long long* info;    // instances, ok, sample, n_match
-  // compaction: block b counts / fills words [b * kSelBlockWords, ...)
-  long long* bsum;             // [ceil(words / kSelBlockWords)] block totals -> exclusive prefix
-  int64_t cap;                 // entries of out (and ticks) the fill may write
-  long long* out;              // [cap] matching instances, ascending
-  int32_t* ticks;              // [cap] their completion ticks, or nullptr
-};
-inline int32_t select_lds_bytes(bool staged) {
-  return 4 * 8 + (staged ? kWavesPerBlock * kStatsStageWords * 4 : 0);
-}
-int launch_select_eval(const SelectParams& p, int32_t blocks, void* stream);
-// count + scan (n_match left in p.info[3]), then the fill of the first p.cap matches
-int launch_select_compact(const SelectParams& p, void* stream);
-
-// ---- device-resident instance sets (cl_iset.hip; include/clsnap.h cl_iset) ----------------------
-// A subset of [0, n_instances) as a bitmap: bit inst & 63 of word inst >> 6, stride / 64 words, the
-// bits at and above n_instances 0.  The analytics kernels filter on it (SampleParams::where).
-enum : int32_t { ISET_AND = 0, ISET_OR = 1, ISET_ANDNOT = 2, ISET_NUM_OPS = 3 };
-constexpr int32_t kIsetThreads = 256;
-// bits[list[r] >> 6] |= 1 << (list[r] & 63), r < n, into a zeroed bitmap (entries outside
-// [0, n_inst) are skipped: the host has refused them before)
-int launch_iset_scatter(const long long* list, int64_t n, int64_t n_inst, unsigned long long* bits, void* stream);
-// dst[w] = a[w] op b[w], w < words (dst may be a or b)
-int launch_iset_combine(unsigned long long* dst, const unsigned long long* a, const unsigned long long* b,
-                        int32_t op, int64_t words, void* stream);
-// The words that overlap [lo, hi), lo < hi, the first and the last masked to the range:
-// dst[j] = src[lo / 64 + j] & mask, j < ceil(hi / 64) - lo / 64 -- what the selection's compaction
-// (launch_select_compact, base = lo rounded down to 64) reads; the count adds their set bits to
-// *count (zeroed by the host), one atomic per workgroup.
-int launch_iset_clip(unsigned long long* dst, const unsigned long long* src, int64_t lo, int64_t hi, void* stream);
-int launch_iset_count(const unsigned long long* src, int64_t lo, int64_t hi, unsigned long long* count, void* stream);
-
-// ---- joint distribution of two snapshot quantities (cl_crosstab.hip; include/clsnap.h cl_snapshot_crosstab) ----
-// A two-axis contingency table with the five joint moments over the instances of [lo, hi) with
-// status OK in which the snapshots of both axes completed.  An axis is one of the quantities a
-// select clause names (SEL_TICK .. SEL_CH_TOK) of one snapshot id, binned:
-//   bin(v) = v < lo ? 0 : min((uint64)(v - lo) / width, bins - 1).
-struct CrosstabAxis {  // the layout of cl_crosstab_axis
-  int32_t sid, field, index, bins;
-  int64_t lo, width;
-};
-constexpr int32_t kXtMaxBins = 4096;   // per axis
-constexpr int32_t kXtMaxCells = 4096;  // bins_a * bins_b: 16 KB of 32-bit workgroup counters
-constexpr int32_t kXtThreads = 256;
-// Words of the flat int64 result (CL_XT_*): wrapping sums, then minima, maxima and the cells.
-enum : int32_t {
-  XT_INSTANCES = 0, XT_OK = 1, XT_SAMPLE = 2, XT_SUM_A = 3, XT_SUM_B = 4, XT_SUM_AA = 5, XT_SUM_AB = 6, XT_SUM_BB = 7,
-  XT_MIN_A = 8, XT_MIN_B = 9, XT_MAX_A = 10, XT_MAX_B = 11, XT_CELLS = 12,
-};
-struct CrosstabParams {
-  SampleParams s;            // the walk, and the planes of axis a's snapshot (s.sid == a.sid)
-  CrosstabAxis a, b;
-  const int32_t* ch_slot;    // [C] record word of channel c
-  const int32_t* hist_off;   // [C + 1]
-  const long long* hist_pre; // as StatsParams::hist_pre
-  int32_t staged;            // N * rw <= kCensusStageWords: the planes an axis reads are staged in LDS
-  long long* out;            // [XT_CELLS + a.bins * b.bins], initialised by the host (0 / INT64_MAX / INT64_MIN)
-};
-inline int32_t crosstab_lds_bytes(int32_t cells, bool staged) {
-  return 16 * 8 + cells * 4 + (staged ? kWavesPerBlock * kStatsStageWords * 4 : 0);
-}
-int launch_crosstab(const CrosstabParams& p, int32_t blocks, void* stream);
 
 }  // namespace clsnap

@@ -1,77 +1,37 @@
 // cl_groups.hip -- group-by over a tuple of snapshot quantities of the batch engine
 // (cl_snapshot_groups).
 //
-// GROUP BY (q1, ..., qk), k <= kGroupsMaxTerms, over the quantities a select clause names, possibly
+// GROUP BY (q1, ..., qk), k <= kGroupsMaxTerms, over quantities of snapshots (cl_quantity.h), possibly
 // of different snapshot ids: exact, without bin edges, one row per tuple that occurs.  The sample is
 // the instances of [lo, hi) with status OK in which the snapshot of every term completed -- of the
 // members of an instance set when one is given.  Groups are keyed by the 64-bit group_key() of the
-// tuple (cl_groups.h); per group the census's row: count, smallest instance, min and max completion
+// tuple (cl_analytics.h); per group the census's row: count, smallest instance, min and max completion
 // tick of terms[0]'s snapshot.  All integer and commutative, so the result does not depend on the
 // grid, the workgroup tables, the record layout or the exec kernel.
 //
 // Key pass (cl_groups_keys).  The sample walk of cl_sample.h, lane = slot.  sample_lane() classifies
 // the slot for terms[0]'s snapshot; a sample lane then reads the completion tick of every other
-// distinct snapshot id from its snap_tick row and leaves the sample if one is negative (the
-// crosstab's scheme, for up to 8 ids).  The key is folded as a running hash in term order: no lane
-// keeps an array of values.  A term that reads records needs its snapshot's plane: records of at
-// most kCensusStageWords words are staged in the wave's LDS tile (stage_tile, whole-record chunk)
+// distinct snapshot id (view_tick) and leaves the sample if one is negative (the crosstab's scheme,
+// for up to 8 ids); every term is read through the view of its snapshot (sample_view).  The key is
+// folded as a running hash in term order: no lane keeps an array of values.  A term that reads
+// records needs its snapshot's plane: records of at most kCensusStageWords words are staged in the
+// wave's LDS tile (stage_tile, whole-record chunk)
 // unless the tile already holds that snapshot -- adjacent terms of one snapshot id stage once,
 // alternating ids restage -- and longer records are read word by word (RecordRow).  A term list of
 // completion ticks reads no records.  Aggregation is the census's (cl_census_table.h).
 //
 // Values (cl_groups_values).  After the host's sort, one lane per returned group evaluates the terms
-// for the group's smallest instance with the same term_value(): the records are addressed directly
-// (rec_word; block-major through the instance -> slot map of the replay).
+// for the group's smallest instance with the same quantity_value(): the records are addressed directly
+// (PlaneRow; block-major through the instance -> slot map of the replay).
 //
 // group_of reuses cl_census_rank / cl_census_lookup (launch_census_class_of).
 #include <hip/hip_runtime.h>
 
 #include "cl_census_table.h"
-#include "cl_engine.h"
-#include "cl_groups.h"
-#include "cl_sample.h"
+#include "cl_quantity.h"
 
 namespace clsnap {
 namespace {
-
-// Word idx of the N * rw record words of (snapshot sid, instance inst), read from the plane in
-// either layout.
-struct PlaneRow {
-  const uint32_t* nod;
-  const int32_t* rec_slot;
-  int64_t stride, inst;
-  int32_t n_nodes, rw, sid;
-  __device__ __forceinline__ uint32_t operator()(int32_t idx) const {
-    return nod[rec_word(stride, n_nodes, rw, sid, inst, rec_slot, idx)];
-  }
-};
-
-// The value of term z for one instance: its completion tick `tick` of z.sid, or what the term
-// names of the record `word` reads (the record of snapshot z.sid).
-template <class Word>
-__device__ __forceinline__ long long term_value(const GroupsParams& p, const GroupTerm& z, const Word& word,
-                                                int32_t tick) {
-  const SampleParams& s = p.c.s;
-  switch (z.field) {
-    case SEL_NODE: return (int32_t)word(z.index * s.rw);
-    case SEL_CH_MSGS: return (long long)rec_msgs(word(p.c.ch_slot[z.index]));
-    case SEL_CH_TOK: return rec_tokens(word(p.c.ch_slot[z.index]), token_prefix(p.hist_pre, p.c.hist_off, z.index));
-    case SEL_MSGS: {
-      long long msgs = 0;
-      for (int32_t c = 0; c < s.n_ch; ++c) msgs += (long long)rec_msgs(word(p.c.ch_slot[c]));
-      return msgs;
-    }
-    case SEL_INFLIGHT: {
-      long long infl = 0;
-      for (int32_t c = 0; c < s.n_ch; ++c)
-        infl += rec_tokens(word(p.c.ch_slot[c]), token_prefix(p.hist_pre, p.c.hist_off, c));
-      return infl;
-    }
-    case SEL_KEY:
-      return (long long)snapshot_key(z.sid, s.n_nodes, s.rw, s.n_ch, p.c.ch_slot, p.c.hist_off, p.c.hist_val, word);
-    default: return tick;
-  }
-}
 
 __global__ __launch_bounds__(kCensusThreads) void cl_groups_keys(GroupsParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char groups_lds[];
@@ -87,7 +47,7 @@ __global__ __launch_bounds__(kCensusThreads) void cl_groups_keys(GroupsParams p)
     // ---- the sample: every other snapshot id completed, too
     if (l.sample)
       for (int32_t q = 0; q < p.n_other; ++q)
-        if (p.c.s.snap_tick[inst * p.c.s.s_cap + p.other_sid[q]] < 0) l.sample = false;
+        if (view_tick(p.c.s, l, p.other_sid[q]) < 0) l.sample = false;
     counts.add(l);
     if (l.in && p.c.keys && !l.sample) p.c.class_of[inst - p.c.s.lo] = -1;
     if (__ballot(l.sample) == 0) continue;  // (wave-uniform)
@@ -98,16 +58,15 @@ __global__ __launch_bounds__(kCensusThreads) void cl_groups_keys(GroupsParams p)
 #pragma unroll 1
     for (int32_t k = 0; k < p.n_terms; ++k) {
       const GroupTerm z = p.term[k];
-      SampleParams sv = p.c.s;  // the view of term k's snapshot: the same walk, another plane
-      sv.sid = z.sid;
+      const SampleParams sv = sample_view(p.c.s, z.sid);  // term k's snapshot: the same walk, another plane
       if (staged && z.field != SEL_TICK && staged_sid != z.sid) {
         stage_tile(sv, t, whole_record_chunk(sv), L.tile, lane);
         staged_sid = z.sid;
       }
-      if (l.sample) {
-        const int32_t tick = z.sid == p.c.s.sid ? l.tick : p.c.s.snap_tick[inst * p.c.s.s_cap + z.sid];
-        key = group_key_fold(key, term_value(p, z, RecordRow(sv, t, lane, L.tile, staged), tick));
-      }
+      if (l.sample)
+        key = group_key_fold(key, quantity_value<SEL_KEY>(sv, p.c.tab, z.sid, z.field, z.index,
+                                                          RecordRow(sv, t, lane, L.tile, staged),
+                                                          view_tick(p.c.s, l, z.sid)));
     }
     if (!l.sample) continue;
     if (p.c.keys) {
@@ -133,7 +92,7 @@ __global__ __launch_bounds__(kCensusThreads) void cl_groups_values(GroupsParams 
     long long v = 0;
     if (known) {
       const PlaneRow row{s.snap_nod, rec_slot, s.stride, inst, s.n_nodes, s.rw, z.sid};
-      v = term_value(p, z, row, s.snap_tick[inst * s.s_cap + z.sid]);
+      v = quantity_value<SEL_KEY>(s, p.c.tab, z.sid, z.field, z.index, row, s.snap_tick[inst * s.s_cap + z.sid]);
     }
     values[g * p.n_terms + k] = v;
   }
@@ -145,9 +104,7 @@ bool terms_ok(const GroupsParams& p) {
   if (s.sid != p.term[0].sid) return false;
   for (int32_t k = 0; k < p.n_terms; ++k) {
     const GroupTerm& z = p.term[k];
-    const int32_t bound = z.field == SEL_NODE ? s.n_nodes : z.field == SEL_CH_MSGS || z.field == SEL_CH_TOK ? s.n_ch : 1;
-    if (z.field < 0 || z.field >= SEL_NUM_FIELDS || z.index < 0 || z.index >= bound || z.sid < 0 || z.sid >= s.s_cap)
-      return false;
+    if (!quantity_ok(z.field, z.index, SEL_KEY, s.n_nodes, s.n_ch) || z.sid < 0 || z.sid >= s.s_cap) return false;
   }
   for (int32_t q = 0; q < p.n_other; ++q)
     if (p.other_sid[q] < 0 || p.other_sid[q] >= s.s_cap) return false;
@@ -159,8 +116,8 @@ bool terms_ok(const GroupsParams& p) {
 int launch_groups_keys(const GroupsParams& p, int32_t blocks, void* stream) {
   const bool staged = p.c.staged != 0 && p.reads_records != 0;
   const size_t lds = (size_t)census_lds_bytes(p.c.lds_slots, staged);
-  if (lds > (size_t)kMaxLdsBytes || blocks < 1 || !terms_ok(p)) return (int)hipErrorInvalidValue;
-  if (p.c.staged && p.c.s.n_nodes * p.c.s.rw > kCensusStageWords) return (int)hipErrorInvalidValue;
+  if (lds > (size_t)kMaxLdsBytes || blocks < 1 || !terms_ok(p) || !staged_ok(p.c.s, p.c.staged))
+    return (int)hipErrorInvalidValue;
   if (lds > 64 * 1024) {
     const hipError_t e =
         hipFuncSetAttribute((const void*)cl_groups_keys, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes);

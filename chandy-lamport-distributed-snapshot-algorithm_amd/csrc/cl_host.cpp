@@ -1356,7 +1356,7 @@ struct cl_sim {
     s->blocked = rec_blocked ? 1 : 0;
     // (the slot order of the replay that wrote the records; the dbg A/B's is the identity)
     s->inst_map = rec_blocked && rec_slot_gen != -2 ? d_map.p : nullptr;
-    *t = SimTables{d_ch_slot.p, d_word_ch.p, d_hist.p, d_hist.p + hist.size() + 1, d_hist_pre.p,
+    *t = SimTables{{d_ch_slot.p, d_hist.p, d_hist.p + hist.size() + 1, d_hist_pre.p}, d_word_ch.p,
                    rec_blocked ? d_rec_slot.p : nullptr};
     return CL_OK;
   }

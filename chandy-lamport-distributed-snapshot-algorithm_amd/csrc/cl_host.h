@@ -2,8 +2,8 @@
 // defines the sim and the functions of the first part, cl_analytics.cpp the second.  The analytics
 // read a sim through these only; they see no field of it.
 #pragma once
+#include "cl_analytics.h"
 #include "cl_dev.h"
-#include "cl_engine.h"
 
 struct cl_sim;
 
@@ -49,9 +49,8 @@ struct SimDevice {
 int sim_device(cl_sim* sim, SimDevice* out);
 
 // The tables next to the records, resident after sim_records.
-struct SimTables {
-  const int32_t *ch_slot, *word_ch, *hist_off, *hist_val;
-  const long long* hist_pre;
+struct SimTables : RecordTables {
+  const int32_t* word_ch;  // [N * rw] record word -> channel, -2 token word, -1 padding
   // instance -> record slot of block-major records (rec_word; the map the packed collect over a
   // list uses), nullptr when the records are instance-major
   const int32_t* rec_slot;

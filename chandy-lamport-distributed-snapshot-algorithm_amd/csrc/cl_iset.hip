@@ -15,7 +15,7 @@
 // All plain loads, stores and integer atomics; grids are sized to the words, capped, grid-stride.
 #include <hip/hip_runtime.h>
 
-#include "cl_engine.h"
+#include "cl_analytics.h"
 
 namespace clsnap {
 namespace {

@@ -1,6 +1,6 @@
 // cl_sample.h -- the sample walk shared by the analytics kernels of the batch engine
-// (cl_stats.hip, cl_census.hip, cl_select.hip, cl_crosstab.hip, cl_groups.hip).  Device code: not part of cl_engine.h, which is
-// also compiled into the run-time lanes kernel.
+// (cl_stats.hip, cl_census.hip, cl_select.hip, cl_crosstab.hip, cl_groups.hip).  Device code; the
+// declarations it works on are cl_analytics.h's.
 //
 // The sample (SampleParams).  Every instance of [lo, hi) with status OK in which snapshot `sid`
 // completed (completion tick >= 0) -- of the members of an instance set when one is given
@@ -12,7 +12,7 @@
 // instance map and a sub-range filters on it; instance-major, slot = instance.  SampleCounts keeps
 // the instances / OK / sample counters of the call's info.
 //
-// Staging (stage_tile).  A tile of records is staged in LDS chunk by chunk (cl_engine.h
+// Staging (stage_tile).  A tile of records is staged in LDS chunk by chunk (cl_analytics.h
 // stats_chunk; records of at most kCensusStageWords words are one chunk, whole_record_chunk):
 //   block-major records [S][I/64][N][64][rw]: the tile is one 64-slot block, a chunk of whole
 //     nodes is nv * 64 * rw contiguous words;
@@ -22,11 +22,12 @@
 // Both are read lane-linear in address order, dwordx4 when rw % 4 == 0 (every chunk then starts
 // and ends on 16 bytes).  Rows are padded to an odd pitch K | 1, so a lane reading its own row and
 // a lane reading one word of every row both go without bank conflicts.  RecordRow reads a word of
-// the lane's record from the staged tile, or from the plane when the records are not staged.
+// the lane's record from the staged tile, or from the plane when the records are not staged;
+// PlaneRow reads a word of any instance's record from the plane.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "cl_engine.h"
+#include "cl_analytics.h"
 
 namespace clsnap {
 
@@ -195,19 +196,35 @@ struct RecordRow {
     return src[((size_t)v * 64 + lane) * rw + (idx - v * rw)];
   }
 };
+// Word idx of the N * rw record words of (snapshot sid, instance inst), read from the plane in
+// either layout (rec_word; rec_slot: instance -> record slot of block-major records, else nullptr).
+struct PlaneRow {
+  const uint32_t* nod;
+  const int32_t* rec_slot;
+  int64_t stride, inst;
+  int32_t n_nodes, rw, sid;
+  __device__ __forceinline__ uint32_t operator()(int32_t idx) const {
+    return nod[rec_word(stride, n_nodes, rw, sid, inst, rec_slot, idx)];
+  }
+};
 
 // A channel's cursor word: begin and end index into its token history, 16 bits each.
 __device__ __forceinline__ uint32_t rec_msgs(uint32_t rec) { return (rec >> 16) - (rec & 0xffffu); }
 // The int64 prefix sums of channel c's token history (the host stores channel c at hist_off[c] + c:
 // one more entry per channel than the history has).
-__device__ __forceinline__ const long long* token_prefix(const long long* hist_pre, const int32_t* hist_off,
-                                                         int32_t c) {
-  return hist_pre + hist_off[c] + c;
+__device__ __forceinline__ const long long* token_prefix(const RecordTables& tab, int32_t c) {
+  return tab.hist_pre + tab.hist_off[c] + c;
 }
 // The recorded tokens of the cursor word: two loads of the channel's prefix (none for no messages).
 __device__ __forceinline__ long long rec_tokens(uint32_t rec, const long long* pre) {
   const uint32_t b = rec & 0xffffu, e = rec >> 16;
   return e != b ? pre[e] - pre[b] : 0;
+}
+// The content hash of the record `word` reads, as snapshot sid's: the census key (snapshot_key).
+template <class Word>
+__device__ __forceinline__ unsigned long long record_key(const SampleParams& s, const RecordTables& tab, int32_t sid,
+                                                         const Word& word) {
+  return snapshot_key(sid, s.n_nodes, s.rw, s.n_ch, tab.ch_slot, tab.hist_off, tab.hist_val, word);
 }
 
 }  // namespace clsnap

@@ -1,9 +1,9 @@
 // cl_select.hip -- instance selection by snapshot predicate of the batch engine (cl_select_instances).
 //
 // Which instances of a batch have a snapshot with given properties: a conjunction of at most
-// kSelMaxClauses range clauses over the quantities cl_snapshot_stats reduces (completion tick, a
-// node's tokenMap entry, a channel's recorded messages and tokens, the instance's totals) and the
-// census key, evaluated over the sample of those calls (cl_sample.h) -- the instances of [lo, hi)
+// kSelMaxClauses range clauses over quantities of one snapshot (cl_quantity.h: completion tick, a
+// node's tokenMap entry, a channel's recorded messages and tokens, the instance's totals, the
+// census key), evaluated over the sample of cl_snapshot_stats (cl_sample.h) -- the instances of [lo, hi)
 // with status OK in which snapshot `sid` completed.  The answer is the ascending list of matching instance
 // indices.  All integer and order-preserving, so it does not depend on the grid, the record layout
 // or the exec kernel.
@@ -11,8 +11,8 @@
 // Evaluate (cl_select_eval).  The sample walk of cl_sample.h, lane = slot.  When a clause reads the
 // records, those of at most kCensusStageWords words per instance are staged in LDS as one chunk
 // (stage_tile); longer ones are read word by word by their lane (RecordRow).  A sample lane computes only what the
-// clauses name: the totals in one pass over the channels' cursor words, a channel's recorded tokens
-// from the int64 prefix of its token history, the key with the census's hash (snapshot_key).  The
+// clauses name, each clause with quantity_value(): the totals once, in one pass over the channels'
+// cursor words, and the key once, however many clauses name them (QuantityOnce).  The
 // verdict goes into a bitmap indexed by instance - base, base = lo rounded down to a multiple of 64:
 //   instance-major records: a tile is 64 consecutive instances, i.e. one bitmap word -- the wave's
 //     ballot, one store (every word of the bitmap is written, none needs zeroing);
@@ -28,8 +28,7 @@
 // Entries from `cap` on are dropped.
 #include <hip/hip_runtime.h>
 
-#include "cl_engine.h"
-#include "cl_sample.h"
+#include "cl_quantity.h"
 
 namespace clsnap {
 namespace {
@@ -51,35 +50,18 @@ __global__ __launch_bounds__(kSelThreads) void cl_select_eval(SelectParams p) {
       if (p.need_records && p.staged) stage_tile(p.s, t, whole_record_chunk(p.s), tile, lane);
       if (l.sample) {
         const RecordRow rb(p.s, t, lane, tile, p.staged);
-        // a channel's recorded messages and tokens from its cursor word
-        auto ch_msgs = [&](int32_t c) -> long long { return (long long)rec_msgs(rb(p.ch_slot[c])); };
-        auto ch_tok = [&](int32_t c) -> long long {
-          return rec_tokens(rb(p.ch_slot[c]), token_prefix(p.hist_pre, p.hist_off, c));
-        };
-        long long msgs = 0, infl = 0;
-        if (p.need_totals)
-          for (int32_t c = 0; c < p.s.n_ch; ++c) msgs += ch_msgs(c), infl += ch_tok(c);
-        unsigned long long key = 0;
-        if (p.need_key)
-          key = snapshot_key(p.s.sid, p.s.n_nodes, p.s.rw, p.s.n_ch, p.ch_slot, p.hist_off, p.hist_val, rb);
+        // what several clauses may name, once: both totals in one pass over the cursor words, the key
+        QuantityOnce once{};
+        if (p.need_totals) once.totals = channel_totals(p.s, p.tab, rb);
+        if (p.need_key) once.key = record_key(p.s, p.tab, p.s.sid, rb);
         hit = true;
         for (int32_t q = 0; q < p.n_clauses; ++q) {
           const SelectClause& z = p.clause[q];
-          bool inside;
-          if (z.field == SEL_KEY) {
-            inside = key >= (unsigned long long)z.lo && key <= (unsigned long long)z.hi;
-          } else {
-            long long v = l.tick;
-            switch (z.field) {
-              case SEL_MSGS: v = msgs; break;
-              case SEL_INFLIGHT: v = infl; break;
-              case SEL_NODE: v = (int32_t)rb(z.index * p.s.rw); break;
-              case SEL_CH_MSGS: v = ch_msgs(z.index); break;
-              case SEL_CH_TOK: v = ch_tok(z.index); break;
-              default: break;
-            }
-            inside = v >= z.lo && v <= z.hi;
-          }
+          const long long v = quantity_value<SEL_KEY>(p.s, p.tab, p.s.sid, z.field, z.index, rb, l.tick, &once);
+          // (a key is compared as the unsigned value it is)
+          const bool inside = z.field == SEL_KEY ? (unsigned long long)v >= (unsigned long long)z.lo &&
+                                                       (unsigned long long)v <= (unsigned long long)z.hi
+                                                 : v >= z.lo && v <= z.hi;
           hit = hit && inside != ((z.flags & kSelNot) != 0);
         }
       }
@@ -183,7 +165,7 @@ __global__ __launch_bounds__(kSelThreads) void cl_select_fill(SelectParams p) {
 int launch_select_eval(const SelectParams& p, int32_t blocks, void* stream) {
   const size_t lds = (size_t)select_lds_bytes(p.staged != 0 && p.need_records != 0);
   if (blocks < 1 || p.n_clauses < 0 || p.n_clauses > kSelMaxClauses) return (int)hipErrorInvalidValue;
-  if (p.staged && p.s.n_nodes * p.s.rw > kCensusStageWords) return (int)hipErrorInvalidValue;
+  if (!staged_ok(p.s, p.staged)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(cl_select_eval, dim3((unsigned)blocks), dim3(kSelThreads), lds, (hipStream_t)stream, p);
   return (int)hipGetLastError();
 }

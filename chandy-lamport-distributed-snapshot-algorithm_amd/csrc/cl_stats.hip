@@ -9,7 +9,7 @@
 // does not depend on the grid, the record layout or the exec kernel that wrote the records.
 //
 // Read pattern.  The sample walk of cl_sample.h: per tile of 64 record slots and chunk of record
-// words (cl_engine.h stats_chunk) the wave stages 64 x K words in LDS (stage_tile), rows at an odd
+// words (cl_analytics.h stats_chunk) the wave stages 64 x K words in LDS (stage_tile), rows at an odd
 // pitch, so both views below read the tile without bank conflicts.
 //
 // Reduction.  Two views of the staged tile:
@@ -25,12 +25,11 @@
 // At the end each workgroup issues one global integer atomic per accumulator that is not at its
 // identity.  No per-lane global atomics, no floating point.
 //
-// LDS: kStatsLdsBytes per workgroup (cl_engine.h).  When the N * rw record words of the topology
+// LDS: kStatsLdsBytes per workgroup (cl_analytics.h).  When the N * rw record words of the topology
 // need more accumulator rows than fit, the host runs several passes, each accumulating a range
 // of chunks; the first also takes the per-instance totals (it reads every chunk).
 #include <hip/hip_runtime.h>
 
-#include "cl_engine.h"
 #include "cl_sample.h"
 
 namespace clsnap {
@@ -140,7 +139,7 @@ __global__ __launch_bounds__(kStatsThreads) void cl_stats_kernel(StatsParams p) 
           if (c < 0) continue;
           const uint32_t rec = tile[lane * pitch + k], cnt = rec_msgs(rec);
           tot_msgs += cnt;
-          if (cnt) tot_tok += (unsigned long long)rec_tokens(rec, token_prefix(p.hist_pre, p.hist_off, c));
+          if (cnt) tot_tok += (unsigned long long)rec_tokens(rec, token_prefix(p.tab, c));
         }
       }
 
@@ -160,7 +159,7 @@ __global__ __launch_bounds__(kStatsThreads) void cl_stats_kernel(StatsParams p) 
             }
             fold(acc, AW, row, 0, a);
           } else {
-            const long long* pre = token_prefix(p.hist_pre, p.hist_off, c);
+            const long long* pre = token_prefix(p.tab, c);
             uint32_t* h = mh + (size_t)row * M;
             for (unsigned long long m = mask; m; m &= m - 1) {
               const int32_t i = __builtin_ctzll(m);
