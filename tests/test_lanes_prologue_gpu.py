@@ -31,7 +31,9 @@ EVENTS = read_text("8nodes-concurrent-snapshots.events")   # 97 draws: rows of 1
 MORE = "send N1 N2 1\nsnapshot N3\ntick 3\n"
 # + 19 draws: 135, rows of 144 bytes (a group and one chunk of the next)
 MORE2 = "send N3 N4 1\nsnapshot N5\ntick 3\n"
-N_MAP = 4096 + 37   # the smallest batch that replays through the slot map, with a ragged last wave
+# past 4096 the clean instances replay in length order, with a ragged last wave (a split alone maps
+# far smaller batches, in index order: test_blocked_ragged_gpu)
+N_MAP = 4096 + 37
 
 
 def new_sim(n, top=TOP, seed_base=O.REFERENCE_SEED, schedule=None, **kw):
