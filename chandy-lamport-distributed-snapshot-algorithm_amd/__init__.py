@@ -126,6 +126,9 @@ def lib():
         "cl_exec_engine": [vp, vp],
         "cl_jit_stats": [vp, vp],
         "cl_lanes_compile_check": [vp, vp, vp, i64],
+        "cl_set_program_kernels": [vp, i32],
+        "cl_exec_program_kernels": [vp, vp],
+        "cl_lanes_program_compile_check": [vp, vp, vp, vp, i64],
         "cl_stats_layout_of": [vp, vp, vp],
         "cl_snapshot_stats": [vp, i32, i64, i64, vp, vp, i64],
         "cl_stats_time": [vp, vp],
@@ -1458,6 +1461,26 @@ class ChandyLamportSim:
         buf = C.create_string_buffer(16384)
         _check(self._L.cl_lanes_compile_check(self._h, C.byref(ms), buf, len(buf)))
         return ms.value, buf.value.decode(errors="replace")
+
+    # kernels specialized on the program for replays on the instance-per-lane kernels
+    # (include/clsnap.h CL_PROGRAM_*): results are identical either way
+    PROGRAM_AUTO, PROGRAM_OFF, PROGRAM_ON = 0, 1, 2
+
+    def set_program_kernels(self, mode):
+        _check(self._L.cl_set_program_kernels(self._h, int(mode)))
+
+    def exec_program_kernels(self):
+        """True when the most recent launch ran program-specialized kernels."""
+        return bool(self._i32(self._L.cl_exec_program_kernels))
+
+    def lanes_program_compile_check(self):
+        """Compile the kernels specialized on the current program without a device: (compile ms,
+        specialized, compiler log); specialized is False (and nothing is compiled) for a program
+        over the cap, which replays on the generic kernels."""
+        ms, spec = C.c_double(), C.c_int32(0)
+        buf = C.create_string_buffer(16384)
+        _check(self._L.cl_lanes_program_compile_check(self._h, C.byref(ms), C.byref(spec), buf, len(buf)))
+        return ms.value, bool(spec.value), buf.value.decode(errors="replace")
 
     def kernel_time(self):
         """(total exec-kernel ms, launches) since the previous call (HIP events)."""

@@ -350,6 +350,11 @@ struct ExecLaunch {
   void* ev_stop2;
   int32_t* stop2_used;
   void* ev_start2;
+  // a replay of a planned program on the instance-per-lane kernels: the host's copy of the device
+  // program [0, p.op_end), for kernels specialized on it (cl_lanes.h program type P), or nullptr:
+  // the generic kernels; *prog_used is set to 1 when the specialized kernels were launched
+  const Op* prog;
+  int32_t* prog_used;
 };
 int launch_exec(const ExecParams& p, const uint32_t* topo, const Op* ops, const uint8_t* sched, const ExecLaunch& L);
 // The instance-per-lane kernel (cl_lanes.h, compiled per topology by cl_jit.cpp): lanes_fit
@@ -357,6 +362,14 @@ int launch_exec(const ExecParams& p, const uint32_t* topo, const Op* ops, const 
 // plan as launch_exec; hipErrorInvalidImage when the kernel could not be compiled, lanes_error
 // says why); lanes_jit_stats: run-time compilations so far and their total time.
 bool lanes_fit(const ExecParams& p);
+// Replays of a planned program may run kernels specialized on the program too, up to this many
+// host ops (sends and snapshot starts) and tick ops: each host op is straight-line code of the
+// kernel, run once per wave (a send ~30 instructions, a snapshot start ~70: C3's 13 are 7 KB
+// beside the tick's 20 KB; the 10-node ring's 110 fit), and compile time grows with them.
+// lanes_prog_fit: the device program [0, n_prog) is under the cap.
+constexpr int32_t kProgMaxHostOps = 128;
+constexpr int32_t kProgMaxSegments = 32;
+bool lanes_prog_fit(const ExecParams& p, const Op* prog, int n_prog);
 int64_t debug_knob(const char* name, int64_t def);  // (A/B knobs of dbg builds; def in the product)
 int launch_lanes(const ExecParams& p, const uint32_t* topo, const Op* ops, const uint8_t* sched, const ExecLaunch& L);
 // ExecParams::sched_pk from the byte rows and the slot map (cl_rowpack.hip): words of the
@@ -373,7 +386,8 @@ void lanes_jit_stats(double* compile_ms, int64_t* compiles);
 #if !defined(__HIPCC_RTC__)
 #include <string>
 namespace clsnap {
-int lanes_compile_only(const ExecParams& p, double* ms, std::string* log);
+// (prog: the program-specialized kernels of the device program [0, n_prog) instead)
+int lanes_compile_only(const ExecParams& p, double* ms, std::string* log, const Op* prog = nullptr, int n_prog = 0);
 }  // namespace clsnap
 #endif
 namespace clsnap {

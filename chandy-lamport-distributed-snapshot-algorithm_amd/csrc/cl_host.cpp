@@ -70,6 +70,10 @@ constexpr int64_t kMapMinInstances = 4096;
 // unordered launch (C3 90 %: kept; C2 95 %: measured slower mapped, §9)
 constexpr int64_t kMapPct = 92;
 
+// CL_PROGRAM_AUTO: replays of a planned program on the lanes kernels run kernels specialized on
+// the program where AUTO's own lanes condition holds (DESIGN §9 round 9 has the A/B this rests on)
+constexpr bool kProgramKernelsByDefault = true;
+
 namespace {
 
 // ---------------------------------------------------------------------------
@@ -303,6 +307,10 @@ struct cl_sim {
   int32_t engine = CL_ENGINE_AUTO;
   bool lanes_unavailable = false;  // the lanes kernel failed to compile for this sim (AUTO falls back)
   int32_t last_engine = 0;
+  // kernels specialized on the program for replays of a planned program on the lanes kernels
+  // (cl_set_program_kernels), and whether the latest launch ran them
+  int32_t prog_mode = CL_PROGRAM_AUTO;
+  int32_t last_prog = 0;
 
   // limits
   int32_t cap_log2 = 3;
@@ -1028,8 +1036,18 @@ struct cl_sim {
     // last fork: consecutive replays touch disjoint instances on the two streams.  C3 per replay,
     // forking every replay / only then: 2^17 0.2391-0.2394 / 0.2370-0.2371 ms, 2^20
     // 1.6146-1.6151 / 1.6104-1.6113 ms, gpurun_out/r05z)
+    // A replay of a planned program on the lanes kernels may run kernels specialized on the
+    // program (cl_lanes.h program type P).  Their compile takes seconds, so by default only where
+    // AUTO's own lanes condition holds -- batches whose replays are worth it, not every small
+    // program a caller replays once; cl_set_program_kernels overrides.  The first launch of a
+    // program (the probe), flushes and resumed launches stay generic.
+    const bool prog = lanes && planned && !save_state && prog_mode != CL_PROGRAM_OFF &&
+                      (prog_mode == CL_PROGRAM_ON ||
+                       (kProgramKernelsByDefault && (int64_t)n_inst >= kLanesAutoMinInstances &&
+                        std::max(max_out, max_in) >= 2));
+    int32_t prog_used = 0;
     const ExecLaunch el{stream, pr.start, pr.stop, stream2, ev_fork, ev_join, (!pipe || s_dirty) ? 1 : 0,
-                        pipe ? 0 : 1, pr.stop2, &pr.stop2_used, pr.start2};
+                        pipe ? 0 : 1, pr.stop2, &pr.stop2_used, pr.start2, prog ? dops.data() : nullptr, &prog_used};
     // a replay through the slot map with no state image (so the next launch starts from the
     // initial state again) writes its records block-major by slot: a wave's stores of one
     // node's records are contiguous (both kernels; C3 2^20 1.636 -> 1.567 ms per replay on the
@@ -1068,6 +1086,7 @@ struct cl_sim {
       e = launch_exec(p, d_topo.p, d_ops.p, d_sched.p, el);
     }
     last_engine = used_lanes ? CL_ENGINE_LANES : CL_ENGINE_NODES;
+    last_prog = used_lanes ? prog_used : 0;
     if (begin == 0) rec_blocked = blocked;
     if (pipe) {
       s2_live = true;
@@ -1799,8 +1818,24 @@ int cl_exec_engine(cl_sim* sim, int32_t* engine) {
   return CL_OK;
 }
 
-int cl_lanes_compile_check(cl_sim* sim, double* compile_ms, char* log, int64_t log_cap) {
+int cl_set_program_kernels(cl_sim* sim, int32_t mode) {
   SIM_CALL(sim);
+  if (mode != CL_PROGRAM_AUTO && mode != CL_PROGRAM_OFF && mode != CL_PROGRAM_ON)
+    return set_err(CL_E_INVALID, "unknown program kernel mode %d", mode);
+  sim->prog_mode = mode;  // (the plan stays: the same replays, on other kernels)
+  return CL_OK;
+}
+
+int cl_exec_program_kernels(cl_sim* sim, int32_t* on) {
+  SIM_CALL(sim);
+  if (!on) return set_err(CL_E_INVALID, "null output");
+  *on = sim->last_prog;
+  return CL_OK;
+}
+
+// The device-less compile of the lanes kernels: the generic ones, or (specialized != nullptr)
+// the ones specialized on the sim's current program, where it is under the cap.
+static int lanes_check(cl_sim* sim, double* compile_ms, int32_t* specialized, char* log, int64_t log_cap) {
   int rc = sim->freeze();
   if (rc) return rc;
   if (sim->ids.empty()) return set_err(CL_E_STATE, "the topology has no nodes");
@@ -1813,13 +1848,33 @@ int cl_lanes_compile_check(cl_sim* sim, double* compile_ms, char* log, int64_t l
   p.lt = sim->lanes_topo();
   if (!lanes_fit(p)) return set_err(CL_E_LIMIT, "the topology does not fit the instance-per-lane kernel");
   std::string l;
-  rc = lanes_compile_only(p, compile_ms, &l);
+  if (specialized) {
+    // the device program of a replay: from op 0 (the next launch builds its own again)
+    sim->build_device_program(0);
+    sim->dops_for = (size_t)-1;
+    *specialized = lanes_prog_fit(p, sim->dops.data(), (int)sim->dops.size()) ? 1 : 0;
+    if (compile_ms) *compile_ms = 0;
+    rc = *specialized ? lanes_compile_only(p, compile_ms, &l, sim->dops.data(), (int)sim->dops.size()) : 0;
+  } else {
+    rc = lanes_compile_only(p, compile_ms, &l);
+  }
   if (log && log_cap > 0) {
     const size_t n = std::min<size_t>(l.size(), (size_t)log_cap - 1);
     std::memcpy(log, l.data(), n);
     log[n] = 0;
   }
   return rc ? set_err(CL_E_DEVICE, "instance-per-lane kernel compilation failed") : CL_OK;
+}
+
+int cl_lanes_compile_check(cl_sim* sim, double* compile_ms, char* log, int64_t log_cap) {
+  SIM_CALL(sim);
+  return lanes_check(sim, compile_ms, nullptr, log, log_cap);
+}
+
+int cl_lanes_program_compile_check(cl_sim* sim, double* compile_ms, int32_t* specialized, char* log, int64_t log_cap) {
+  SIM_CALL(sim);
+  if (!specialized) return set_err(CL_E_INVALID, "null output");
+  return lanes_check(sim, compile_ms, specialized, log, log_cap);
 }
 
 int cl_jit_stats(double* compile_ms, int64_t* compiles) {

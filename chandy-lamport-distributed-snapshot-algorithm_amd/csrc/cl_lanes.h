@@ -797,8 +797,140 @@ __device__ __forceinline__ void start_snapshot(const Ctx& x, State<T>& s, const 
   resolve(s);
 }
 
-// The whole event program for one wave of 64 instances (slots slot_base + wave * 64 + lane).
+// ---- the event program compiled in ------------------------------------------------------------
+// A replay re-runs the program its plan was built from, so cl_jit.cpp can also generate a program
+// type P beside T: the op list as constants.  The tick ops cut the program into segments; P gives
+// per segment the host ops (sends and snapshot starts, OP_SENDS groups as their sends in order)
+// that precede its tick op, and the tick op's fields (all constexpr):
+//   SPEC              true (NoProg: false, the generic kernels that read `ops`)
+//   NSEG, NARM        tick segments; arms of host ops: NSEG, + 1 for host ops after the last tick
+//   h0(g)             first host op of arm g (h0(NARM): their number)
+//   hk(h), ha(h), hb(h), hc(h)   host op h: OP_SEND or OP_SNAP and its fields a, b, c
+//   td(g), ta(g), tb(g)          segment g's tick op: 1 for OP_DRAIN, and its fields a, b
+//   ns(g)             snapshots started before segment g's tick op
+// send_c / snap_c are send_one / start_snapshot with the node, link, token count and snapshot id
+// as constants: they touch the node's own registers, with no select ladder over node slots and no
+// op fetched, and compute the same values in the same order (the failure paths included).
+struct NoProg {
+  static constexpr bool SPEC = false;
+};
+
+template <class T, bool SPILL, int A, int B, int C>
+__device__ __forceinline__ void send_c(const Ctx& x, State<T>& s) {
+  const bool insufficient = s.alive && s.tok[A] < C;
+  const bool go = s.alive && !insufficient && B >= 0;
+  int32_t nf = 0;
+  if constexpr (B >= 0) {  // (an unknown destination pushes nothing: go is false)
+    push<T, SPILL>(x, s.hw[A][B], T::off(A) + (uint32_t)B, go, (uint32_t)C << 8, s.draw, delays8<T>(x, s.draw) & 15u,
+                   s.time, nf);
+    s.tok[A] -= go ? C : 0;
+  }
+  s.flag = nf;
+  if (s.alive) {
+    if (insufficient) {
+      s.status = ST_FATAL_INSUFFICIENT;
+      s.alive = false;
+    } else if (B < 0) {
+      s.status = ST_FATAL_UNKNOWN_DEST;
+      s.alive = false;
+    } else {
+      s.draw += 1;
+    }
+  }
+  resolve(s);
+}
+
+template <class T, bool SPILL, int A, int SID, int C>
+__device__ __forceinline__ void snap_c(const Ctx& x, State<T>& s) {
+  constexpr int id = T::id(A), od = T::od(A);
+  const bool on = s.alive;
+  constexpr uint32_t nib = (id == 0 ? 15u : (uint32_t)id + 1u) << ((SID & 7) * 4);
+  s.pd[A][SID >> 3] |= on ? nib : 0u;
+  // CreateLocalSnapshot (node.go:58-84) with every in-channel recording
+  if (on) create_record<T>(x, kpar()->snap_nod, s, A, -1, plane_off(x, (uint32_t)SID) + x.lrec);
+  // SendToNeighbors (node.go:97-109): one guard, then the push that cannot fail, else push()
+  int32_t nf = 0;
+  if constexpr (od > 0) {
+    const uint32_t dl = delays8<T>(x, s.draw);
+    constexpr uint32_t mpl = 0x8000u | ((uint32_t)SID << 8);
+    uint32_t any = 0;
+#pragma unroll
+    for (int k = 0; k < od; ++k) any |= s.hw[A][k];
+    const bool hard = on && (s.draw + od > x.draws || (any & Guard<T>::FULL) != 0);
+    if (__builtin_expect(__ballot(hard) != 0, 0)) {
+#pragma unroll
+      for (int k = 0; k < od; ++k)
+        push<T, SPILL>(x, s.hw[A][k], T::off(A) + (uint32_t)k, on, mpl, s.draw + k, (dl >> (4 * k)) & 15u, s.time, nf);
+    } else {
+      uint32_t sl[od], en[od];
+#pragma unroll
+      for (int k = 0; k < od; ++k) {
+        sl[k] = sure_slot<T>(x, s.hw[A][k]);
+        en[k] = sure_entry(mpl, (dl >> (4 * k)) & 15u, s.time);
+      }
+      if (on) {  // (stores only: no register is written under the lane mask)
+#pragma unroll
+        for (int k = 0; k < od; ++k) lds16_at(sl[k])[(T::off(A) + k) << (T::CAPL + 6)] = (uint16_t)en[k];
+      }
+      const uint32_t on01 = on ? 1u : 0u;
+#pragma unroll
+      for (int k = 0; k < od; ++k) s.hw[A][k] += on01;
+    }
+  }
+  s.flag = nf;
+  if (s.alive) s.draw += C;
+  resolve(s);
+}
+
+// The tick loop of one tick op.  TICK: `a` ticks.  DRAIN: tick until every started snapshot
+// completed (at most `a` ticks, else HANG), then `b` more (test_common.go:123-137).  Per lane: a
+// lane ticks while iter < until (cl_kernels.hip exec_wave).
 template <class T, bool SPILL>
+__device__ __forceinline__ void tick_loop(const Ctx& x, State<T>& s, bool drain, int32_t a, int32_t b,
+                                          int32_t n_started) {
+  constexpr int N = T::N, D = T::D;
+  constexpr int32_t kNoUntil = 0x7fffffff;
+  int32_t until = drain ? kNoUntil : a;
+  bool anyw = drain;
+  for (int32_t iter = 0;; ++iter) {
+    if (anyw) {
+      const bool w = until == kNoUntil;
+      if (w && (!s.alive || (int32_t)s.ndone >= n_started)) {
+        until = iter + b;
+      } else if (w && iter >= a) {
+        s.status = ST_HANG;
+        s.alive = false;
+        until = iter;
+      }
+      anyw = __ballot(until == kNoUntil) != 0;
+    }
+    const bool act = s.alive && iter < until;
+    if (!__ballot(act)) break;
+    const bool idle = tick<T, SPILL>(x, s, act);
+    if (idle && !anyw) {
+      // no lane picked anything: if nothing is queued anywhere in the wave either, every
+      // remaining tick of this op is empty for every lane (no peek, draw or delivery; the
+      // drain tail after the last delivery, all of C3's idle wave-ticks) -- add them at once
+      uint32_t q = 0;
+#pragma unroll
+      for (int v = 0; v < N; ++v)
+#pragma unroll
+        for (int k = 0; k < D; ++k)
+          if (k < T::od(v)) q |= s.hw[v][k] & 0x7fu;
+      if (!__ballot(q != 0)) {
+        if (s.alive) s.time += max(0, until - (iter + 1));
+        break;
+      }
+    }
+  }
+}
+
+// The whole event program for one wave of 64 instances (slots slot_base + wave * 64 + lane).
+// P = NoProg: the program is read from `ops`.  A program type P (replays of a planned program):
+// the program is P's, `ops` is not read; the kernel starts from the initial state and saves no
+// state image (the host launches it only so), so the resume prologue and the state-image epilogue
+// are compiled out.
+template <class T, bool SPILL, class P = NoProg>
 __device__ __forceinline__ void program(const ExecParams& p, const Op* __restrict__ ops,
                                         const uint8_t* __restrict__ sched) {
   constexpr int N = T::N, D = T::D, RW = rec_w(T::D);
@@ -885,7 +1017,7 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
   }
   s.time = s.draw = s.status = 0;
   s.peek = s.push = s.ndone = 0;
-  if (p.fresh) {
+  if (P::SPEC || p.fresh) {
     // (completion ticks are stored later by this same lane: program order keeps them after)
     if (valid)
       for (int32_t sid = 0; sid < lay.s_cap; ++sid) p.snap_tick[inst * (uint32_t)lay.s_cap + sid] = -1;
@@ -940,11 +1072,44 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
   int32_t n_started = p.n_started_before;
   tl.mark(TL_PRO);
 
+  if constexpr (P::SPEC) {
+    // A run-time loop over the segments: each segment's host ops are straight-line code on
+    // constant slots behind a uniform branch on the segment index, and the tick loop's body
+    // exists once (the waves of a CU sit in different segments and share its instruction cache).
+#pragma nounroll
+    for (int32_t seg = 0; seg < P::NARM; ++seg) {
+      bool drain = false;
+      int32_t ta = 0, tb = 0;
+      sfor<0, P::NARM>([&](auto gc) {
+        constexpr int g = decltype(gc)::value;
+        if (seg == g) {
+          sfor<P::h0(g), P::h0(g + 1)>([&](auto hc) {
+            constexpr int h = decltype(hc)::value;
+            if constexpr (P::hk(h) == OP_SEND) send_c<T, SPILL, P::ha(h), P::hb(h), P::hc(h)>(x, s);
+            else snap_c<T, SPILL, P::ha(h), P::hb(h), P::hc(h)>(x, s);
+          });
+          if constexpr (g < P::NSEG) {
+            drain = P::td(g) != 0;
+            ta = P::ta(g);
+            tb = P::tb(g);
+            n_started = P::ns(g);
+          }
+        }
+      });
+      if (P::NARM > P::NSEG && seg == P::NSEG) break;  // (host ops after the last tick op)
+      tl.mark(TL_OPS);
+      tick_loop<T, SPILL>(x, s, drain, ta, tb, n_started);
+      tl.mark(TL_LOOP);
+      tl.drain();
+      tl.mark(TL_WAIT);
+      tl.count(TL_LOOPS);
+    }
+  }
   // the program through the constant address space: scalar loads, so every op field is a
   // uniform SGPR value (a vector load would make the node dispatch divergent)
   typedef const __attribute__((address_space(4))) Op COp;
   COp* cops = (COp*)ops;
-  for (int32_t i = p.op_begin; i < p.op_end; ++i) {
+  for (int32_t i = p.op_begin; !P::SPEC && i < p.op_end; ++i) {
     const Op op = cops[i];
     // The tick ops first, leaving through `continue`: as the last arm of the chain below, the
     // tick loop's exit joined the other arms' paths into the next op, and the compiler kept the
@@ -952,45 +1117,8 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
     // before every tick loop and loaded again (unused on this path) after it, behind the loop's
     // record stores.  This way the spill-free kernel has no scratch (C3: 168 -> 154 VGPRs).
     if (op.kind == OP_TICK || op.kind == OP_DRAIN) {
-      // TICK: op.a ticks.  DRAIN: tick until every started snapshot completed (at most op.a
-      // ticks, else HANG), then op.b more (test_common.go:123-137).  Per lane: a lane ticks
-      // while iter < until (cl_kernels.hip exec_wave).
-      const bool drain = op.kind == OP_DRAIN;
-      constexpr int32_t kNoUntil = 0x7fffffff;
-      int32_t until = drain ? kNoUntil : op.a;
-      bool anyw = drain;
       tl.mark(TL_OPS);
-      for (int32_t iter = 0;; ++iter) {
-        if (anyw) {
-          const bool w = until == kNoUntil;
-          if (w && (!s.alive || (int32_t)s.ndone >= n_started)) {
-            until = iter + op.b;
-          } else if (w && iter >= op.a) {
-            s.status = ST_HANG;
-            s.alive = false;
-            until = iter;
-          }
-          anyw = __ballot(until == kNoUntil) != 0;
-        }
-        const bool act = s.alive && iter < until;
-        if (!__ballot(act)) break;
-        const bool idle = tick<T, SPILL>(x, s, act);
-        if (idle && !anyw) {
-          // no lane picked anything: if nothing is queued anywhere in the wave either, every
-          // remaining tick of this op is empty for every lane (no peek, draw or delivery; the
-          // drain tail after the last delivery, all of C3's idle wave-ticks) -- add them at once
-          uint32_t q = 0;
-#pragma unroll
-          for (int v = 0; v < N; ++v)
-#pragma unroll
-            for (int k = 0; k < D; ++k)
-              if (k < T::od(v)) q |= s.hw[v][k] & 0x7fu;
-          if (!__ballot(q != 0)) {
-            if (s.alive) s.time += max(0, until - (iter + 1));
-            break;
-          }
-        }
-      }
+      tick_loop<T, SPILL>(x, s, op.kind == OP_DRAIN, op.a, op.b, n_started);
       tl.mark(TL_LOOP);
       tl.drain();
       tl.mark(TL_WAIT);
@@ -1065,7 +1193,7 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
   tl.drain();
   tl.mark(TL_EPI);
   tl.flush(SPILL ? 1 : 0);
-  if (!p.save_state) return;
+  if (P::SPEC || !p.save_state) return;
   // the node-parallel state image (peek and push counts as node 0's, the others 0)
   uint32_t* S = p.state + inst;
 #pragma unroll

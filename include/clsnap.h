@@ -213,12 +213,32 @@ int cl_records_blocked(cl_sim* sim, int32_t* on);
 #define CL_ENGINE_LANES 2
 int cl_set_exec_engine(cl_sim* sim, int32_t engine);
 int cl_exec_engine(cl_sim* sim, int32_t* engine);
+/* Replays (cl_rerun) of a planned program on the instance-per-lane kernels can run kernels
+ * compiled for the topology and the program: the sends and snapshot starts as straight-line code
+ * on their nodes' registers (engine-internal; results are identical).  Such a compile takes
+ * seconds, once per program and process:
+ *   CL_PROGRAM_AUTO  only for batches AUTO itself would put on the instance-per-lane kernels
+ *                    (cl_engine.h kLanesAutoMinInstances, a topology degree of at least 2)
+ *   CL_PROGRAM_OFF   never
+ *   CL_PROGRAM_ON    for every replay of a planned program on those kernels
+ * Programs over 128 sends and snapshot starts or 32 tick ops, first launches, flushes and resumed
+ * launches always run the generic kernels; so does a program whose compile fails.
+ * cl_exec_program_kernels: 1 when the most recent launch ran program-specialized kernels. */
+#define CL_PROGRAM_AUTO 0
+#define CL_PROGRAM_OFF 1
+#define CL_PROGRAM_ON 2
+int cl_set_program_kernels(cl_sim* sim, int32_t mode);
+int cl_exec_program_kernels(cl_sim* sim, int32_t* on);
 /* Run-time kernel compilations of this process so far and their total wall time. */
 int cl_jit_stats(double* compile_ms, int64_t* compiles);
 /* Compile the instance-per-lane kernels for this sim's topology and layout without loading
  * them (no device needed): CL_OK, or CL_E_LIMIT (the topology does not fit them) / CL_E_DEVICE
  * (compilation failed); the compiler log goes to log (log_cap bytes, may be NULL). */
 int cl_lanes_compile_check(cl_sim* sim, double* compile_ms, char* log, int64_t log_cap);
+/* The same for the kernels specialized on the sim's current program (every event issued so far,
+ * as a replay would run it): *specialized = 1 and they are compiled, or 0 and nothing is -- the
+ * program is over the cap and replays on the generic kernels. */
+int cl_lanes_program_compile_check(cl_sim* sim, double* compile_ms, int32_t* specialized, char* log, int64_t log_cap);
 
 /* Test/benchmark aid (no reference counterpart): overwrite every result plane the exec
  * kernel writes -- node snapshot records, completion ticks, per-instance result rows,
