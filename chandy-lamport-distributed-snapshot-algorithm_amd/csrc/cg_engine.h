@@ -1,5 +1,5 @@
 // cg_engine.h -- data layout shared by the graph engine's host runtime (cg_host.cpp)
-// and its gfx950 kernels (cg_kernels.hip, cg_table.hip, cg_sparse.hip).  DESIGN.md §10 draws the same layout.
+// and its gfx950 kernels (cg_kernels.hip, cg_table.hip, cg_sparse.hip, cg_wave.hip).  DESIGN.md §10 draws the same layout.
 //
 // The graph engine runs ONE reference simulation over a large topology (BASELINE
 // configs 4 and 5: 2^20-node regular digraph, 100k-node power-law graph with 4,096
@@ -289,5 +289,22 @@ int cg_launch_sparse_write(const GParams& p, int32_t sid_lo, int32_t n_sids, con
                            const ulonglong2* rtot, const long long* row_off, const long long* row_moff,
                            int32_t* ent_channel, int32_t* ent_count, int32_t* msg, void* stream);
 int cg_launch_sparse_tokens(const GParams& p, int32_t sid_lo, int32_t n_sids, int32_t* out, void* stream);
+// Marker-wave profile and marker tree (cg_wave.hip).  A row is rw = CL_WV_HEAD + lat_bins +
+// depth_bins int64 words (clgraph.h).  wave_init leaves rows[n_rows] of the snapshots sid_lo + r at
+// their identities with the origin set: org[r] is the origin itself (user != 0) or the rank of
+// the initiator, whose record's creation tick is then the origin (-1: not an owned node).  wave
+// reduces the owned nodes' records into the rows; with pairs != nullptr also the resolved
+// {ancestor, hops} pairs [n_rows][n] (lo32 ancestor, hi32 hops) into the depth fields.  wave_link
+// writes the guarded first link of every pair, wave_jump runs one pointer-doubling round in place
+// and stores 1 to *changed if a pair moved.  wave_pack turns the records of the owned ranks into
+// the int32 planes parent / tick [n_rows][part_hi - part_lo] (tick may be null).
+int cg_launch_wave_init(const GParams& p, const long long* org, int32_t user, int32_t sid_lo, int32_t n_rows, int32_t rw,
+                        long long* rows, void* stream);
+int cg_launch_wave(const GParams& p, int32_t sid_lo, int32_t n_rows, int32_t rw, int32_t lat_bins, int32_t lat_width,
+                   int32_t depth_bins, int32_t user, const unsigned long long* pairs, long long* rows, int32_t n_cus,
+                   void* stream);
+int cg_launch_wave_link(const GParams& p, int32_t sid_lo, int32_t n_rows, unsigned long long* pairs, void* stream);
+int cg_launch_wave_jump(const GParams& p, int32_t n_rows, unsigned long long* pairs, int32_t* changed, void* stream);
+int cg_launch_wave_pack(const GParams& p, int32_t sid_lo, int32_t n_rows, int32_t* parent, int32_t* tick, void* stream);
 
 }  // namespace clsnap

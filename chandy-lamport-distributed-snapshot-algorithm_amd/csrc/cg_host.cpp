@@ -159,6 +159,16 @@ struct cl_graph {
   DevBuf<long long> d_sp_head;
   DevBuf<int32_t> d_sp_chan, d_sp_cnt, d_sp_msg, d_sp_tok;
   Timer<4> sp;
+  // marker-wave profile and tree (cl_graph_snapshot_wave / _tree): the device rows, the origins
+  // (or initiator ranks) of the rows, the doubling round's flag, and the scratch of one chunk of
+  // sids -- the {ancestor, hops} pairs of the wave, the packed planes of the tree; the events
+  // around the latest wave call's kernels and its doubling rounds
+  DevBuf<long long> d_wv_rows, d_wv_org;
+  DevBuf<int32_t> d_wv_flag;
+  DevBuf<unsigned long long> d_wv_scratch;
+  Timer<2> wv;
+  int32_t wv_rounds = 0;
+  size_t wv_budget = 0;  // bytes of scratch per chunk of sids (0: kWaveScratchBytes; cl_graph_set_wave_scratch)
   size_t ops_uploaded = 0;
   // device event trace (cl_graph_trace_enable)
   int32_t trace_cap = 0;
@@ -1244,6 +1254,7 @@ int cl_graph_device_bytes(cl_graph* g, int64_t* bytes) {
        g->d_big.bytes() + g->d_cpart.bytes() +
        g->d_cre.bytes() + g->d_bsum.bytes() + g->d_hq.bytes() +
        g->d_histv.bytes() + g->d_fifo.bytes() + g->d_sn.bytes() + g->d_rec.bytes() + g->d_done.bytes() + g->d_ctick.bytes() + g->d_sched.bytes();
+  b += g->d_wv_scratch.bytes() + g->d_wv_rows.bytes() + g->d_wv_org.bytes();  // (the wave's pairs and rows)
   *bytes = (int64_t)b;
   return CL_OK;
 }
@@ -1484,6 +1495,133 @@ int cl_graph_table_time(cl_graph* g, double* ms) {
   if (!ms) return set_err(CL_E_INVALID, "null output");
   if (!g->tb.done) return set_err(CL_E_STATE, "no snapshot table has been computed");
   return g->tb.ms(0, 1, ms);
+}
+
+// ---- marker-wave profile and marker tree (cg_wave.hip) ------------------------------------
+// Scratch of one chunk of sids: the wave's 8-byte pairs over all nodes, the tree's int32 planes
+// over the owned ones.  256 MiB holds 32 sids of a 2^20-node graph and every sid of a 20,000-node
+// x 256-snapshot run at once, and is small next to the planes of either run; a graph whose single
+// sid needs more takes one sid per chunk.
+constexpr size_t kWaveScratchBytes = (size_t)256 << 20;
+constexpr int32_t kWaveMaxRounds = 32;
+
+int cl_graph_set_wave_scratch(cl_graph* g, int64_t bytes) {
+  G_CHECK(g);
+  if (bytes < 0) return set_err(CL_E_INVALID, "negative scratch budget");
+  g->wv_budget = (size_t)bytes;
+  return CL_OK;
+}
+
+int cl_graph_snapshot_wave(cl_graph* g, int32_t sid_lo, int32_t sid_hi, const cl_graph_wave_spec* spec,
+                           const int64_t* origins, int64_t* out, int64_t out_words) {
+  G_CHECK(g);
+  static_assert(sizeof(cl_graph_wave_spec) == 4 * sizeof(int32_t), "cl_graph_wave_spec is 4 x int32");
+  if (!spec || !out) return set_err(CL_E_INVALID, "null %s", !spec ? "spec" : "output");
+  if (spec->lat_bins < 1 || spec->lat_bins > CL_GRAPH_WAVE_MAX_BINS || spec->lat_width < 1 || spec->depth_bins < 0 ||
+      spec->depth_bins > CL_GRAPH_WAVE_MAX_BINS || spec->reserved)
+    return set_err(CL_E_INVALID, "wave spec: lat_bins %d (1..%d), lat_width %d (>= 1), depth_bins %d (0..%d), reserved %d",
+                spec->lat_bins, CL_GRAPH_WAVE_MAX_BINS, spec->lat_width, spec->depth_bins, CL_GRAPH_WAVE_MAX_BINS,
+                spec->reserved);
+  if (sid_lo < 0 || sid_lo > sid_hi || sid_hi > g->n_sids)
+    return set_err(CL_E_INVALID, "snapshot range [%d, %d) outside [0, %d]", sid_lo, sid_hi, g->n_sids);
+  const int32_t ns = sid_hi - sid_lo, rw = CL_WV_HEAD + spec->lat_bins + spec->depth_bins;
+  if (out_words < (int64_t)ns * rw)
+    return set_err(CL_E_LIMIT, "%d rows of %d words exceed out_words %lld", ns, rw, (long long)out_words);
+  if (g->part && spec->depth_bins > 0)
+    return set_err(CL_E_STATE, "a partitioned run has no device depth: the parents' records live on other devices");
+  if (g->part && !origins)
+    return set_err(CL_E_STATE, "a partitioned run needs the origins: only the initiator's owner knows the start");
+  if (ns == 0) return CL_OK;
+  int rc = g->flush();
+  if (rc) return rc;
+  const GParams& P = g->P;
+  const bool depth = spec->depth_bins > 0;
+  const size_t nsz = (size_t)ns, n = (size_t)P.n;
+  // sids per chunk of pairs
+  const size_t budget = g->wv_budget ? g->wv_budget : kWaveScratchBytes;
+  size_t cs = std::max<size_t>(1, budget / std::max<size_t>(1, n * sizeof(unsigned long long)));
+  cs = std::min(cs, nsz);
+  if ((rc = g->d_wv_rows.ensure(nsz * (size_t)rw)) || (rc = g->d_wv_org.ensure(nsz)) || (rc = g->d_wv_flag.ensure(1)))
+    return rc;
+  if (depth && (rc = g->d_wv_scratch.ensure(cs * n))) return rc;
+  // the origins, or the initiators' ranks (the program's snapshot events)
+  std::vector<long long> org(nsz, -1);
+  if (origins) std::copy(origins, origins + ns, org.begin());
+  else
+    for (const GOp& op : g->gops)
+      if (op.kind == GOP_SNAP && op.b >= sid_lo && op.b < sid_hi) org[(size_t)(op.b - sid_lo)] = op.a;
+  HIP_TRY(hipMemcpyAsync(g->d_wv_org.p, org.data(), nsz * sizeof(long long), hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));  // (`org` is a local)
+  const int32_t user = origins ? 1 : 0;
+  g->wv.done = 0;
+  g->wv_rounds = 0;
+  if ((rc = g->wv.mark(0, g->stream))) return rc;
+  if ((rc = g->k_err(cg_launch_wave_init(P, g->d_wv_org.p, user, sid_lo, ns, rw, g->d_wv_rows.p, g->stream)))) return rc;
+  if (!depth) {
+    if ((rc = g->k_err(cg_launch_wave(P, sid_lo, ns, rw, spec->lat_bins, spec->lat_width, 0, user, nullptr,
+                                      g->d_wv_rows.p, g->n_cus, g->stream))))
+      return rc;
+  } else {
+    for (size_t c0 = 0; c0 < nsz; c0 += cs) {
+      const int32_t cn = (int32_t)std::min(cs, nsz - c0), sid0 = sid_lo + (int32_t)c0;
+      if ((rc = g->k_err(cg_launch_wave_link(P, sid0, cn, g->d_wv_scratch.p, g->stream)))) return rc;
+      int32_t rounds = 0, moved = 1;
+      while (moved && rounds < kWaveMaxRounds) {  // until a round moves no pair
+        HIP_TRY(hipMemsetAsync(g->d_wv_flag.p, 0, sizeof(int32_t), g->stream));
+        if ((rc = g->k_err(cg_launch_wave_jump(P, cn, g->d_wv_scratch.p, g->d_wv_flag.p, g->stream)))) return rc;
+        HIP_TRY(hipMemcpyAsync(&moved, g->d_wv_flag.p, sizeof moved, hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        ++rounds;
+      }
+      g->wv_rounds = std::max(g->wv_rounds, rounds);
+      if ((rc = g->k_err(cg_launch_wave(P, sid0, cn, rw, spec->lat_bins, spec->lat_width, spec->depth_bins, user,
+                                        g->d_wv_scratch.p, g->d_wv_rows.p + c0 * (size_t)rw, g->n_cus, g->stream))))
+        return rc;
+    }
+  }
+  if ((rc = g->wv.mark(1, g->stream))) return rc;
+  HIP_TRY(hipMemcpyAsync(out, g->d_wv_rows.p, nsz * (size_t)rw * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  g->wv.done = 1;
+  return CL_OK;
+}
+
+int cl_graph_wave_time(cl_graph* g, double* ms, int32_t* rounds) {
+  G_CHECK(g);
+  if (!ms) return set_err(CL_E_INVALID, "null output");
+  if (!g->wv.done) return set_err(CL_E_STATE, "no snapshot wave has been computed");
+  if (rounds) *rounds = g->wv_rounds;
+  return g->wv.ms(0, 1, ms);
+}
+
+int cl_graph_snapshot_tree(cl_graph* g, int32_t sid_lo, int32_t sid_hi, int32_t* parent, int32_t* tick) {
+  G_CHECK(g);
+  if (!parent) return set_err(CL_E_INVALID, "null output");
+  if (sid_lo < 0 || sid_lo > sid_hi || sid_hi > g->n_sids)
+    return set_err(CL_E_INVALID, "snapshot range [%d, %d) outside [0, %d]", sid_lo, sid_hi, g->n_sids);
+  const int32_t ns = sid_hi - sid_lo;
+  if (ns == 0) return CL_OK;
+  int rc = g->flush();
+  if (rc) return rc;
+  const GParams& P = g->P;
+  const size_t nsz = (size_t)ns, width = (size_t)(P.part_hi - P.part_lo), planes = tick ? 2 : 1;
+  if (width == 0) return CL_OK;
+  // sids per chunk of packed planes
+  const size_t budget = g->wv_budget ? g->wv_budget : kWaveScratchBytes;
+  size_t cs = std::max<size_t>(1, budget / (width * planes * sizeof(int32_t)));
+  cs = std::min(cs, nsz);
+  if ((rc = g->d_wv_scratch.ensure((cs * width * planes + 1) / 2))) return rc;
+  int32_t* d_parent = reinterpret_cast<int32_t*>(g->d_wv_scratch.p);
+  int32_t* d_tick = tick ? d_parent + cs * width : nullptr;
+  for (size_t c0 = 0; c0 < nsz; c0 += cs) {  // (stream order: a chunk's copies end before the next pack)
+    const size_t cn = std::min(cs, nsz - c0);
+    if ((rc = g->k_err(cg_launch_wave_pack(P, sid_lo + (int32_t)c0, (int32_t)cn, d_parent, d_tick, g->stream)))) return rc;
+    HIP_TRY(hipMemcpyAsync(parent + c0 * width, d_parent, cn * width * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (tick)
+      HIP_TRY(hipMemcpyAsync(tick + c0 * width, d_tick, cn * width * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  return CL_OK;
 }
 
 int cl_graph_collect_sparse(cl_graph* g, int32_t sid_lo, int32_t sid_hi, int32_t* complete, int64_t* row_offsets,

@@ -81,6 +81,10 @@ def glib():
             "cl_graph_get_checksums": [vp, vp],
             "cl_graph_snapshot_table": [vp, i32, i32, vp],
             "cl_graph_table_time": [vp, vp],
+            "cl_graph_snapshot_wave": [vp, i32, i32, vp, vp, vp, i64],
+            "cl_graph_wave_time": [vp, vp, vp],
+            "cl_graph_set_wave_scratch": [vp, i64],
+            "cl_graph_snapshot_tree": [vp, i32, i32, vp, vp],
             "cl_graph_collect_sparse": [vp, i32, i32, vp, vp, vp, vp, i64, vp, i64, vp, vp],
             "cl_graph_sparse_time": [vp, vp],
             "cl_graph_part_begin": [vp, i32, i32],
@@ -181,6 +185,185 @@ class SnapshotTable:
         for f in self._CHANNEL:
             out[f] = np.where(done, out[f], np.int64(0))
         return SnapshotTable(out)
+
+
+# Head words of a cl_graph_snapshot_wave row (include/clgraph.h CL_WV_*): word i is WAVE_HEAD[i];
+# lat_hist[lat_bins] and depth_hist[depth_bins] follow.
+WAVE_HEAD = ("sid", "origin", "created", "lat_sum", "lat_sumsq", "lat_min", "lat_max", "depth_sum", "depth_sumsq",
+             "depth_max", "broken", "reserved")
+WAVE_MAX_BINS = 1024      # CL_GRAPH_WAVE_MAX_BINS
+WAVE_SPEC_DTYPE = np.dtype([(f, np.int32) for f in ("lat_bins", "lat_width", "depth_bins", "reserved")])
+_WV = {f: i for i, f in enumerate(WAVE_HEAD)}
+
+
+class SnapshotWave:
+    """Marker-wave profile rows of GraphSim.snapshot_wave, reduced on the device: per snapshot
+    id the moments and the histogram of the nodes' creation latency (creation tick - origin; bin
+    = latency < 0 ? 0 : min(latency // lat_width, lat_bins - 1)) and, with depth_bins > 0, of
+    their depth in the marker tree (bin = min(depth, depth_bins - 1)).
+
+      rows    int64[ns, len(WAVE_HEAD) + lat_bins + depth_bins]; the head words by name through
+              word(name), the common ones as properties
+      spec    (lat_bins, lat_width, depth_bins)"""
+
+    def __init__(self, rows, lat_bins, lat_width=1, depth_bins=0):
+        self.lat_bins, self.lat_width, self.depth_bins = int(lat_bins), int(lat_width), int(depth_bins)
+        self.rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, self.row_words)
+
+    @property
+    def spec(self):
+        return self.lat_bins, self.lat_width, self.depth_bins
+
+    @property
+    def row_words(self):
+        return len(WAVE_HEAD) + self.lat_bins + self.depth_bins
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    def __eq__(self, other):
+        return isinstance(other, SnapshotWave) and self.spec == other.spec and np.array_equal(self.rows, other.rows)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"SnapshotWave({len(self)} snapshots, lat_bins={self.lat_bins}, lat_width={self.lat_width}, " \
+               f"depth_bins={self.depth_bins})"
+
+    def word(self, name):
+        """Head word `name` (WAVE_HEAD) of every row."""
+        return self.rows[:, _WV[name]]
+
+    sid = property(lambda self: self.word("sid"))
+    origin = property(lambda self: self.word("origin"))
+    created = property(lambda self: self.word("created"))
+    broken = property(lambda self: self.word("broken"))
+
+    @property
+    def lat_hist(self):
+        return self.rows[:, len(WAVE_HEAD):len(WAVE_HEAD) + self.lat_bins]
+
+    @property
+    def depth_hist(self):
+        return self.rows[:, len(WAVE_HEAD) + self.lat_bins:]
+
+    @staticmethod
+    def _ratio(a, b):
+        out = np.full(a.shape, np.nan)
+        np.divide(a, b, out=out, where=b > 0)
+        return out
+
+    @property
+    def mean_latency(self):
+        """lat_sum / created per row; nan where nothing was created."""
+        return self._ratio(self.word("lat_sum").astype(np.float64), self.created)
+
+    @property
+    def mean_depth(self):
+        """depth_sum over the nodes that have a depth; nan with the depth off or none."""
+        return self._ratio(self.word("depth_sum").astype(np.float64), self.depth_hist.sum(axis=1))
+
+    def coverage(self):
+        """float[ns, lat_bins]: the share of the created nodes whose latency lies in bins 0..b --
+        how far the wave had got by the end of bin b; 0 where nothing was created."""
+        c = np.cumsum(self.lat_hist, axis=1).astype(np.float64)
+        out = np.zeros_like(c)
+        np.divide(c, self.created[:, None], out=out, where=self.created[:, None] > 0)
+        return out
+
+    def merge(self, other):
+        """The profile of two parts of one partitioned run (the same sids, spec and origins, else
+        ValueError): counts, sums and histograms add (the squares modulo 2^64), extremes combine."""
+        if not isinstance(other, SnapshotWave) or self.spec != other.spec:
+            raise ValueError("merge needs profiles of the same spec")
+        a, b = self.rows, other.rows
+        if a.shape != b.shape or not np.array_equal(self.sid, other.sid):
+            raise ValueError("merge needs profiles of the same snapshot ids in the same order")
+        if not np.array_equal(self.origin, other.origin):
+            raise ValueError("merge needs profiles measured from the same origins")
+        with np.errstate(over="ignore"):
+            out = (a.astype(np.uint64) + b.astype(np.uint64)).astype(np.int64)     # sums and histograms
+        for f in ("sid", "origin", "reserved"):
+            out[:, _WV[f]] = a[:, _WV[f]]
+        for f in ("lat_max", "depth_max"):
+            out[:, _WV[f]] = np.maximum(a[:, _WV[f]], b[:, _WV[f]])
+        out[:, _WV["lat_min"]] = np.minimum(a[:, _WV["lat_min"]], b[:, _WV["lat_min"]])
+        return SnapshotWave(out, *self.spec)
+
+
+class MarkerTree:
+    """The marker tree of one snapshot over the node ranks [node_lo, node_lo + len(parent))
+    (GraphSim.snapshot_tree): parent[v - node_lo] is the rank of the node whose marker created v's
+    local snapshot, -1 at the initiator, -2 where there is no local snapshot; tick the creation
+    epoch (-1 likewise), or None."""
+
+    def __init__(self, parent, tick=None, node_lo=0, sid=-1):
+        self.parent = np.ascontiguousarray(parent, dtype=np.int32).reshape(-1)
+        self.tick = None if tick is None else np.ascontiguousarray(tick, dtype=np.int32).reshape(-1)
+        if self.tick is not None and self.tick.size != self.parent.size:
+            raise ValueError("parent and tick cover different nodes")
+        self.node_lo, self.sid = int(node_lo), int(sid)
+
+    def __len__(self):
+        return self.parent.size
+
+    def __eq__(self, other):
+        if not isinstance(other, MarkerTree):
+            return NotImplemented
+        return self.node_lo == other.node_lo and np.array_equal(self.parent, other.parent) and \
+            (self.tick is None) == (other.tick is None) and (self.tick is None or np.array_equal(self.tick, other.tick))
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"MarkerTree(sid {self.sid}, nodes [{self.node_lo}, {self.node_lo + len(self)}), " \
+               f"{int((self.parent != -2).sum())} created)"
+
+    @property
+    def created(self):
+        return self.parent != -2
+
+    def _whole(self):
+        n = self.parent.size
+        if self.node_lo != 0:
+            raise ValueError("the tree of a part: gather the parts first (PartitionedGraphSim.snapshot_tree)")
+        if ((self.parent < -2) | (self.parent >= n)).any():
+            raise ValueError("a parent outside the tree's nodes")
+        return n
+
+    def depth(self):
+        """int64 per node: tree edges up to the initiator (the initiator: 0), the definition of
+        the device's depth fields, by pointer doubling in numpy; -1 where there is no local
+        snapshot, or where the chain does not end at the initiator (it reaches a node without a
+        local snapshot).  ValueError on a cycle."""
+        self._whole()
+        anc = self.parent.astype(np.int64)
+        hops = (anc >= 0).astype(np.int64)
+        for _ in range(64):
+            live = np.nonzero(anc >= 0)[0]
+            if live.size == 0:
+                return np.where(anc == -1, hops, np.int64(-1))
+            a = anc[live]
+            up, more = anc[a], hops[a]
+            anc[live], hops[live] = up, hops[live] + more
+        raise ValueError("the parents hold a cycle")
+
+    def path(self, v):
+        """The ranks from v up to the initiator, both included.  ValueError if v holds no local
+        snapshot or its chain does not end at the initiator."""
+        n = self._whole()
+        out, u = [], int(v)
+        if not 0 <= u < n:
+            raise IndexError(f"node {v} outside [0, {n})")
+        while len(out) <= n:
+            p = int(self.parent[u])
+            if p == -2:
+                raise ValueError(f"node {u} holds no local snapshot")
+            out.append(u)
+            if p == -1:
+                return out
+            u = p
+        raise ValueError("the parents hold a cycle")
 
 
 # cl_graph_sparse_info (include/clgraph.h): 8 x int64.
@@ -642,6 +825,57 @@ class GraphSim:
         """Device ms of the latest snapshot_table call's kernels (HIP events)."""
         return self._get(self._L.cl_graph_table_time, C.c_double)
 
+    def snapshot_wave(self, sid_lo=0, sid_hi=None, lat_bins=64, lat_width=1, depth_bins=32, origins=None):
+        """SnapshotWave of the snapshots [sid_lo, sid_hi) (default: all), reduced on the device
+        from the node records (cl_graph_snapshot_wave): how the marker wave of each spread over
+        time and, with depth_bins > 0, how deep the tree is that it took.  origins (one tick per
+        snapshot) replaces the start tick the latencies are measured from; a part of a
+        partitioned run needs it, and takes depth_bins=0."""
+        if sid_hi is None:
+            sid_hi = self.num_snapshots
+        ns = max(sid_hi - sid_lo, 0)
+        spec = np.zeros(1, dtype=WAVE_SPEC_DTYPE)
+        spec["lat_bins"], spec["lat_width"], spec["depth_bins"] = lat_bins, lat_width, depth_bins
+        rw = len(WAVE_HEAD) + max(int(lat_bins), 0) + max(int(depth_bins), 0)
+        out = np.zeros((max(ns, 1), rw), dtype=np.int64)
+        org = None
+        if origins is not None:
+            org = np.ascontiguousarray(origins, dtype=np.int64).reshape(-1)
+            if org.size != ns:
+                raise ValueError(f"{org.size} origins for {ns} snapshots")
+            org = np.concatenate([org, np.zeros(1, dtype=np.int64)])       # (never an empty buffer)
+        _check(self._L.cl_graph_snapshot_wave(self._h, sid_lo, sid_hi, _p(spec), None if org is None else _p(org),
+                                              _p(out), ns * rw))
+        return SnapshotWave(out[:ns], lat_bins, lat_width, depth_bins)
+
+    def wave_time(self):
+        """(device ms of the latest snapshot_wave call's kernels, its pointer-doubling rounds)."""
+        ms, rounds = C.c_double(0), C.c_int32(0)
+        _check(self._L.cl_graph_wave_time(self._h, C.byref(ms), C.byref(rounds)))
+        return ms.value, rounds.value
+
+    def set_wave_scratch(self, nbytes=0):
+        """Bytes of device scratch one chunk of snapshot ids may take in snapshot_wave and
+        snapshot_tree (0: the default, 256 MiB).  The results do not depend on it."""
+        _check(self._L.cl_graph_set_wave_scratch(self._h, nbytes))
+
+    def _tree_planes(self, sid_lo, sid_hi, ticks, width):
+        """(parent, tick | None) int32[ns, width] of one cl_graph_snapshot_tree call."""
+        ns = max(sid_hi - sid_lo, 0)
+        parent = np.zeros((max(ns, 1), width), dtype=np.int32)
+        tick = np.zeros((max(ns, 1), width), dtype=np.int32) if ticks else None
+        _check(self._L.cl_graph_snapshot_tree(self._h, sid_lo, sid_hi, _p(parent), None if tick is None else _p(tick)))
+        return parent[:ns], None if tick is None else tick[:ns]
+
+    def snapshot_tree(self, sid_lo=0, sid_hi=None, ticks=True):
+        """One MarkerTree per snapshot of [sid_lo, sid_hi) (default: all): the creating sender
+        and, with ticks, the creation epoch of every node, packed on the device
+        (cl_graph_snapshot_tree)."""
+        if sid_hi is None:
+            sid_hi = self.num_snapshots
+        parent, tick = self._tree_planes(sid_lo, sid_hi, ticks, self.num_nodes)
+        return [MarkerTree(parent[r], None if tick is None else tick[r], 0, sid_lo + r) for r in range(len(parent))]
+
     def _collect_sparse(self, sid_lo, sid_hi, complete=None, row_offsets=None, channel=None, count=None, ent_cap=0,
                         msg_tokens=None, msg_cap=0, tokens=None):
         """One cl_graph_collect_sparse call: (return code, info record)."""
@@ -933,6 +1167,37 @@ class PartitionedGraphSim:
         for t in parts[1:]:
             out = out.merge(t)
         return out
+
+    def snapshot_wave(self, sid_lo=0, sid_hi=None, lat_bins=64, lat_width=1):
+        """The whole run's latency profile (SnapshotWave with depth_bins=0) on every rank: the
+        origins are the start ticks of the merged snapshot_table, each part reduces its own nodes
+        against them, and the parts' rows are all-gathered and merged.  The depth needs the whole
+        tree: snapshot_tree(sid).depth()."""
+        if sid_hi is None:
+            sid_hi = self.n_sids
+        origins = self.snapshot_table().rows["start_tick"][sid_lo:sid_hi]
+        mine = self.g.snapshot_wave(sid_lo, sid_hi, lat_bins, lat_width, 0, origins=origins)
+        words = mine.rows.ravel()
+        allw = self.D.allgather_ints(words.tolist() or [0], self.dev)[:, :words.size]
+        out = None
+        for w in allw:
+            part = SnapshotWave(np.ascontiguousarray(w), lat_bins, lat_width, 0)
+            out = part if out is None else out.merge(part)
+        return out
+
+    def snapshot_tree(self, sid, ticks=True):
+        """The whole MarkerTree of snapshot sid on every rank: the parts' planes (each rank's
+        nodes; the parents are global ranks) all-gathered in rank order."""
+        parent, tick = self.g._tree_planes(sid, sid + 1, ticks, self.hi - self.lo)
+        mine = np.concatenate([parent[0], tick[0]] if ticks else [parent[0]]).astype(np.int64)
+        pad = np.full((2 if ticks else 1) * self.span - mine.size, -2, dtype=np.int64)   # (equal lengths)
+        allw = self.D.allgather_ints(np.concatenate([mine, pad]).tolist(), self.dev)
+        ps, ts = [], []
+        for r, w in enumerate(allw):
+            k = min(self.n, (r + 1) * self.span) - min(self.n, r * self.span)
+            ps.append(w[:k])
+            ts.append(w[k:2 * k])
+        return MarkerTree(np.concatenate(ps), np.concatenate(ts) if ticks else None, 0, sid)
 
     def collect_sparse(self, sid_lo=0, sid_hi=None, tokens=False, payloads=True):
         """The whole run's SparseSnapshots on every rank: the parts' sparse collects (each

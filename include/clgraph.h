@@ -186,6 +186,75 @@ int cl_graph_snapshot_table(cl_graph* g, int32_t sid_lo, int32_t sid_hi, cl_grap
 /* Device ms of the latest table call's kernels (HIP events on the engine's stream). */
 int cl_graph_table_time(cl_graph* g, double* ms);
 
+/* ---- marker-wave profile and marker tree per snapshot, on the device ---------------
+ * A node's local snapshot of a sid is created by the first marker of the sid delivered to it
+ * (the reference's scan order: lowest tick, then lowest sender rank), or by StartSnapshot at
+ * the initiator.  The engine keeps that tick and that sender per (snapshot, node); these calls
+ * read them out at scale: how the marker wave spread over time, and the spanning tree it took.
+ * Only the node records are read, no channel plane.  All results are exact integers and pure
+ * functions of the run.
+ *
+ * cl_graph_snapshot_wave: row r (snapshot sid_lo + r) = CL_WV_HEAD + lat_bins + depth_bins
+ * int64 words, reduced over the owned nodes that hold a local snapshot of the sid.
+ *   latency  creation tick - origin (signed); bin = latency < 0 ? 0 : min(latency / lat_width,
+ *            lat_bins - 1).  origins == NULL: the origin of a sid is the creation tick of its
+ *            initiator's record -- the table's start_tick -- and -1 with the row left at its
+ *            identities if the run never started it.  An origins array gives the origin of
+ *            every row, whatever its sign.
+ *   depth    (depth_bins > 0) tree edges from the node up to the initiator along the creating
+ *            senders, the initiator at 0; bin = min(depth, depth_bins - 1).  Computed by pointer
+ *            doubling over an 8-byte {ancestor, hops} pair per (sid, node); the sid range is
+ *            processed in chunks whose pairs fit in 256 MiB (one sid at least), counted in
+ *            cl_graph_device_bytes.  Rounds run until none moves a pair, at most 32.
+ *   guard    before the first round every node's creating sender must lie in [0, N), hold a
+ *            local snapshot of the sid and have a strictly smaller creation tick.  A node that
+ *            fails is a root that is not the initiator; it and every node whose chain ends at
+ *            it are left out of the depth fields and counted in CL_WV_BROKEN.  The engine's
+ *            runs always pass: the guard keeps the call inside its planes and finite on any
+ *            record contents, and CL_WV_BROKEN != 0 reports an engine defect.
+ * Errors, all before any device work and with `out` untouched: CL_E_INVALID on a NULL g, spec
+ * or out, lat_bins outside [1, CL_GRAPH_WAVE_MAX_BINS], lat_width < 1, depth_bins outside
+ * [0, CL_GRAPH_WAVE_MAX_BINS], a non-zero reserved, or a range outside 0 <= sid_lo <= sid_hi <=
+ * num_snapshots; CL_E_LIMIT if out_words < rows x row words; CL_E_STATE in a partitioned run with
+ * depth_bins > 0 (the parents' records live on other devices) or with origins == NULL (only the
+ * initiator's owner knows the start: pass the merged table's start_tick).  An empty range
+ * returns CL_OK and launches nothing.  Partitioned runs: this device's nodes; the rows of the
+ * parts add up (graph.py SnapshotWave.merge). */
+#define CL_GRAPH_WAVE_MAX_BINS 1024
+typedef struct { int32_t lat_bins, lat_width, depth_bins, reserved; } cl_graph_wave_spec;
+#define CL_WV_SID 0
+#define CL_WV_ORIGIN 1      /* the tick latencies are measured from */
+#define CL_WV_CREATED 2     /* owned nodes with a local snapshot */
+#define CL_WV_LAT_SUM 3
+#define CL_WV_LAT_SUMSQ 4   /* modulo 2^64, like the batch statistics */
+#define CL_WV_LAT_MIN 5     /* INT64_MAX when CREATED == 0 */
+#define CL_WV_LAT_MAX 6     /* INT64_MIN when CREATED == 0 */
+#define CL_WV_DEPTH_SUM 7
+#define CL_WV_DEPTH_SUMSQ 8
+#define CL_WV_DEPTH_MAX 9   /* -1 when depth is off or nothing was created */
+#define CL_WV_BROKEN 10     /* nodes under a root the guard made; 0 in every run */
+#define CL_WV_HEAD 12       /* word 11 reserved, 0; lat_hist[lat_bins], then depth_hist[depth_bins] follow */
+int cl_graph_snapshot_wave(cl_graph* g, int32_t sid_lo, int32_t sid_hi, const cl_graph_wave_spec* spec,
+                           const int64_t* origins /* [sid_hi - sid_lo] or NULL */, int64_t* out, int64_t out_words);
+/* Device ms of the latest wave call's kernels (HIP events on the engine's stream, the reads of
+ * the round flag between them included) and, with rounds != NULL, its doubling rounds: the most
+ * any chunk of sids ran, the round that moved nothing included; 0 with the depth off.
+ * CL_E_STATE before any wave call. */
+int cl_graph_wave_time(cl_graph* g, double* ms, int32_t* rounds /* may be NULL */);
+/* Bytes of scratch one chunk of sids may take in the wave and tree calls (0 = the default,
+ * 256 MiB; a chunk holds one sid at least).  The results do not depend on it. */
+int cl_graph_set_wave_scratch(cl_graph* g, int64_t bytes);
+/* The tree itself over the owned ranks [node_lo, node_hi) (all nodes outside the partitioned
+ * mode): parent[r][v - node_lo] = the rank of the creating sender of node v's local snapshot of
+ * sid_lo + r (a global rank, also in a partitioned run), -1 at the initiator, -2 where there is
+ * no local snapshot; tick = the creation epoch, or -1.  A pack kernel writes the two int32 planes
+ * on the device, so 8 bytes per node cross to the host, 4 with tick == NULL.  CL_E_INVALID on a
+ * NULL g or parent or a range outside 0 <= sid_lo <= sid_hi <= num_snapshots, before any device
+ * work; an empty range returns CL_OK and launches nothing. */
+int cl_graph_snapshot_tree(cl_graph* g, int32_t sid_lo, int32_t sid_hi,
+                           int32_t* parent /* [sid_hi - sid_lo][node_hi - node_lo] */,
+                           int32_t* tick /* same shape, or NULL */);
+
 /* ---- sparse packed collect of snapshot contents, compacted on the device -----------
  * The recorded channel state of the COMPLETED snapshots of [sid_lo, sid_hi), one entry per
  * channel with at least one recorded message: entry i is channel ent_channel[i] (the channel
