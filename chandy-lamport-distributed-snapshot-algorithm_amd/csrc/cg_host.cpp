@@ -20,7 +20,6 @@
 #include <map>
 #include <tuple>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <numeric>
@@ -29,9 +28,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/clgraph.h"
-#include "cg_engine.h"
-#include "cl_dev.h"
+#include "cg_host.h"
 #include "cl_text.h"
 
 using namespace clsnap;
@@ -114,11 +111,8 @@ struct cl_graph {
   size_t ev_used = 0;
   double run_ms = 0;
   int64_t runs = 0, run_ticks = 0, pending_ticks = 0;
-  // timing only: no cache writeback per record
-  template <int N>
-  using Timer = DevTimer<N, hipEventDisableSystemFence>;
   // phases of the latest run (cl_graph_phase_time): start, first drain, end; done: a run has begun
-  Timer<3> ph;
+  GraphTimer<3> ph;
   bool ph_drain = false, ph_fresh = false;
   int64_t ph_time[3] = {0, 0, 0};
 
@@ -145,30 +139,10 @@ struct cl_graph {
   DevBuf<GOp> d_ops;
   DevBuf<uint8_t> d_sched;
   DevBuf<unsigned long long> d_scratch;
-  // per-snapshot summary table (cl_graph_snapshot_table): channel of every in-position, the
-  // device rows, the events around the latest call's kernels
+  // the readouts (cg_host.h): the table's channel of every in-position, the CU count, their own scratch and timers
   DevBuf<int32_t> d_in_ch;
-  DevBuf<long long> d_table;
-  Timer<2> tb;
   int32_t n_cus = 0;
-  // sparse packed collect (cl_graph_collect_sparse): per-(sid, tile) offsets, per-sid totals,
-  // the head the host reads between scan and write (row_offsets, message offsets, complete),
-  // the packed outputs, and the events around the scan ([0], [1]) and the write ([2], [3]);
-  // done: the pairs of the latest call that completed
-  DevBuf<ulonglong2> d_sp_tiles, d_sp_rows;
-  DevBuf<long long> d_sp_head;
-  DevBuf<int32_t> d_sp_chan, d_sp_cnt, d_sp_msg, d_sp_tok;
-  Timer<4> sp;
-  // marker-wave profile and tree (cl_graph_snapshot_wave / _tree): the device rows, the origins
-  // (or initiator ranks) of the rows, the doubling round's flag, and the scratch of one chunk of
-  // sids -- the {ancestor, hops} pairs of the wave, the packed planes of the tree; the events
-  // around the latest wave call's kernels and its doubling rounds
-  DevBuf<long long> d_wv_rows, d_wv_org;
-  DevBuf<int32_t> d_wv_flag;
-  DevBuf<unsigned long long> d_wv_scratch;
-  Timer<2> wv;
-  int32_t wv_rounds = 0;
-  size_t wv_budget = 0;  // bytes of scratch per chunk of sids (0: kWaveScratchBytes; cl_graph_set_wave_scratch)
+  Readouts* readouts = readouts_new();
   size_t ops_uploaded = 0;
   // device event trace (cl_graph_trace_enable)
   int32_t trace_cap = 0;
@@ -190,13 +164,17 @@ struct cl_graph {
   void *bk_send = nullptr, *bk_recv = nullptr, *tot_send = nullptr, *tot_recv = nullptr;
   DevBuf<uint32_t> d_bk_cnt;
 
+  // What has an order: streams drain, readouts go, then run events and stream; members after this body.
   ~cl_graph() {
+    if (dev_ready) {
+      (void)hipSetDevice(device);
+      // both streams drain before any buffer is freed: the caller's (cl_graph_set_stream) and
+      // the engine's own, which may hold work issued before the switch
+      (void)hipStreamSynchronize(stream);
+      if (own_stream != stream) (void)hipStreamSynchronize(own_stream);
+    }
+    readouts_delete(readouts);  // (a graph that never reached a device has them too, empty)
     if (!dev_ready) return;
-    (void)hipSetDevice(device);
-    // both streams drain before any buffer is freed: the caller's (cl_graph_set_stream) and
-    // the engine's own, which may hold work issued before the switch
-    (void)hipStreamSynchronize(stream);
-    if (own_stream != stream) (void)hipStreamSynchronize(own_stream);
     for (auto& ev : ev_pool) {
       (void)hipEventDestroy(ev.first);
       (void)hipEventDestroy(ev.second);
@@ -231,22 +209,7 @@ struct cl_graph {
   }
 
   // rank of an id, -1 if unknown
-  int32_t rank_of_id(const char* id) const {
-    if (!id) return -1;
-    if (bulk) {
-      const size_t L = std::strlen(id);
-      if (L != (size_t)id_width + 1 || id[0] != 'N') return -1;
-      int64_t v = 0;
-      for (size_t i = 1; i < L; ++i) {
-        if (id[i] < '0' || id[i] > '9') return -1;
-        v = v * 10 + (id[i] - '0');
-      }
-      return v < n ? (int32_t)v : -1;
-    }
-    auto it = id_index.find(id);
-    if (it == id_index.end()) return -1;
-    return frozen ? rank_of[it->second] : it->second;
-  }
+  int32_t rank_of_id(const char* id) const { return id ? rank_of_sv(std::string_view(id)) : -1; }
 
   // channels (src rank, dst rank), sorted and unique -> CSR
   int build_csr(std::vector<std::pair<int32_t, int32_t>>& ch) {
@@ -558,16 +521,17 @@ struct cl_graph {
     return CL_OK;
   }
 
-  int k_err(int e_) {
-    if (e_) return set_err(CL_E_DEVICE, "graph kernel launch failed: %s", hipGetErrorString((hipError_t)e_));
+  // one more tick of simulated time, while the pick words can hold it
+  int advance_time() {
+    if (time + 1 > kMaxGraphTime) return set_err(CL_E_LIMIT, "simulated time would exceed %lld ticks", (long long)kMaxGraphTime);
+    ++time;
     return CL_OK;
   }
 
   int launch_tick() {
-    if (time + 1 > kMaxGraphTime) return set_err(CL_E_LIMIT, "simulated time would exceed %lld ticks", (long long)kMaxGraphTime);
-    ++time;
+    if (int rc = advance_time()) return rc;
     ++run_ticks;
-    return k_err(cg_launch_tick(P, (int32_t)time, stream));
+    return launch_err(cg_launch_tick(P, (int32_t)time, stream));
   }
 
   // Host events [pend_begin, +pend_count) in program order.  Maximal runs of at least
@@ -591,43 +555,42 @@ struct cl_graph {
       }
       while (j < end && gops[j].kind == GOP_SEND && seen_stamp[gops[j].a] != stamp) seen_stamp[gops[j].a] = stamp, ++j;
       if (j - i >= kSendGroupMin) {
-        if (i > seq) rc = k_err(cg_launch_hostops(P, (int32_t)time, (int32_t)seq, (int32_t)(i - seq), stream));
-        if (rc == CL_OK) rc = k_err(cg_launch_sendgroup(P, (int32_t)time, (int32_t)i, (int32_t)(j - i), stream));
+        if (i > seq) rc = launch_err(cg_launch_hostops(P, (int32_t)time, (int32_t)seq, (int32_t)(i - seq), stream));
+        if (rc == CL_OK) rc = launch_err(cg_launch_sendgroup(P, (int32_t)time, (int32_t)i, (int32_t)(j - i), stream));
         i = seq = j;
       } else {
         i = std::max(j, i + 1);
       }
     }
-    if (rc == CL_OK && end > seq) rc = k_err(cg_launch_hostops(P, (int32_t)time, (int32_t)seq, (int32_t)(end - seq), stream));
+    if (rc == CL_OK && end > seq) rc = launch_err(cg_launch_hostops(P, (int32_t)time, (int32_t)seq, (int32_t)(end - seq), stream));
     pend_begin = end;
     pend_count = 0;
     return rc;
   }
 
-  int read_status(int32_t* st) {
-    GScal sc;
-    HIP_TRY(hipMemcpyAsync(&sc, d_sc.p, sizeof sc, hipMemcpyDeviceToHost, stream));
+  // the device scalars, stream-ordered: queued after what is on the stream, then waited for
+  int read_scal(GScal* sc) {
+    HIP_TRY(hipMemcpyAsync(sc, d_sc.p, sizeof *sc, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    *st = sc.status;
     return CL_OK;
   }
+  int64_t reported_time(const GScal& sc) const { return sc.status ? sc.time : time; }  // (a frozen run: the device's)
 
   // test_common.go:123-137: tick until the snapshots started before this drain (sids
   // [0, n_before)) have completed, then +6.  Later snapshots are not waited for.  The
   // loop runs on the device (k_drain_ctl before every tick decides whether it runs), so
   // the host launches ticks in growing batches and reads the drain state once per batch.
   int run_drain(int32_t n_before) {
-    int rc = k_err(cg_launch_drain_begin(P, (int32_t)time, n_before, max_drain, stream));
+    int rc = launch_err(cg_launch_drain_begin(P, (int32_t)time, n_before, max_drain, stream));
     if (rc) return rc;
     const int32_t time0 = (int32_t)time;
     int32_t batch = 8;
     int64_t launched = 0;  // drain ticks launched (tick i uses control slot i & 1)
     GScal sc;
     for (;;) {
-      if ((rc = k_err(cg_launch_drain_ticks(P, n_before, max_drain, launched, batch, stream)))) return rc;
+      if ((rc = launch_err(cg_launch_drain_ticks(P, n_before, max_drain, launched, batch, stream)))) return rc;
       launched += batch;
-      HIP_TRY(hipMemcpyAsync(&sc, d_sc.p, sizeof sc, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
+      if ((rc = read_scal(&sc))) return rc;
       if (sc.status || sc.dphase == kDrainDone || sc.dphase == kDrainHang) break;
       batch = std::min(batch * 2, 256);
     }
@@ -635,7 +598,7 @@ struct cl_graph {
     if (!sc.status) time = sc.time;  // (a frozen run reports the device time itself)
     else time = std::max<int64_t>(time, sc.time);
     run_ticks += std::max<int64_t>(0, time - time0);
-    return k_err(cg_launch_drain_end(P, stream));
+    return launch_err(cg_launch_drain_end(P, stream));
   }
 
   // Execute program ops [executed, end) on the device; from scratch if `fresh`.
@@ -674,10 +637,10 @@ struct cl_graph {
       gop_cursor = 0;
       time = 0;
       hang = false;
-      if ((rc = k_err(cg_launch_reset(P, d_init_tok.p, stream)))) return rc;
+      if ((rc = launch_err(cg_launch_reset(P, d_init_tok.p, stream)))) return rc;
       // a replay from the initial state restarts the log (an incremental run appends)
       if (trace_cap > 0) HIP_TRY(hipMemsetAsync(d_trace_cnt.p, 0, sizeof(uint32_t), stream));
-      if (traffic_steps > 0 && (rc = k_err(cg_launch_sends(P, 0, stream)))) return rc;  // step 0 traffic
+      if (traffic_steps > 0 && (rc = launch_err(cg_launch_sends(P, 0, stream)))) return rc;  // step 0 traffic
     }
     state_valid = false;
     size_t pend_begin = gop_cursor, pend_count = 0;
@@ -757,17 +720,41 @@ struct cl_graph {
   }
 };
 
-// ---------------------------------------------------------------------------
-// C ABI
-// ---------------------------------------------------------------------------
-#define G_CHECK(g)                                                     \
-  do {                                                                 \
-    if (!(g)) return set_err(CL_E_INVALID, "null cl_graph handle");       \
-  } while (0)
-#define G_TOPO_OPEN(g)                                                                       \
-  do {                                                                                       \
-    if ((g)->frozen) return set_err(CL_E_STATE, "topology changes after events are not supported"); \
-  } while (0)
+// ---- what a readout knows of a graph (cg_host.h) ------------------------------------------
+GraphFacts clsnap::graph_facts(const cl_graph* g) {
+  if (g->part) return GraphFacts{g->n_sids, true, g->part_lo, g->part_hi};
+  return GraphFacts{g->n_sids, false, 0, g->frozen ? g->n : 0};
+}
+
+int clsnap::sid_range_ok(const cl_graph* g, int32_t sid_lo, int32_t sid_hi) {
+  if (sid_lo < 0 || sid_lo > sid_hi || sid_hi > g->n_sids)
+    return set_err(CL_E_INVALID, "snapshot range [%d, %d) outside [0, %d]", sid_lo, sid_hi, g->n_sids);
+  return CL_OK;
+}
+
+int clsnap::graph_view(cl_graph* g, GraphView* out) {
+  const int rc = g->flush();
+  const GParams& P = g->P;  // (part_lo .. part_hi: all nodes outside the partitioned mode)
+  if (!rc)
+    *out = GraphView{&P, g->stream, g->n_cus, g->d_in_ch.p, g->in_off[(size_t)P.part_lo], g->in_off[(size_t)P.part_hi], g->hist};
+  return rc;
+}
+
+void clsnap::graph_initiators(const cl_graph* g, int32_t sid_lo, int32_t sid_hi, long long* out) {
+  std::fill(out, out + (sid_hi - sid_lo), -1);
+  for (const GOp& op : g->gops)
+    if (op.kind == GOP_SNAP && op.b >= sid_lo && op.b < sid_hi) out[op.b - sid_lo] = op.a;
+}
+
+Readouts* clsnap::graph_readouts(const cl_graph* g) { return g->readouts; }
+
+// ---- C ABI ------------------------------------------------------------------------------------
+#define G_TOPO_OPEN(g) \
+  if ((g)->frozen) return set_err(CL_E_STATE, "topology changes after events are not supported")
+// the opening of a call that needs the topology in rank order: the first of them freezes it
+#define G_FROZEN(g) \
+  GRAPH_CALL(g);    \
+  if (int rc_ = (g)->freeze()) return rc_
 
 extern "C" {
 
@@ -785,14 +772,14 @@ int cl_graph_destroy(cl_graph* g) {
 }
 
 int cl_graph_set_device(cl_graph* g, int32_t device_ordinal) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (g->dev_ready) return set_err(CL_E_STATE, "device already selected");
   g->device = device_ordinal;
   return CL_OK;
 }
 
 int cl_graph_add_node(cl_graph* g, const char* id, int64_t tokens) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   G_TOPO_OPEN(g);
   if (g->bulk) return set_err(CL_E_STATE, "bulk topology already set");
   if (!id) return set_err(CL_E_INVALID, "null id");
@@ -807,7 +794,7 @@ int cl_graph_add_node(cl_graph* g, const char* id, int64_t tokens) {
 }
 
 int cl_graph_add_link(cl_graph* g, const char* src, const char* dest) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   const int a = g->rank_of_id(src), b = g->rank_of_id(dest);
   if (a < 0) return set_err(CL_E_UNKNOWN_NODE, "Node %s does not exist", src ? src : "(null)");  // sim.go:49-51
   if (b < 0) return set_err(CL_E_UNKNOWN_NODE, "Node %s does not exist", dest ? dest : "(null)");  // sim.go:52-54
@@ -823,7 +810,7 @@ int cl_graph_add_link(cl_graph* g, const char* src, const char* dest) {
 // over newline-aligned chunks (read-only id lookups) and appended in file order; the
 // first error in file order is the one reported, as in a sequential parse.
 int cl_graph_read_topology_text(cl_graph* g, const char* text) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!text) return set_err(CL_E_INVALID, "null text");
   const std::string_view all(text);
   LineIter it{all};
@@ -907,7 +894,7 @@ int cl_graph_read_topology_text(cl_graph* g, const char* text) {
 }
 
 int cl_graph_read_topology_file(cl_graph* g, const char* path) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   std::string text;
   if (!path || !read_file(path, &text)) return set_err(CL_E_IO, "cannot read %s", path ? path : "(null)");
   return cl_graph_read_topology_text(g, text.c_str());
@@ -915,12 +902,12 @@ int cl_graph_read_topology_file(cl_graph* g, const char* path) {
 
 int cl_graph_set_topology(cl_graph* g, int32_t n_nodes, int32_t id_width, const int64_t* tokens, int64_t n_edges,
                           const int32_t* src, const int32_t* dst) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   return g->set_topology(n_nodes, id_width, tokens, n_edges, src, dst);
 }
 
 int cl_graph_generate_regular(cl_graph* g, int32_t n_nodes, int32_t degree, int64_t tokens, uint64_t seed) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (n_nodes <= 0 || degree < 0 || degree > kGMaxOutDegree) return set_err(CL_E_INVALID, "bad regular graph size");
   const size_t N = (size_t)n_nodes;
   std::vector<int32_t> src(N * degree), dst(N * degree);
@@ -946,7 +933,7 @@ int cl_graph_generate_regular(cl_graph* g, int32_t n_nodes, int32_t degree, int6
 
 int cl_graph_generate_powerlaw(cl_graph* g, int32_t n_nodes, int32_t targets, double exponent, int32_t ring,
                                int64_t tokens, uint64_t seed) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (n_nodes <= 0 || targets < 0 || targets > kGMaxOutDegree - 2) return set_err(CL_E_INVALID, "bad power-law graph size");
   const size_t N = (size_t)n_nodes;
   std::vector<double> cdf(N);
@@ -982,7 +969,7 @@ int cl_graph_generate_powerlaw(cl_graph* g, int32_t n_nodes, int32_t targets, do
 }
 
 int cl_graph_num_nodes(cl_graph* g, int32_t* n) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!n) return set_err(CL_E_INVALID, "null output");
   int rc = g->freeze();
   if (rc) return rc;
@@ -991,7 +978,7 @@ int cl_graph_num_nodes(cl_graph* g, int32_t* n) {
 }
 
 int cl_graph_num_channels(cl_graph* g, int64_t* n) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!n) return set_err(CL_E_INVALID, "null output");
   int rc = g->freeze();
   if (rc) return rc;
@@ -1000,18 +987,14 @@ int cl_graph_num_channels(cl_graph* g, int64_t* n) {
 }
 
 int cl_graph_channels(cl_graph* g, int32_t* src, int32_t* dst) {
-  G_CHECK(g);
-  int rc = g->freeze();
-  if (rc) return rc;
+  G_FROZEN(g);
   if (src) std::copy(g->ch_src.begin(), g->ch_src.end(), src);
   if (dst) std::copy(g->ch_dst.begin(), g->ch_dst.end(), dst);
   return CL_OK;
 }
 
 int cl_graph_node_id(cl_graph* g, int32_t rank, char* buf, int32_t cap) {
-  G_CHECK(g);
-  int rc = g->freeze();
-  if (rc) return rc;
+  G_FROZEN(g);
   if (rank < 0 || rank >= g->n || !buf || cap <= 0) return set_err(CL_E_INVALID, "bad rank or buffer");
   const std::string s = g->node_id(rank);
   if ((int32_t)s.size() >= cap) return set_err(CL_E_LIMIT, "buffer too small");
@@ -1020,7 +1003,7 @@ int cl_graph_node_id(cl_graph* g, int32_t rank, char* buf, int32_t cap) {
 }
 
 int cl_graph_set_limits(cl_graph* g, int32_t fifo_slots, int32_t max_snapshots, int64_t max_drain_ticks) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   int l = 0;
   while ((1 << l) < fifo_slots) ++l;
   if (fifo_slots < 2 || fifo_slots > 32768 || (1 << l) != fifo_slots)
@@ -1034,7 +1017,7 @@ int cl_graph_set_limits(cl_graph* g, int32_t fifo_slots, int32_t max_snapshots, 
 }
 
 int cl_graph_set_push_lanes(cl_graph* g, int32_t lanes) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (lanes != 0 && lanes != 1 && lanes != kPushLanes)
     return set_err(CL_E_INVALID, "push lanes must be 0 (automatic), 1 or %d", kPushLanes);
   g->push_lanes = lanes;
@@ -1042,16 +1025,14 @@ int cl_graph_set_push_lanes(cl_graph* g, int32_t lanes) {
 }
 
 int cl_graph_node_id_length(cl_graph* g, int32_t rank, int32_t* len) {
-  G_CHECK(g);
-  int rc = g->freeze();
-  if (rc) return rc;
+  G_FROZEN(g);
   if (rank < 0 || rank >= g->n || !len) return set_err(CL_E_INVALID, "bad rank or output");
   *len = (int32_t)g->node_id(rank).size();
   return CL_OK;
 }
 
 int cl_graph_set_delay_hash(cl_graph* g, uint64_t seed) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   g->delay_mode = 0;
   g->delay_seed = seed;
   g->go_seed = false;
@@ -1060,7 +1041,7 @@ int cl_graph_set_delay_hash(cl_graph* g, uint64_t seed) {
 }
 
 int cl_graph_set_delay_go_seed(cl_graph* g, int64_t seed) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   g->delay_mode = 1;
   g->go_seed = true;
   g->go_seed_val = seed;
@@ -1070,7 +1051,7 @@ int cl_graph_set_delay_go_seed(cl_graph* g, int64_t seed) {
 }
 
 int cl_graph_set_delay_schedule(cl_graph* g, const uint8_t* delays, int64_t n) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!delays || n <= 0) return set_err(CL_E_INVALID, "empty schedule");
   for (int64_t i = 0; i < n; ++i)
     if (delays[i] >= 5) return set_err(CL_E_INVALID, "delay %u at %lld outside [0, maxDelay)", delays[i], (long long)i);
@@ -1083,7 +1064,7 @@ int cl_graph_set_delay_schedule(cl_graph* g, const uint8_t* delays, int64_t n) {
 }
 
 int cl_graph_set_traffic(cl_graph* g, uint64_t seed, uint32_t threshold, int64_t steps) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (steps < 0) return set_err(CL_E_INVALID, "negative traffic steps");
   g->traffic_seed = seed;
   g->traffic_thresh = threshold;
@@ -1093,50 +1074,38 @@ int cl_graph_set_traffic(cl_graph* g, uint64_t seed, uint32_t threshold, int64_t
 }
 
 int cl_graph_send_tokens_rank(cl_graph* g, int32_t src, int32_t dest, int64_t n) {
-  G_CHECK(g);
-  int rc = g->freeze();
-  if (rc) return rc;
+  G_FROZEN(g);
   if (src < 0 || src >= g->n) return set_err(CL_E_UNKNOWN_NODE, "send from unknown rank %d", src);
   return g->append_send(src, dest >= 0 && dest < g->n ? dest : -1, n);
 }
 
 int cl_graph_send_tokens(cl_graph* g, const char* src, const char* dest, int64_t n) {
-  G_CHECK(g);
-  int rc = g->freeze();
-  if (rc) return rc;
+  G_FROZEN(g);
   const int32_t a = g->rank_of_id(src);
   if (a < 0) return set_err(CL_E_UNKNOWN_NODE, "send from unknown node %s", src ? src : "(null)");
   return g->append_send(a, g->rank_of_id(dest), n);  // unknown dest: fatal at run time (node.go:121-124)
 }
 
 int cl_graph_start_snapshot_rank(cl_graph* g, int32_t node, int32_t* out_sid) {
-  G_CHECK(g);
-  int rc = g->freeze();
-  if (rc) return rc;
+  G_FROZEN(g);
   if (node < 0 || node >= g->n) return set_err(CL_E_UNKNOWN_NODE, "snapshot at unknown rank %d", node);
   return g->append_snap(node, out_sid);
 }
 
 int cl_graph_start_snapshot(cl_graph* g, const char* node, int32_t* out_sid) {
-  G_CHECK(g);
-  int rc = g->freeze();
-  if (rc) return rc;
+  G_FROZEN(g);
   const int32_t a = g->rank_of_id(node);
   if (a < 0) return set_err(CL_E_UNKNOWN_NODE, "snapshot at unknown node %s", node ? node : "(null)");
   return g->append_snap(a, out_sid);
 }
 
 int cl_graph_tick(cl_graph* g, int32_t n) {
-  G_CHECK(g);
-  int rc = g->freeze();
-  if (rc) return rc;
+  G_FROZEN(g);
   return g->append_tick(n);
 }
 
 int cl_graph_drain(cl_graph* g) {
-  G_CHECK(g);
-  int rc = g->freeze();
-  if (rc) return rc;
+  G_FROZEN(g);
   g->prog.push_back(ProgOp{P_DRAIN, g->n_sids, 0, 0});  // waits for the snapshots started so far
   return CL_OK;
 }
@@ -1146,7 +1115,7 @@ int cl_graph_drain(cl_graph* g) {
 // append to the program without per-line copies; runs of sends from distinct senders
 // execute as parallel send groups (cg_launch_sendgroup).
 int cl_graph_read_events_text(cl_graph* g, const char* text, int32_t* n_snapshots) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!text) return set_err(CL_E_INVALID, "null text");
   int rc = g->freeze();
   if (rc) return rc;
@@ -1184,35 +1153,35 @@ int cl_graph_read_events_text(cl_graph* g, const char* text, int32_t* n_snapshot
 }
 
 int cl_graph_read_events_file(cl_graph* g, const char* path, int32_t* n_snapshots) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   std::string text;
   if (!path || !read_file(path, &text)) return set_err(CL_E_IO, "cannot read %s", path ? path : "(null)");
   return cl_graph_read_events_text(g, text.c_str(), n_snapshots);
 }
 
 int cl_graph_flush(cl_graph* g) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   return g->flush();
 }
 
 int cl_graph_rerun(cl_graph* g) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   return g->run(true);
 }
 
 int cl_graph_synchronize(cl_graph* g) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   return g->sync();
 }
 
 int cl_graph_run_time(cl_graph* g, double* total_ms, int64_t* runs, int64_t* ticks) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!total_ms || !runs || !ticks) return set_err(CL_E_INVALID, "null output");
   return g->fold_time(total_ms, runs, ticks);
 }
 
 int cl_graph_debug_poison_outputs(cl_graph* g) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!g->dev_ready || !g->d_tokens.p) return CL_OK;
   HIP_TRY(hipSetDevice(g->device));
   HIP_TRY(hipMemsetAsync(g->d_tokens.p, 0xA5, g->d_tokens.bytes(), g->stream));
@@ -1226,7 +1195,7 @@ int cl_graph_debug_poison_outputs(cl_graph* g) {
 }
 
 int cl_graph_phase_time(cl_graph* g, double* ms, int64_t* ticks) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!ms || !ticks) return set_err(CL_E_INVALID, "null output");
   if (!g->ph.done) return set_err(CL_E_STATE, "nothing has run");
   int rc = g->sync();
@@ -1245,50 +1214,50 @@ int cl_graph_phase_time(cl_graph* g, double* ms, int64_t* ticks) {
 }
 
 int cl_graph_device_bytes(cl_graph* g, int64_t* bytes) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!bytes) return set_err(CL_E_INVALID, "null output");
-  size_t b = 0;
-  b += g->d_out_off.bytes() + g->d_route.bytes() + g->d_in_off.bytes() +
-       g->d_in_src.bytes() + g->d_init_tok.bytes() + g->d_tokens.bytes() + g->d_pp.bytes() + g->d_tokcnt.bytes() + g->d_in_oj.bytes() +
-       g->d_ltrig.bytes() + g->d_lsend.bytes() + g->d_crn.bytes() + g->d_mlist.bytes() + g->d_mcnt.bytes() +
-       g->d_big.bytes() + g->d_cpart.bytes() +
-       g->d_cre.bytes() + g->d_bsum.bytes() + g->d_hq.bytes() +
-       g->d_histv.bytes() + g->d_fifo.bytes() + g->d_sn.bytes() + g->d_rec.bytes() + g->d_done.bytes() + g->d_ctick.bytes() + g->d_sched.bytes();
-  b += g->d_wv_scratch.bytes() + g->d_wv_rows.bytes() + g->d_wv_org.bytes();  // (the wave's pairs and rows)
-  *bytes = (int64_t)b;
+  // the engine's own: topology, run state and delay schedule; then what the readouts count of theirs
+  const size_t b =
+      g->d_out_off.bytes() + g->d_route.bytes() + g->d_in_off.bytes() + g->d_in_src.bytes() + g->d_init_tok.bytes() +
+      g->d_tokens.bytes() + g->d_pp.bytes() + g->d_tokcnt.bytes() + g->d_in_oj.bytes() + g->d_ltrig.bytes() +
+      g->d_lsend.bytes() + g->d_crn.bytes() + g->d_mlist.bytes() + g->d_mcnt.bytes() + g->d_big.bytes() +
+      g->d_cpart.bytes() + g->d_cre.bytes() + g->d_bsum.bytes() + g->d_hq.bytes() + g->d_histv.bytes() +
+      g->d_fifo.bytes() + g->d_sn.bytes() + g->d_rec.bytes() + g->d_done.bytes() + g->d_ctick.bytes() + g->d_sched.bytes();
+  *bytes = (int64_t)b + readouts_device_bytes(g->readouts);
   return CL_OK;
 }
 
 int cl_graph_get_status(cl_graph* g, int32_t* status) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!status) return set_err(CL_E_INVALID, "null output");
   int rc = g->flush();
   if (rc) return rc;
-  if ((rc = g->read_status(status))) return rc;
-  if (!*status && g->hang) *status = CL_INST_HANG;
+  GScal sc;
+  if ((rc = g->read_scal(&sc))) return rc;
+  *status = !sc.status && g->hang ? CL_INST_HANG : sc.status;
   return CL_OK;
 }
 
 int cl_graph_get_time(cl_graph* g, int64_t* time) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!time) return set_err(CL_E_INVALID, "null output");
   int rc = g->flush();
   if (rc) return rc;
   GScal sc;
-  HIP_TRY(hipMemcpy(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost));
-  *time = sc.status ? sc.time : g->time;
+  if ((rc = g->read_scal(&sc))) return rc;
+  *time = g->reported_time(sc);
   return CL_OK;
 }
 
 int cl_graph_num_snapshots(cl_graph* g, int32_t* n) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!n) return set_err(CL_E_INVALID, "null output");
   *n = g->n_sids;
   return CL_OK;
 }
 
 int cl_graph_node_tokens(cl_graph* g, int64_t* out) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!out) return set_err(CL_E_INVALID, "null output");
   int rc = g->flush();
   if (rc) return rc;
@@ -1299,7 +1268,7 @@ int cl_graph_node_tokens(cl_graph* g, int64_t* out) {
 }
 
 int cl_graph_snapshot_tick(cl_graph* g, int32_t sid, int32_t* tick) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!tick) return set_err(CL_E_INVALID, "null output");
   if (sid < 0 || sid >= g->n_sids) return set_err(CL_E_INVALID, "unknown snapshot %d", sid);
   int rc = g->flush();
@@ -1310,7 +1279,7 @@ int cl_graph_snapshot_tick(cl_graph* g, int32_t sid, int32_t* tick) {
 
 int cl_graph_collect_snapshot(cl_graph* g, int32_t sid, int64_t* tokens, int64_t* msg_offsets, int64_t* msg_tokens,
                               int64_t msg_cap) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (sid < 0 || sid >= g->n_sids) return set_err(CL_E_INVALID, "unknown snapshot %d", sid);
   int32_t tick;
   int rc = cl_graph_snapshot_tick(g, sid, &tick);
@@ -1351,7 +1320,7 @@ int cl_graph_collect_snapshot(cl_graph* g, int32_t sid, int64_t* tokens, int64_t
 }
 
 int cl_graph_trace_enable(cl_graph* g, int32_t capacity) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (capacity < 0) return set_err(CL_E_INVALID, "negative trace capacity");
   g->trace_cap = capacity;
   g->state_valid = false;  // the next flush replays the program with tracing on (or off)
@@ -1359,7 +1328,7 @@ int cl_graph_trace_enable(cl_graph* g, int32_t capacity) {
 }
 
 int cl_graph_trace_read(cl_graph* g, cl_log_event* out, int32_t cap, int32_t* n_events) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!n_events) return set_err(CL_E_INVALID, "null output");
   if (g->trace_cap <= 0) return set_err(CL_E_INVALID, "tracing is off (cl_graph_trace_enable)");
   int rc = g->flush();
@@ -1406,17 +1375,17 @@ int cl_graph_trace_read(cl_graph* g, cl_log_event* out, int32_t cap, int32_t* n_
 }
 
 int cl_graph_get_counters(cl_graph* g, int64_t* out) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!out) return set_err(CL_E_INVALID, "null output");
   int rc = g->flush();
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(g->d_scratch.p, 0, sizeof(unsigned long long), g->stream));
-  if ((rc = g->k_err(cg_launch_finish(g->P, g->n_sids, g->d_scratch.p, g->stream)))) return rc;
+  if ((rc = launch_err(cg_launch_finish(g->P, g->n_sids, g->d_scratch.p, g->stream)))) return rc;
   GScal sc;
   unsigned long long open = 0;
   uint64_t cnt[kNumCnt];
   if ((rc = g->counter_totals(cnt))) return rc;
-  HIP_TRY(hipMemcpyAsync(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipMemcpyAsync(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost, g->stream));  // (one sync for both)
   HIP_TRY(hipMemcpyAsync(&open, g->d_scratch.p, sizeof open, hipMemcpyDeviceToHost, g->stream));
   HIP_TRY(hipStreamSynchronize(g->stream));
   out[CL_CNT_PUSH] = (int64_t)cnt[GC_PUSH];
@@ -1426,26 +1395,25 @@ int cl_graph_get_counters(cl_graph* g, int64_t* out) {
   out[CL_CNT_RECORDED] = (int64_t)open;  // (k_finish: every created local snapshot's recorded copies)
   out[CL_CNT_COMPLETED] = (int64_t)cnt[GC_COMPLETED];
   out[CL_CNT_INSTANCES] = 1;
-  out[CL_CNT_TICKS] = sc.status ? sc.time : g->time;
+  out[CL_CNT_TICKS] = g->reported_time(sc);
   return CL_OK;
 }
 
 int cl_graph_get_checksums(cl_graph* g, int64_t* out) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   if (!out) return set_err(CL_E_INVALID, "null output");
   int rc = g->flush();
   if (rc) return rc;
   const size_t ns = 3 + (size_t)g->n_sids;
   HIP_TRY(hipMemsetAsync(g->d_scratch.p, 0, ns * sizeof(unsigned long long), g->stream));
-  if ((rc = g->k_err(cg_launch_checks(g->P, g->n_sids, g->d_scratch.p, g->stream)))) return rc;
+  if ((rc = launch_err(cg_launch_checks(g->P, g->n_sids, g->d_scratch.p, g->stream)))) return rc;
   std::vector<unsigned long long> r(ns);
   std::vector<int32_t> ct((size_t)std::max(g->n_sids, 1));
   GScal sc;
   HIP_TRY(hipMemcpyAsync(r.data(), g->d_scratch.p, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost, g->stream));
   if (g->n_sids)
     HIP_TRY(hipMemcpyAsync(ct.data(), g->d_ctick.p, (size_t)g->n_sids * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(hipMemcpyAsync(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(hipStreamSynchronize(g->stream));
+  if ((rc = g->read_scal(&sc))) return rc;
   int64_t cut = 0, completed = 0;
   for (int32_t s = 0; s < g->n_sids; ++s) {
     if (ct[s] < 0) continue;
@@ -1466,270 +1434,13 @@ int cl_graph_get_checksums(cl_graph* g, int64_t* out) {
   return CL_OK;
 }
 
-int cl_graph_snapshot_table(cl_graph* g, int32_t sid_lo, int32_t sid_hi, cl_graph_snap_row* rows) {
-  G_CHECK(g);
-  static_assert(sizeof(cl_graph_snap_row) == 16 * sizeof(int64_t), "cl_graph_snap_row is 16 x int64");
-  if (sid_lo < 0 || sid_lo > sid_hi || sid_hi > g->n_sids)
-    return set_err(CL_E_INVALID, "snapshot range [%d, %d) outside [0, %d]", sid_lo, sid_hi, g->n_sids);
-  const int32_t ns = sid_hi - sid_lo;
-  if (ns == 0) return CL_OK;
-  if (!rows) return set_err(CL_E_INVALID, "null output");
-  int rc = g->flush();
-  if (rc) return rc;
-  if ((rc = g->d_table.ensure((size_t)ns * 16))) return rc;
-  g->tb.done = 0;
-  if ((rc = g->tb.mark(0, g->stream))) return rc;
-  // the in-CSR range of the owned nodes (all of them outside the partitioned mode)
-  const int32_t k_lo = g->in_off[(size_t)g->P.part_lo], k_hi = g->in_off[(size_t)g->P.part_hi];
-  if ((rc = g->k_err(cg_launch_table(g->P, g->d_in_ch.p, k_lo, k_hi, sid_lo, ns, g->d_table.p, g->n_cus, g->stream))))
-    return rc;
-  if ((rc = g->tb.mark(1, g->stream))) return rc;
-  HIP_TRY(hipMemcpyAsync(rows, g->d_table.p, (size_t)ns * sizeof(cl_graph_snap_row), hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(hipStreamSynchronize(g->stream));
-  g->tb.done = 1;
-  return CL_OK;
-}
-
-int cl_graph_table_time(cl_graph* g, double* ms) {
-  G_CHECK(g);
-  if (!ms) return set_err(CL_E_INVALID, "null output");
-  if (!g->tb.done) return set_err(CL_E_STATE, "no snapshot table has been computed");
-  return g->tb.ms(0, 1, ms);
-}
-
-// ---- marker-wave profile and marker tree (cg_wave.hip) ------------------------------------
-// Scratch of one chunk of sids: the wave's 8-byte pairs over all nodes, the tree's int32 planes
-// over the owned ones.  256 MiB holds 32 sids of a 2^20-node graph and every sid of a 20,000-node
-// x 256-snapshot run at once, and is small next to the planes of either run; a graph whose single
-// sid needs more takes one sid per chunk.
-constexpr size_t kWaveScratchBytes = (size_t)256 << 20;
-constexpr int32_t kWaveMaxRounds = 32;
-
-int cl_graph_set_wave_scratch(cl_graph* g, int64_t bytes) {
-  G_CHECK(g);
-  if (bytes < 0) return set_err(CL_E_INVALID, "negative scratch budget");
-  g->wv_budget = (size_t)bytes;
-  return CL_OK;
-}
-
-int cl_graph_snapshot_wave(cl_graph* g, int32_t sid_lo, int32_t sid_hi, const cl_graph_wave_spec* spec,
-                           const int64_t* origins, int64_t* out, int64_t out_words) {
-  G_CHECK(g);
-  static_assert(sizeof(cl_graph_wave_spec) == 4 * sizeof(int32_t), "cl_graph_wave_spec is 4 x int32");
-  if (!spec || !out) return set_err(CL_E_INVALID, "null %s", !spec ? "spec" : "output");
-  if (spec->lat_bins < 1 || spec->lat_bins > CL_GRAPH_WAVE_MAX_BINS || spec->lat_width < 1 || spec->depth_bins < 0 ||
-      spec->depth_bins > CL_GRAPH_WAVE_MAX_BINS || spec->reserved)
-    return set_err(CL_E_INVALID, "wave spec: lat_bins %d (1..%d), lat_width %d (>= 1), depth_bins %d (0..%d), reserved %d",
-                spec->lat_bins, CL_GRAPH_WAVE_MAX_BINS, spec->lat_width, spec->depth_bins, CL_GRAPH_WAVE_MAX_BINS,
-                spec->reserved);
-  if (sid_lo < 0 || sid_lo > sid_hi || sid_hi > g->n_sids)
-    return set_err(CL_E_INVALID, "snapshot range [%d, %d) outside [0, %d]", sid_lo, sid_hi, g->n_sids);
-  const int32_t ns = sid_hi - sid_lo, rw = CL_WV_HEAD + spec->lat_bins + spec->depth_bins;
-  if (out_words < (int64_t)ns * rw)
-    return set_err(CL_E_LIMIT, "%d rows of %d words exceed out_words %lld", ns, rw, (long long)out_words);
-  if (g->part && spec->depth_bins > 0)
-    return set_err(CL_E_STATE, "a partitioned run has no device depth: the parents' records live on other devices");
-  if (g->part && !origins)
-    return set_err(CL_E_STATE, "a partitioned run needs the origins: only the initiator's owner knows the start");
-  if (ns == 0) return CL_OK;
-  int rc = g->flush();
-  if (rc) return rc;
-  const GParams& P = g->P;
-  const bool depth = spec->depth_bins > 0;
-  const size_t nsz = (size_t)ns, n = (size_t)P.n;
-  // sids per chunk of pairs
-  const size_t budget = g->wv_budget ? g->wv_budget : kWaveScratchBytes;
-  size_t cs = std::max<size_t>(1, budget / std::max<size_t>(1, n * sizeof(unsigned long long)));
-  cs = std::min(cs, nsz);
-  if ((rc = g->d_wv_rows.ensure(nsz * (size_t)rw)) || (rc = g->d_wv_org.ensure(nsz)) || (rc = g->d_wv_flag.ensure(1)))
-    return rc;
-  if (depth && (rc = g->d_wv_scratch.ensure(cs * n))) return rc;
-  // the origins, or the initiators' ranks (the program's snapshot events)
-  std::vector<long long> org(nsz, -1);
-  if (origins) std::copy(origins, origins + ns, org.begin());
-  else
-    for (const GOp& op : g->gops)
-      if (op.kind == GOP_SNAP && op.b >= sid_lo && op.b < sid_hi) org[(size_t)(op.b - sid_lo)] = op.a;
-  HIP_TRY(hipMemcpyAsync(g->d_wv_org.p, org.data(), nsz * sizeof(long long), hipMemcpyHostToDevice, g->stream));
-  HIP_TRY(hipStreamSynchronize(g->stream));  // (`org` is a local)
-  const int32_t user = origins ? 1 : 0;
-  g->wv.done = 0;
-  g->wv_rounds = 0;
-  if ((rc = g->wv.mark(0, g->stream))) return rc;
-  if ((rc = g->k_err(cg_launch_wave_init(P, g->d_wv_org.p, user, sid_lo, ns, rw, g->d_wv_rows.p, g->stream)))) return rc;
-  if (!depth) {
-    if ((rc = g->k_err(cg_launch_wave(P, sid_lo, ns, rw, spec->lat_bins, spec->lat_width, 0, user, nullptr,
-                                      g->d_wv_rows.p, g->n_cus, g->stream))))
-      return rc;
-  } else {
-    for (size_t c0 = 0; c0 < nsz; c0 += cs) {
-      const int32_t cn = (int32_t)std::min(cs, nsz - c0), sid0 = sid_lo + (int32_t)c0;
-      if ((rc = g->k_err(cg_launch_wave_link(P, sid0, cn, g->d_wv_scratch.p, g->stream)))) return rc;
-      int32_t rounds = 0, moved = 1;
-      while (moved && rounds < kWaveMaxRounds) {  // until a round moves no pair
-        HIP_TRY(hipMemsetAsync(g->d_wv_flag.p, 0, sizeof(int32_t), g->stream));
-        if ((rc = g->k_err(cg_launch_wave_jump(P, cn, g->d_wv_scratch.p, g->d_wv_flag.p, g->stream)))) return rc;
-        HIP_TRY(hipMemcpyAsync(&moved, g->d_wv_flag.p, sizeof moved, hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        ++rounds;
-      }
-      g->wv_rounds = std::max(g->wv_rounds, rounds);
-      if ((rc = g->k_err(cg_launch_wave(P, sid0, cn, rw, spec->lat_bins, spec->lat_width, spec->depth_bins, user,
-                                        g->d_wv_scratch.p, g->d_wv_rows.p + c0 * (size_t)rw, g->n_cus, g->stream))))
-        return rc;
-    }
-  }
-  if ((rc = g->wv.mark(1, g->stream))) return rc;
-  HIP_TRY(hipMemcpyAsync(out, g->d_wv_rows.p, nsz * (size_t)rw * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(hipStreamSynchronize(g->stream));
-  g->wv.done = 1;
-  return CL_OK;
-}
-
-int cl_graph_wave_time(cl_graph* g, double* ms, int32_t* rounds) {
-  G_CHECK(g);
-  if (!ms) return set_err(CL_E_INVALID, "null output");
-  if (!g->wv.done) return set_err(CL_E_STATE, "no snapshot wave has been computed");
-  if (rounds) *rounds = g->wv_rounds;
-  return g->wv.ms(0, 1, ms);
-}
-
-int cl_graph_snapshot_tree(cl_graph* g, int32_t sid_lo, int32_t sid_hi, int32_t* parent, int32_t* tick) {
-  G_CHECK(g);
-  if (!parent) return set_err(CL_E_INVALID, "null output");
-  if (sid_lo < 0 || sid_lo > sid_hi || sid_hi > g->n_sids)
-    return set_err(CL_E_INVALID, "snapshot range [%d, %d) outside [0, %d]", sid_lo, sid_hi, g->n_sids);
-  const int32_t ns = sid_hi - sid_lo;
-  if (ns == 0) return CL_OK;
-  int rc = g->flush();
-  if (rc) return rc;
-  const GParams& P = g->P;
-  const size_t nsz = (size_t)ns, width = (size_t)(P.part_hi - P.part_lo), planes = tick ? 2 : 1;
-  if (width == 0) return CL_OK;
-  // sids per chunk of packed planes
-  const size_t budget = g->wv_budget ? g->wv_budget : kWaveScratchBytes;
-  size_t cs = std::max<size_t>(1, budget / (width * planes * sizeof(int32_t)));
-  cs = std::min(cs, nsz);
-  if ((rc = g->d_wv_scratch.ensure((cs * width * planes + 1) / 2))) return rc;
-  int32_t* d_parent = reinterpret_cast<int32_t*>(g->d_wv_scratch.p);
-  int32_t* d_tick = tick ? d_parent + cs * width : nullptr;
-  for (size_t c0 = 0; c0 < nsz; c0 += cs) {  // (stream order: a chunk's copies end before the next pack)
-    const size_t cn = std::min(cs, nsz - c0);
-    if ((rc = g->k_err(cg_launch_wave_pack(P, sid_lo + (int32_t)c0, (int32_t)cn, d_parent, d_tick, g->stream)))) return rc;
-    HIP_TRY(hipMemcpyAsync(parent + c0 * width, d_parent, cn * width * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (tick)
-      HIP_TRY(hipMemcpyAsync(tick + c0 * width, d_tick, cn * width * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(g->stream));
-  return CL_OK;
-}
-
-int cl_graph_collect_sparse(cl_graph* g, int32_t sid_lo, int32_t sid_hi, int32_t* complete, int64_t* row_offsets,
-                            int32_t* ent_channel, int32_t* ent_count, int64_t ent_cap, int32_t* msg_tokens,
-                            int64_t msg_cap, int32_t* tokens, cl_graph_sparse_info* info) {
-  G_CHECK(g);
-  static_assert(sizeof(cl_graph_sparse_info) == 8 * sizeof(int64_t), "cl_graph_sparse_info is 8 x int64");
-  if (!info) return set_err(CL_E_INVALID, "null info");
-  if (sid_lo < 0 || sid_lo > sid_hi || sid_hi > g->n_sids)
-    return set_err(CL_E_INVALID, "snapshot range [%d, %d) outside [0, %d]", sid_lo, sid_hi, g->n_sids);
-  if (ent_cap < 0 || msg_cap < 0) return set_err(CL_E_INVALID, "negative capacity");
-  if (ent_cap > 0 && (!ent_channel || !ent_count)) return set_err(CL_E_INVALID, "null entry arrays with ent_cap > 0");
-  const int32_t ns = sid_hi - sid_lo;
-  *info = cl_graph_sparse_info{};
-  info->node_lo = g->part ? g->part_lo : 0;
-  info->node_hi = g->part ? g->part_hi : (g->frozen ? g->n : 0);
-  if (ns == 0) {
-    if (row_offsets) row_offsets[0] = 0;
-    return CL_OK;
-  }
-  int rc = g->flush();
-  if (rc) return rc;
-  const GParams& P = g->P;
-  const size_t tiles = (size_t)cg_sparse_tiles(P.e), nsz = (size_t)ns;
-  // head: row_offsets[ns + 1], message offsets[ns + 1], then complete[ns] as int32
-  const size_t head_words = 2 * (nsz + 1) + (nsz + 1) / 2;
-  if ((rc = g->d_sp_tiles.ensure(nsz * tiles)) || (rc = g->d_sp_rows.ensure(nsz)) ||
-      (rc = g->d_sp_head.ensure(head_words)))
-    return rc;
-  long long* d_off = g->d_sp_head.p;
-  long long* d_moff = d_off + (nsz + 1);
-  int32_t* d_complete = reinterpret_cast<int32_t*>(d_moff + (nsz + 1));
-  g->sp.done = 0;
-  if ((rc = g->sp.mark(0, g->stream))) return rc;
-  if ((rc = g->k_err(cg_launch_sparse_scan(P, sid_lo, ns, g->d_sp_tiles.p, g->d_sp_rows.p, d_off, d_moff, d_complete,
-                                           g->stream))))
-    return rc;
-  if ((rc = g->sp.mark(1, g->stream))) return rc;
-  // the totals decide the sizes: the host reads the head between scan and write
-  std::vector<long long> head(head_words);
-  HIP_TRY(hipMemcpyAsync(head.data(), d_off, head_words * sizeof(long long), hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(hipStreamSynchronize(g->stream));
-  g->sp.done = 1;
-  const int32_t* h_complete = reinterpret_cast<const int32_t*>(head.data() + 2 * (nsz + 1));
-  const int64_t n_entries = head[nsz], n_msgs = head[2 * nsz + 1];
-  info->n_sids = ns;
-  for (int32_t r = 0; r < ns; ++r) info->n_complete += h_complete[r] != 0;
-  info->n_entries = n_entries;
-  info->n_msgs = n_msgs;
-  info->unit_payloads = g->hist == 0 ? 1 : 0;
-  if (complete) std::copy(h_complete, h_complete + ns, complete);
-  if (row_offsets) std::copy(head.begin(), head.begin() + (ns + 1), row_offsets);
-  if (n_entries > ent_cap)
-    return set_err(CL_E_LIMIT, "%lld entries exceed ent_cap %lld", (long long)n_entries, (long long)ent_cap);
-  if (msg_tokens && n_msgs > msg_cap)
-    return set_err(CL_E_LIMIT, "%lld messages exceed msg_cap %lld", (long long)n_msgs, (long long)msg_cap);
-  // unit payloads are all 1: no history on the device, nothing to pack or copy
-  const bool dev_msgs = msg_tokens && g->hist > 0 && n_msgs > 0;
-  const int64_t width = info->node_hi - info->node_lo;
-  if ((rc = g->d_sp_chan.ensure((size_t)n_entries)) || (rc = g->d_sp_cnt.ensure((size_t)n_entries))) return rc;
-  if (dev_msgs && (rc = g->d_sp_msg.ensure((size_t)n_msgs))) return rc;
-  if (tokens && (rc = g->d_sp_tok.ensure(nsz * (size_t)width))) return rc;
-  if ((rc = g->sp.mark(2, g->stream))) return rc;
-  if (n_entries > 0 &&
-      (rc = g->k_err(cg_launch_sparse_write(P, sid_lo, ns, g->d_sp_tiles.p, g->d_sp_rows.p, d_off, d_moff,
-                                            g->d_sp_chan.p, g->d_sp_cnt.p, dev_msgs ? g->d_sp_msg.p : nullptr,
-                                            g->stream))))
-    return rc;
-  if (tokens && (rc = g->k_err(cg_launch_sparse_tokens(P, sid_lo, ns, g->d_sp_tok.p, g->stream)))) return rc;
-  if ((rc = g->sp.mark(3, g->stream))) return rc;
-  if (n_entries > 0) {
-    HIP_TRY(hipMemcpyAsync(ent_channel, g->d_sp_chan.p, (size_t)n_entries * sizeof(int32_t), hipMemcpyDeviceToHost,
-                        g->stream));
-    HIP_TRY(hipMemcpyAsync(ent_count, g->d_sp_cnt.p, (size_t)n_entries * sizeof(int32_t), hipMemcpyDeviceToHost,
-                        g->stream));
-  }
-  if (dev_msgs)
-    HIP_TRY(hipMemcpyAsync(msg_tokens, g->d_sp_msg.p, (size_t)n_msgs * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-  if (tokens && width > 0)
-    HIP_TRY(hipMemcpyAsync(tokens, g->d_sp_tok.p, nsz * (size_t)width * sizeof(int32_t), hipMemcpyDeviceToHost,
-                        g->stream));
-  HIP_TRY(hipStreamSynchronize(g->stream));
-  g->sp.done = 2;
-  if (msg_tokens && !dev_msgs) std::fill(msg_tokens, msg_tokens + n_msgs, 1);
-  return CL_OK;
-}
-
-int cl_graph_sparse_time(cl_graph* g, double* ms) {
-  G_CHECK(g);
-  if (!ms) return set_err(CL_E_INVALID, "null output");
-  if (!g->sp.done) return set_err(CL_E_STATE, "no sparse collect has run");
-  double a = 0, b = 0;
-  int rc = g->sp.ms(0, 1, &a);
-  if (!rc && g->sp.done > 1) rc = g->sp.ms(2, 3, &b);
-  *ms = a + b;
-  return rc;
-}
-
 // ---- graph-partitioned mode ---------------------------------------------
-#define G_PART(g)                                                                           \
-  do {                                                                                       \
-    if (!(g)->part) return set_err(CL_E_STATE, "not a partitioned run (cl_graph_part_begin)");  \
-  } while (0)
+#define G_PART(g) \
+  if (!(g)->part) return set_err(CL_E_STATE, "not a partitioned run (cl_graph_part_begin)")
 
 int cl_graph_part_begin(cl_graph* g, int32_t node_lo, int32_t node_hi) {
-  G_CHECK(g);
-  int rc = g->freeze();
-  if (rc) return rc;
+  G_FROZEN(g);
+  int rc;
   if (g->part) return set_err(CL_E_STATE, "the partitioned run has begun");
   if (!g->prog.empty()) return set_err(CL_E_STATE, "a partitioned run starts from an empty program");
   if (g->trace_cap > 0) return set_err(CL_E_STATE, "the event trace is not available in the partitioned mode");
@@ -1751,7 +1462,7 @@ int cl_graph_part_begin(cl_graph* g, int32_t node_lo, int32_t node_hi) {
   g->part_lo = node_lo;
   g->part_hi = node_hi;
   g->fill_params();
-  if ((rc = g->k_err(cg_launch_reset(g->P, g->d_init_tok.p, g->stream)))) return rc;
+  if ((rc = launch_err(cg_launch_reset(g->P, g->d_init_tok.p, g->stream)))) return rc;
   HIP_TRY(hipMemsetAsync(g->d_trigv.p, 0, N * sizeof(int32_t), g->stream));
   HIP_TRY(hipStreamSynchronize(g->stream));
   g->time = 0;
@@ -1762,7 +1473,7 @@ int cl_graph_part_begin(cl_graph* g, int32_t node_lo, int32_t node_hi) {
 }
 
 int cl_graph_part_snapshot(cl_graph* g, int32_t node, int32_t* out_sid) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   G_PART(g);
   if (node < 0 || node >= g->n) return set_err(CL_E_UNKNOWN_NODE, "snapshot at unknown rank %d", node);
   if (g->n_sids >= g->s_cap) return set_err(CL_E_LIMIT, "more than %d snapshots (cl_graph_set_limits)", g->s_cap);
@@ -1773,7 +1484,7 @@ int cl_graph_part_snapshot(cl_graph* g, int32_t node, int32_t* out_sid) {
   HIP_TRY(hipMemcpyAsync(g->d_pop.p, &op, sizeof op, hipMemcpyHostToDevice, g->stream));
   GParams q = g->P;
   q.ops = g->d_pop.p;
-  int rc = g->k_err(cg_launch_hostops(q, (int32_t)g->time, 0, 1, g->stream));
+  int rc = launch_err(cg_launch_hostops(q, (int32_t)g->time, 0, 1, g->stream));
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(g->stream));  // (`op` is a stack copy)
   if (out_sid) *out_sid = g->n_sids;
@@ -1782,13 +1493,11 @@ int cl_graph_part_snapshot(cl_graph* g, int32_t node, int32_t* out_sid) {
 }
 
 int cl_graph_part_pick(cl_graph* g, int32_t* rows, int64_t cap, int64_t* n_rows) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   G_PART(g);
   if (!n_rows || (cap > 0 && !rows)) return set_err(CL_E_INVALID, "null output");
-  if (g->time + 1 > kMaxGraphTime) return set_err(CL_E_LIMIT, "simulated time would exceed %lld ticks", (long long)kMaxGraphTime);
-  ++g->time;
-  int rc = g->k_err(cg_launch_part_pick(g->P, (int32_t)g->time, g->stream));
-  if (rc) return rc;
+  int rc = g->advance_time();
+  if (rc || (rc = launch_err(cg_launch_part_pick(g->P, (int32_t)g->time, g->stream)))) return rc;
   uint32_t cnt[4];
   HIP_TRY(hipMemcpyAsync(cnt, g->d_out_n.p, sizeof cnt, hipMemcpyDeviceToHost, g->stream));
   HIP_TRY(hipStreamSynchronize(g->stream));
@@ -1800,7 +1509,7 @@ int cl_graph_part_pick(cl_graph* g, int32_t* rows, int64_t cap, int64_t* n_rows)
 
 int cl_graph_part_receive(cl_graph* g, const int32_t* rows, int64_t n, int32_t* reports, int64_t cap,
                           int64_t* n_reports) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   G_PART(g);
   if (!n_reports || (n > 0 && !rows) || (cap > 0 && !reports)) return set_err(CL_E_INVALID, "null array");
   if (n < 0 || n > g->n) return set_err(CL_E_INVALID, "%lld incoming deliveries", (long long)n);
@@ -1812,7 +1521,7 @@ int cl_graph_part_receive(cl_graph* g, const int32_t* rows, int64_t n, int32_t* 
       return set_err(CL_E_INVALID, "delivery %lld is not addressed to this device's nodes", (long long)i);
   }
   if (n) HIP_TRY(hipMemcpyAsync(g->d_inbox.p, rows, (size_t)n * sizeof(PDel), hipMemcpyHostToDevice, g->stream));
-  if ((rc = g->k_err(cg_launch_part_receive(g->P, (int32_t)g->time, g->d_inbox.p, (int32_t)n, g->stream)))) return rc;
+  if ((rc = launch_err(cg_launch_part_receive(g->P, (int32_t)g->time, g->d_inbox.p, (int32_t)n, g->stream)))) return rc;
   uint32_t cnt[4];
   HIP_TRY(hipMemcpyAsync(cnt, g->d_out_n.p, sizeof cnt, hipMemcpyDeviceToHost, g->stream));
   HIP_TRY(hipStreamSynchronize(g->stream));
@@ -1823,7 +1532,7 @@ int cl_graph_part_receive(cl_graph* g, const int32_t* rows, int64_t n, int32_t* 
 }
 
 int cl_graph_part_tally(cl_graph* g, int32_t step, const int32_t* reports, int64_t n, int64_t* totals) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   G_PART(g);
   if (!totals || (n > 0 && !reports)) return set_err(CL_E_INVALID, "null array");
   if (n < 0 || n > g->n) return set_err(CL_E_INVALID, "%lld reports", (long long)n);
@@ -1833,10 +1542,9 @@ int cl_graph_part_tally(cl_graph* g, int32_t step, const int32_t* reports, int64
   int rc = g->d_rep_in.ensure((size_t)n);
   if (rc) return rc;
   if (n) HIP_TRY(hipMemcpyAsync(g->d_rep_in.p, reports, (size_t)n * sizeof(int2), hipMemcpyHostToDevice, g->stream));
-  if ((rc = g->k_err(cg_launch_part_tally(g->P, step, g->d_rep_in.p, (int32_t)n, g->stream)))) return rc;
+  if ((rc = launch_err(cg_launch_part_tally(g->P, step, g->d_rep_in.p, (int32_t)n, g->stream)))) return rc;
   GScal sc;
-  HIP_TRY(hipMemcpyAsync(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(hipStreamSynchronize(g->stream));
+  if ((rc = g->read_scal(&sc))) return rc;
   totals[0] = (int64_t)sc.tot_trig;
   totals[1] = (int64_t)sc.tot_send;
   totals[2] = sc.status;
@@ -1844,20 +1552,19 @@ int cl_graph_part_tally(cl_graph* g, int32_t step, const int32_t* reports, int64
 }
 
 int cl_graph_part_freeze(cl_graph* g, int32_t status) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   G_PART(g);
   if (status <= 0) return set_err(CL_E_INVALID, "freeze needs a nonzero status");
   GScal sc;
-  HIP_TRY(hipMemcpyAsync(&sc, g->d_sc.p, sizeof sc, hipMemcpyDeviceToHost, g->stream));
-  HIP_TRY(hipStreamSynchronize(g->stream));
-  if (sc.status) return CL_OK;
+  int rc = g->read_scal(&sc);
+  if (rc || sc.status) return rc;
   HIP_TRY(hipMemcpyAsync(&g->d_sc.p->status, &status, sizeof status, hipMemcpyHostToDevice, g->stream));
   HIP_TRY(hipStreamSynchronize(g->stream));
   return CL_OK;
 }
 
 int cl_graph_part_bases(cl_graph* g, const int64_t* bases, const int32_t* s0, int64_t n, int64_t* draw0) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   G_PART(g);
   if (!bases || (n > 0 && (!s0 || !draw0))) return set_err(CL_E_INVALID, "null array");
   if (n < 0 || n > g->n) return set_err(CL_E_INVALID, "%lld reports", (long long)n);
@@ -1866,7 +1573,7 @@ int cl_graph_part_bases(cl_graph* g, const int64_t* bases, const int32_t* s0, in
   int rc;
   if ((rc = g->d_s0.ensure((size_t)n)) || (rc = g->d_draw0.ensure((size_t)n))) return rc;
   if (n) HIP_TRY(hipMemcpyAsync(g->d_s0.p, s0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
-  if ((rc = g->k_err(cg_launch_part_bases(g->P, bases[0], bases[1], bases[2], bases[3], g->d_s0.p, (int32_t)n,
+  if ((rc = launch_err(cg_launch_part_bases(g->P, bases[0], bases[1], bases[2], bases[3], g->d_s0.p, (int32_t)n,
                                           g->d_draw0.p, g->stream))))
     return rc;
   if (n) HIP_TRY(hipMemcpyAsync(draw0, g->d_draw0.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
@@ -1875,7 +1582,7 @@ int cl_graph_part_bases(cl_graph* g, const int64_t* bases, const int32_t* s0, in
 }
 
 int cl_graph_part_push(cl_graph* g, int32_t step, const int64_t* replies, int64_t n) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   G_PART(g);
   if (n > 0 && !replies) return set_err(CL_E_INVALID, "null array");
   if (n < 0 || n > g->n) return set_err(CL_E_INVALID, "%lld replies", (long long)n);
@@ -1885,14 +1592,14 @@ int cl_graph_part_push(cl_graph* g, int32_t step, const int64_t* replies, int64_
   int rc = g->d_replies.ensure(2 * (size_t)n);
   if (rc) return rc;
   if (n) HIP_TRY(hipMemcpyAsync(g->d_replies.p, replies, 2 * (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
-  if ((rc = g->k_err(cg_launch_part_push(g->P, (int32_t)g->time, step, g->d_replies.p, (int32_t)n, g->stream)))) return rc;
+  if ((rc = launch_err(cg_launch_part_push(g->P, (int32_t)g->time, step, g->d_replies.p, (int32_t)n, g->stream)))) return rc;
   HIP_TRY(hipStreamSynchronize(g->stream));  // (the staged rows must outlive the launch)
   return CL_OK;
 }
 
 // ---- partitioned mode, device-resident exchange (clgraph.h cl_graph_part_dev_*) ----------
 int cl_graph_set_stream(cl_graph* g, void* stream) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   int rc = g->ensure_device();
   if (rc) return rc;
   HIP_TRY(hipSetDevice(g->device));
@@ -1901,16 +1608,14 @@ int cl_graph_set_stream(cl_graph* g, void* stream) {
   return CL_OK;
 }
 
-#define G_DEV(g)                                                                                  \
-  do {                                                                                            \
-    G_CHECK(g);                                                                                   \
-    G_PART(g);                                                                                    \
-    if (!(g)->bk_send) return set_err(CL_E_STATE, "no device exchange buffers (cl_graph_part_dev_bind)"); \
-  } while (0)
+#define G_DEV(g)  \
+  GRAPH_CALL(g);  \
+  G_PART(g);      \
+  if (!(g)->bk_send) return set_err(CL_E_STATE, "no device exchange buffers (cl_graph_part_dev_bind)")
 
 int cl_graph_part_dev_bind(cl_graph* g, int32_t world, int32_t rank, int32_t span, int64_t cap, void* send,
                            void* recv, void* tot_send, void* tot_recv) {
-  G_CHECK(g);
+  GRAPH_CALL(g);
   G_PART(g);
   if (world < 1 || rank < 0 || rank >= world || span <= 0 || span % kGThreads)
     return set_err(CL_E_INVALID, "rank %d of %d, span %d (a positive multiple of %d)", rank, world, span, kGThreads);
@@ -1939,34 +1644,33 @@ int cl_graph_part_dev_bind(cl_graph* g, int32_t world, int32_t rank, int32_t spa
 
 int cl_graph_part_dev_seal(cl_graph* g) {
   G_DEV(g);
-  return g->k_err(cg_launch_part_dev_seal(g->P, g->stream));
+  return launch_err(cg_launch_part_dev_seal(g->P, g->stream));
 }
 
 int cl_graph_part_dev_pick(cl_graph* g) {
   G_DEV(g);
-  if (g->time + 1 > kMaxGraphTime) return set_err(CL_E_LIMIT, "simulated time would exceed %lld ticks", (long long)kMaxGraphTime);
-  ++g->time;
-  return g->k_err(cg_launch_part_dev_pick(g->P, (int32_t)g->time, g->stream));
+  int rc = g->advance_time();
+  return rc ? rc : launch_err(cg_launch_part_dev_pick(g->P, (int32_t)g->time, g->stream));
 }
 
 int cl_graph_part_dev_receive(cl_graph* g) {
   G_DEV(g);
-  return g->k_err(cg_launch_part_dev_receive(g->P, (int32_t)g->time, g->stream));
+  return launch_err(cg_launch_part_dev_receive(g->P, (int32_t)g->time, g->stream));
 }
 
 int cl_graph_part_dev_tally(cl_graph* g, int32_t step) {
   G_DEV(g);
-  return g->k_err(cg_launch_part_dev_tally(g->P, step, g->stream));
+  return launch_err(cg_launch_part_dev_tally(g->P, step, g->stream));
 }
 
 int cl_graph_part_dev_bases(cl_graph* g) {
   G_DEV(g);
-  return g->k_err(cg_launch_part_dev_bases(g->P, g->stream));
+  return launch_err(cg_launch_part_dev_bases(g->P, g->stream));
 }
 
 int cl_graph_part_dev_push(cl_graph* g, int32_t step) {
   G_DEV(g);
-  return g->k_err(cg_launch_part_dev_push(g->P, (int32_t)g->time, step, g->stream));
+  return launch_err(cg_launch_part_dev_push(g->P, (int32_t)g->time, step, g->stream));
 }
 
 }  // extern "C"

@@ -1,0 +1,60 @@
+// cg_host.h -- what the graph readouts (cg_readout.cpp) know of a cl_graph: cg_host.cpp defines the
+// graph and the functions of the first part, cg_readout.cpp the second.  A readout reads a graph
+// through these only; it sees no field of it.
+#pragma once
+#include "../../include/clgraph.h"
+#include "cg_engine.h"
+#include "cl_dev.h"
+
+namespace clsnap {
+
+// ---- of both units ------------------------------------------------------------------------------
+// The opening of an ABI call on a graph: a null handle is refused (no lock: one thread drives a graph).
+#define GRAPH_CALL(g) \
+  if (!(g)) return clsnap::set_err(CL_E_INVALID, "null cl_graph handle")
+
+// The return of a cg_launch_* call as an ABI code.
+inline int launch_err(int e) {
+  return e ? set_err(CL_E_DEVICE, "graph kernel launch failed: %s", hipGetErrorString((hipError_t)e)) : CL_OK;
+}
+
+// The timing events of a call (timing only: no cache writeback per record).
+template <int N>
+using GraphTimer = DevTimer<N, hipEventDisableSystemFence>;
+
+// ---- of cg_host.cpp ---------------------------------------------------------------------------
+// What the argument checks need; no device work behind it (every argument is checked before any).
+struct GraphFacts {
+  int32_t n_sids;
+  bool part;                 // a partitioned run (cl_graph_part_begin)
+  int32_t node_lo, node_hi;  // the owned nodes: all outside the partitioned mode, [0, 0) before the freeze
+};
+GraphFacts graph_facts(const cl_graph* g);
+
+// 0 <= sid_lo <= sid_hi <= the snapshots started so far, or CL_E_INVALID.
+int sid_range_ok(const cl_graph* g, int32_t sid_lo, int32_t sid_hi);
+
+// The engine's state on the device, valid until the next event or setter of the graph.
+struct GraphView {
+  const GParams* P;
+  hipStream_t stream;
+  int32_t n_cus;           // the CU count the grids are sized by
+  const int32_t* d_in_ch;  // [e] channel of every in-position (resident with the topology)
+  int32_t k_lo, k_hi;      // the in-CSR range of the owned nodes
+  int32_t hist;            // payload history slots per channel, 0: every message carries 1 token
+};
+// Executes what is pending, waits for it, and fills *out.
+int graph_view(cl_graph* g, GraphView* out);
+
+// out[sid - sid_lo] = rank of the initiator of sid in [sid_lo, sid_hi) (the program's snapshot events), -1 for none.
+void graph_initiators(const cl_graph* g, int32_t sid_lo, int32_t sid_hi, long long* out);
+
+// ---- of cg_readout.cpp --------------------------------------------------------------------------
+// A graph's readout scratch and timers; the graph makes it with itself and deletes it once its streams are idle.
+struct Readouts;
+Readouts* readouts_new();
+void readouts_delete(Readouts* r);
+Readouts* graph_readouts(const cl_graph* g);  // (defined in cg_host.cpp)
+int64_t readouts_device_bytes(const Readouts* r);
+
+}  // namespace clsnap

@@ -1,4 +1,4 @@
-// cl_dev.h -- what every host unit (cl_host.cpp, cl_analytics.cpp, cg_host.cpp) owns on the
+// cl_dev.h -- what every host unit (cl_host.cpp, cl_analytics.cpp, cg_host.cpp, cg_readout.cpp) owns on the
 // device: the error return of a failed HIP call, a buffer that frees itself, and a set of timing
 // events that destroy themselves.  Nothing here orders the frees against work in flight: an owner
 // synchronises its streams in its destructor's body, and its members go after that.

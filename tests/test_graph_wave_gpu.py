@@ -4,6 +4,7 @@ the CPU oracle's Logger alone (wavecheck.Expected).  Every comparison is exact, 
 has CL_WV_BROKEN == 0 (wavecheck.assert_wave)."""
 import ctypes as C
 import functools
+import os
 
 import numpy as np
 import pytest
@@ -13,6 +14,7 @@ import graphgen as G
 import oracle as O
 import tablecheck as T
 import wavecheck as WC
+from snapcheck import TEST_DATA
 
 pytestmark = pytest.mark.gpu
 
@@ -240,3 +242,24 @@ def test_limits_and_status_on_a_flushed_graph():
     assert ms > 0 and 1 <= rounds <= 32
     t = C.c_double(0)
     assert g._L.cl_graph_wave_time(g._h, C.byref(t), None) == 0 and t.value == ms
+
+
+def test_device_bytes_count_the_wave_alone_of_the_readouts():
+    """The byte count over the engine and its readouts: the table and the sparse collect add
+    nothing to it, the first wave adds its pairs, rows and origins (both sids in one chunk of the
+    default budget), and a graph deleted with every readout buffer alive goes cleanly."""
+    g = clg.GraphSim()
+    g.read_topology_file(os.path.join(TEST_DATA, "3nodes.top"))
+    g.set_delay_go_seed(O.REFERENCE_SEED)
+    n, s = g.num_nodes, 2
+    assert n == 3 and [g.StartSnapshot("N1"), g.StartSnapshot("N3")] == [0, 1]
+    g.drain()
+    assert g.status() == 0
+    before = g.device_bytes
+    assert before > 0
+    assert len(g.snapshot_table()) == s and len(g.collect_sparse(tokens=True)) == s
+    assert g.device_bytes == before
+    w = g.snapshot_wave(0, s, lat_bins=4, depth_bins=2)
+    assert (w.created == n).all()
+    assert HEAD == 12 and g.device_bytes - before == 8 * n * 2 + 8 * 2 * (12 + 4 + 2) + 8 * 2
+    del g
