@@ -1,5 +1,5 @@
 // cg_engine.h -- data layout shared by the graph engine's host runtime (cg_host.cpp)
-// and its gfx950 kernels (cg_kernels.hip, cg_table.hip, cg_sparse.hip, cg_wave.hip).  DESIGN.md §10 draws the same layout.
+// and its gfx950 kernels (cg_kernels.hip, cg_table.hip, cg_sparse.hip, cg_wave.hip, cg_restore.hip).  DESIGN.md §10 draws the same layout.
 //
 // The graph engine runs ONE reference simulation over a large topology (BASELINE
 // configs 4 and 5: 2^20-node regular digraph, 100k-node power-law graph with 4,096
@@ -23,6 +23,33 @@ inline uint64_t cg_hash(uint64_t seed, uint64_t a, uint64_t b) {
   const uint64_t h = mix64(seed ^ (a * 0x9E3779B97F4A7C15ULL));
   return mix64(h ^ (b * 0xD6E8FEB86659FD93ULL));
 }
+
+#if defined(__HIPCC__)
+// Exclusive prefix of v over the threads of a workgroup of WAVES waves (thread order), and the
+// workgroup's total.  lds: WAVES words, free again when the call returns.
+template <int WAVES>
+__device__ __forceinline__ uint64_t cg_block_prefix(uint64_t v, uint64_t* lds, uint64_t& total) {
+  const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint64_t inc = v;
+#pragma unroll
+  for (int32_t o = 1; o < 64; o <<= 1) {
+    const uint64_t u = __shfl_up(inc, o);
+    if (lane >= o) inc += u;
+  }
+  if (lane == 63) lds[wave] = inc;
+  __syncthreads();
+  uint64_t base = 0;
+  total = 0;
+#pragma unroll
+  for (int32_t w = 0; w < WAVES; ++w) {
+    const uint64_t x = lds[w];
+    base += w < wave ? x : 0;
+    total += x;
+  }
+  __syncthreads();
+  return base + inc - v;
+}
+#endif
 
 // FIFO entry (u64): lo32 = payload | kGMarker (token count or snapshot id, common.go:28-31),
 // hi32 = receiveTime (sim.go:101).
@@ -289,6 +316,34 @@ int cg_launch_sparse_write(const GParams& p, int32_t sid_lo, int32_t n_sids, con
                            const ulonglong2* rtot, const long long* row_off, const long long* row_moff,
                            int32_t* ent_channel, int32_t* ent_count, int32_t* msg, void* stream);
 int cg_launch_sparse_tokens(const GParams& p, int32_t sid_lo, int32_t n_sids, int32_t* out, void* stream);
+// Restore (cg_restore.hip).  The seed of a restored graph is the sparse collect of one sid kept
+// on the device: one entry per channel with recorded messages, in channel order -- channel,
+// count and moff, the exclusive prefix of the counts (= the draw index of the entry's first
+// message) -- and the n_msgs payloads back to back (msgs == nullptr: every payload is 1).
+struct GSeed {
+  const int32_t* channel;  // [n_ent]
+  const int32_t* count;    // [n_ent]
+  const long long* moff;   // [n_ent]
+  const int32_t* msgs;     // [n_msgs] or nullptr
+  int64_t n_ent, n_msgs;
+  int64_t max_count;       // the largest count
+};
+// cg_restore_tiles(n_ent) = words of scan scratch `tiles` the offsets need.  restore_offsets:
+// moff = exclusive prefix of count (three passes: tile sums, one workgroup over the tiles, tile
+// prefixes).  restore_reduce adds into out[4] (zeroed by the caller): [0] max count, [1] the
+// payload sum, [2] payloads that differ from 1 (both stay 0 with msgs == nullptr), [3] the sum of tok[n].
+int64_t cg_restore_tiles(int64_t n_ent);
+int cg_launch_restore_offsets(const int32_t* count, int64_t n_ent, long long* moff, unsigned long long* tiles,
+                              void* stream);
+int cg_launch_restore_reduce(const int32_t* count, int64_t n_ent, const int32_t* msgs, int64_t n_msgs,
+                             const int32_t* tok, int64_t n, unsigned long long* out, void* stream);
+// The seed of a run, after cg_launch_reset and before anything else: message j of the seed
+// (entry i, position q = j - moff[i]) goes to ring slot q of its channel with receiveTime
+// receive_time(draw j, time 0); the entry's hq word gets head 0, its count and the receiveTime
+// of position 0; the draw counter and GC_PUSH start at n_msgs.  A count above the ring's slots
+// or (schedule mode) n_msgs above the schedule's length sets the status and queues nothing.
+// No Logger record.  Any grid gives the same result.
+int cg_launch_seed(const GParams& p, const GSeed& s, void* stream);
 // Marker-wave profile and marker tree (cg_wave.hip).  A row is rw = CL_WV_HEAD + lat_bins +
 // depth_bins int64 words (clgraph.h).  wave_init leaves rows[n_rows] of the snapshots sid_lo + r at
 // their identities with the origin set: org[r] is the origin itself (user != 0) or the rank of

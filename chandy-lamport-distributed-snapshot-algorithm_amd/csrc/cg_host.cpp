@@ -143,6 +143,8 @@ struct cl_graph {
   DevBuf<int32_t> d_in_ch;
   int32_t n_cus = 0;
   Readouts* readouts = readouts_new();
+  // the seed of a graph made by cl_graph_restore (cg_host.h), nullptr for every other graph
+  GraphSeed* seed = nullptr;
   size_t ops_uploaded = 0;
   // device event trace (cl_graph_trace_enable)
   int32_t trace_cap = 0;
@@ -174,6 +176,7 @@ struct cl_graph {
       if (own_stream != stream) (void)hipStreamSynchronize(own_stream);
     }
     readouts_delete(readouts);  // (a graph that never reached a device has them too, empty)
+    delete seed;
     if (!dev_ready) return;
     for (auto& ev : ev_pool) {
       (void)hipEventDestroy(ev.first);
@@ -378,18 +381,20 @@ struct cl_graph {
     return CL_OK;
   }
 
+  // (a seeded graph: its seeded messages are delivered and may be recorded like any sent ones)
   int32_t hist_needed() const {
-    if (!nonunit) return 0;
+    if (!nonunit && !(seed && !seed->info.unit_payloads)) return 0;
     int64_t mx = 0;
     for (auto c : ch_sends) mx = std::max<int64_t>(mx, c);
     mx += traffic_steps;
+    if (seed) mx += seed->info.max_ch_msgs;
     int32_t h = 16;
     while (h < mx) h <<= 1;
     return h;
   }
 
   int64_t draws_bound() const {
-    return host_sends + traffic_steps * (int64_t)n + (int64_t)n_sids * e;
+    return (seed ? seed->info.msgs : 0) + host_sends + traffic_steps * (int64_t)n + (int64_t)n_sids * e;
   }
 
   // (Re)allocate the run state when the program outgrew it. Returns 1 in *realloc when
@@ -601,6 +606,17 @@ struct cl_graph {
     return launch_err(cg_launch_drain_end(P, stream));
   }
 
+  // The seed of a restored graph, between the reset and the run's first event.
+  int launch_seed() {
+    const GSeed s{seed->channel.p, seed->count.p, seed->moff.p, seed->info.unit_payloads ? nullptr : seed->msgs.p,
+                  seed->info.channels, seed->info.msgs, seed->info.max_ch_msgs};
+    seed->seed_t.done = 0;
+    int rc = seed->seed_t.mark(0, stream);
+    if (rc || (rc = launch_err(cg_launch_seed(P, s, stream))) || (rc = seed->seed_t.mark(1, stream))) return rc;
+    seed->seed_t.done = 1;
+    return CL_OK;
+  }
+
   // Execute program ops [executed, end) on the device; from scratch if `fresh`.
   int run(bool fresh) {
     if (part) return set_err(CL_E_STATE, "a partitioned run advances only through the cl_graph_part_* calls");
@@ -637,9 +653,10 @@ struct cl_graph {
       gop_cursor = 0;
       time = 0;
       hang = false;
-      if ((rc = launch_err(cg_launch_reset(P, d_init_tok.p, stream)))) return rc;
+      if ((rc = launch_err(cg_launch_reset(P, seed ? seed->init_tok.p : d_init_tok.p, stream)))) return rc;
       // a replay from the initial state restarts the log (an incremental run appends)
       if (trace_cap > 0) HIP_TRY(hipMemsetAsync(d_trace_cnt.p, 0, sizeof(uint32_t), stream));
+      if (seed && (rc = launch_seed())) return rc;  // the recorded cut, before step 0's traffic
       if (traffic_steps > 0 && (rc = launch_err(cg_launch_sends(P, 0, stream)))) return rc;  // step 0 traffic
     }
     state_valid = false;
@@ -747,6 +764,75 @@ void clsnap::graph_initiators(const cl_graph* g, int32_t sid_lo, int32_t sid_hi,
 }
 
 Readouts* clsnap::graph_readouts(const cl_graph* g) { return g->readouts; }
+
+int clsnap::graph_clone_frozen(const cl_graph* g, cl_graph** out) {
+  *out = nullptr;
+  if (!g->frozen || !g->dev_ready) return set_err(CL_E_STATE, "the source graph has not run");
+  cl_graph* r = new cl_graph();
+  struct Guard {
+    cl_graph* r;
+    ~Guard() { delete r; }
+  } guard{r};
+  r->device = g->device;
+  r->ids = g->ids;
+  r->id_index = g->id_index;
+  r->bulk = g->bulk;
+  r->id_width = g->id_width;
+  r->frozen = true;
+  r->n = g->n;
+  r->e = g->e;
+  r->rank_of = g->rank_of;
+  r->by_rank = g->by_rank;
+  r->out_off = g->out_off;
+  r->ch_dst = g->ch_dst;
+  r->ch_src = g->ch_src;
+  r->ch_inpos = g->ch_inpos;
+  r->in_off = g->in_off;
+  r->in_src = g->in_src;
+  r->max_out = g->max_out;
+  r->max_in = g->max_in;
+  r->ch_sends.assign((size_t)g->e, 0);
+  r->cap_log2 = g->cap_log2;
+  r->max_snaps_cfg = g->max_snaps_cfg;
+  r->max_drain = g->max_drain;
+  r->push_lanes = g->push_lanes;
+  r->delay_mode = g->delay_mode;
+  r->delay_seed = g->delay_seed;
+  r->go_seed = g->go_seed;
+  r->go_seed_val = g->go_seed_val;
+  r->user_sched = g->user_sched;
+  r->sched_len = g->delay_mode && !g->go_seed ? -1 : 0;  // (the first run uploads or generates its own)
+  HIP_TRY(hipSetDevice(g->device));
+  HIP_TRY(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+  r->own_stream = r->stream;
+  r->n_cus = g->n_cus;
+  r->dev_ready = true;
+  // the topology's device arrays (g's are idle: its view was taken)
+  int rc = CL_OK;
+  auto copy = [&](auto& dst, const auto& src) {
+    if (rc || (rc = dst.ensure(src.n))) return;
+    const hipError_t e_ = hipMemcpyAsync(dst.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, r->stream);
+    if (e_ != hipSuccess) rc = set_err(CL_E_DEVICE, "topology copy: %s", hipGetErrorString(e_));
+  };
+  copy(r->d_in_ch, g->d_in_ch);
+  copy(r->d_out_off, g->d_out_off);
+  copy(r->d_route, g->d_route);
+  copy(r->d_in_off, g->d_in_off);
+  copy(r->d_in_src, g->d_in_src);
+  copy(r->d_in_oj, g->d_in_oj);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  guard.r = nullptr;
+  *out = r;
+  return CL_OK;
+}
+
+void clsnap::graph_adopt_seed(cl_graph* r, GraphSeed* seed) {
+  r->seed = seed;
+  r->total_tokens = seed->info.node_tokens + seed->info.tokens;
+}
+
+GraphSeed* clsnap::graph_seed(const cl_graph* g) { return g->seed; }
 
 // ---- C ABI ------------------------------------------------------------------------------------
 #define G_TOPO_OPEN(g) \
@@ -1223,7 +1309,7 @@ int cl_graph_device_bytes(cl_graph* g, int64_t* bytes) {
       g->d_lsend.bytes() + g->d_crn.bytes() + g->d_mlist.bytes() + g->d_mcnt.bytes() + g->d_big.bytes() +
       g->d_cpart.bytes() + g->d_cre.bytes() + g->d_bsum.bytes() + g->d_hq.bytes() + g->d_histv.bytes() +
       g->d_fifo.bytes() + g->d_sn.bytes() + g->d_rec.bytes() + g->d_done.bytes() + g->d_ctick.bytes() + g->d_sched.bytes();
-  *bytes = (int64_t)b + readouts_device_bytes(g->readouts);
+  *bytes = (int64_t)b + readouts_device_bytes(g->readouts) + (g->seed ? g->seed->device_bytes() : 0);
   return CL_OK;
 }
 
@@ -1356,7 +1442,13 @@ int cl_graph_trace_read(cl_graph* g, cl_log_event* out, int32_t cap, int32_t* n_
   });
   // LogEvent.nodeTokens (logger.go:71-76): the node's tokens when the record is made --
   // replayed from the initial tokens through the token changes the records carry
+  // (a restored graph's: the seed's plane, which lives on the device alone)
   std::vector<int64_t> tok(g->init_tok.begin(), g->init_tok.end());
+  if (g->seed) {
+    std::vector<int32_t> t0((size_t)g->n);
+    HIP_TRY(hipMemcpy(t0.data(), g->seed->init_tok.p, t0.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    tok.assign(t0.begin(), t0.end());
+  }
   *n_events = (int32_t)have;
   for (uint32_t i = 0; i < have; ++i) {
     const GTraceRec& x = r[i];
@@ -1442,6 +1534,7 @@ int cl_graph_part_begin(cl_graph* g, int32_t node_lo, int32_t node_hi) {
   G_FROZEN(g);
   int rc;
   if (g->part) return set_err(CL_E_STATE, "the partitioned run has begun");
+  if (g->seed) return set_err(CL_E_STATE, "a restored graph does not run partitioned");
   if (!g->prog.empty()) return set_err(CL_E_STATE, "a partitioned run starts from an empty program");
   if (g->trace_cap > 0) return set_err(CL_E_STATE, "the event trace is not available in the partitioned mode");
   if (g->go_seed) return set_err(CL_E_STATE, "the partitioned mode takes the counter hash or an explicit delay schedule");

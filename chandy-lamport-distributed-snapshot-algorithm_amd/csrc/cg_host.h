@@ -1,6 +1,6 @@
-// cg_host.h -- what the graph readouts (cg_readout.cpp) know of a cl_graph: cg_host.cpp defines the
-// graph and the functions of the first part, cg_readout.cpp the second.  A readout reads a graph
-// through these only; it sees no field of it.
+// cg_host.h -- what the graph readouts (cg_readout.cpp) and the restore (cg_restore_host.cpp) know
+// of a cl_graph: cg_host.cpp defines the graph and the functions of the first part, cg_readout.cpp
+// the second.  A readout and the restore read a graph through these only; they see no field of it.
 #pragma once
 #include "../../include/clgraph.h"
 #include "cg_engine.h"
@@ -48,6 +48,30 @@ int graph_view(cl_graph* g, GraphView* out);
 
 // out[sid - sid_lo] = rank of the initiator of sid in [sid_lo, sid_hi) (the program's snapshot events), -1 for none.
 void graph_initiators(const cl_graph* g, int32_t sid_lo, int32_t sid_hi, long long* out);
+
+// The seed of a restored graph (cl_graph_restore, cg_restore_host.cpp builds it; cg_engine.h GSeed
+// draws the layout): the initial token plane, the entries and payloads on the device, what
+// cl_graph_seed_info_of reports, and the timing of the build and of the latest seeding.
+struct GraphSeed {
+  cl_graph_seed_info info{};
+  DevBuf<int32_t> init_tok;        // [n] the recorded node tokens
+  DevBuf<int32_t> channel, count;  // [info.channels]
+  DevBuf<long long> moff;          // [info.channels]
+  DevBuf<int32_t> msgs;            // [info.msgs]; empty with unit payloads
+  double build_ms = 0;
+  GraphTimer<2> seed_t;            // around the seed kernel of the latest run from the initial state
+  int64_t device_bytes() const {
+    return (int64_t)(init_tok.bytes() + channel.bytes() + count.bytes() + moff.bytes() + msgs.bytes());
+  }
+};
+// A new graph on g's device with g's frozen topology (host arrays copied, device arrays copied
+// device to device) and g's limits, push lanes and delay source; no traffic, trace, program or
+// bound stream.  g has run (graph_view succeeded).
+int graph_clone_frozen(const cl_graph* g, cl_graph** out);
+// Hands r its seed (r owns it from here on): r's runs start from it, its initial tokens are the
+// seed's plane and its token total counts the seeded payloads.
+void graph_adopt_seed(cl_graph* r, GraphSeed* seed);
+GraphSeed* graph_seed(const cl_graph* g);  // nullptr: not made by restore
 
 // ---- of cg_readout.cpp --------------------------------------------------------------------------
 // A graph's readout scratch and timers; the graph makes it with itself and deletes it once its streams are idle.

@@ -43,30 +43,6 @@ static_assert(kSparseTile <= (1 << kSparseEntBits) - 1, "a tile's entries must f
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// Exclusive prefix of v over the workgroup's threads (thread order), and the workgroup's total.
-// lds: kSparseWaves words, free again when the call returns.
-__device__ __forceinline__ uint64_t block_prefix(uint64_t v, uint64_t* lds, uint64_t& total) {
-  const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint64_t inc = v;
-#pragma unroll
-  for (int32_t o = 1; o < 64; o <<= 1) {
-    const uint64_t u = __shfl_up(inc, o);
-    if (lane >= o) inc += u;
-  }
-  if (lane == 63) lds[wave] = inc;
-  __syncthreads();
-  uint64_t base = 0;
-  total = 0;
-#pragma unroll
-  for (int32_t w = 0; w < kSparseWaves; ++w) {
-    const uint64_t x = lds[w];
-    base += w < wave ? x : 0;
-    total += x;
-  }
-  __syncthreads();
-  return base + inc - v;
-}
-
 // In-positions of the lane's channels c0 + [0, kSparseItems): -1 for a channel past the end or
 // into a node this device does not own (its cursors belong to another device).
 __device__ __forceinline__ void tile_inpos(const GParams& p, int64_t c0, int32_t (&k)[kSparseItems]) {
@@ -123,7 +99,7 @@ __global__ void __launch_bounds__(kSparseThreads) k_sparse_count(GParams p, int3
       w = tile_cursors(p.rec + (int64_t)sid * p.e, k, b, n);
     }
     uint64_t total;
-    (void)block_prefix(w, lds, total);
+    (void)cg_block_prefix<kSparseWaves>(w, lds, total);
     if (threadIdx.x == 0)
       tb[(int64_t)r * tiles + blockIdx.x] = make_ulonglong2(total & kSparseEntMask, total >> kSparseEntBits);
   }
@@ -140,7 +116,7 @@ __global__ void __launch_bounds__(kSparseThreads) k_sparse_scan_rows(int32_t til
     const int32_t t = t0 + threadIdx.x;
     const ulonglong2 v = t < tiles ? row[t] : make_ulonglong2(0, 0);
     uint64_t te, tm;
-    const uint64_t xe = block_prefix(v.x, lds, te), xm = block_prefix(v.y, lds, tm);
+    const uint64_t xe = cg_block_prefix<kSparseWaves>(v.x, lds, te), xm = cg_block_prefix<kSparseWaves>(v.y, lds, tm);
     if (t < tiles) row[t] = make_ulonglong2(ce + xe, cm + xm);
     ce += te;
     cm += tm;
@@ -161,7 +137,7 @@ __global__ void __launch_bounds__(kSparseThreads) k_sparse_scan_top(const int32_
     const int32_t r = r0 + threadIdx.x;
     const ulonglong2 v = r < n_sids ? rtot[r] : make_ulonglong2(0, 0);
     uint64_t te, tm;
-    const uint64_t xe = block_prefix(v.x, lds, te), xm = block_prefix(v.y, lds, tm);
+    const uint64_t xe = cg_block_prefix<kSparseWaves>(v.x, lds, te), xm = cg_block_prefix<kSparseWaves>(v.y, lds, tm);
     if (r < n_sids) {
       row_off[r] = (long long)(ce + xe);
       row_moff[r] = (long long)(cm + xm);
@@ -199,7 +175,7 @@ __global__ void __launch_bounds__(kSparseThreads) k_sparse_write(GParams p, int3
     uint32_t b[kSparseItems], n[kSparseItems];
     const uint64_t w = tile_cursors(p.rec + (int64_t)sid * p.e, k, b, n);
     uint64_t total;
-    const uint64_t x = block_prefix(w, lds, total);
+    const uint64_t x = cg_block_prefix<kSparseWaves>(w, lds, total);
     int64_t e_at = row_off[r] + (int64_t)me.x + (int64_t)(x & kSparseEntMask);
     int64_t m_at = row_moff[r] + (int64_t)me.y + (int64_t)(x >> kSparseEntBits);
 #pragma unroll

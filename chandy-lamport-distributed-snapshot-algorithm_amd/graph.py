@@ -87,6 +87,9 @@ def glib():
             "cl_graph_snapshot_tree": [vp, i32, i32, vp, vp],
             "cl_graph_collect_sparse": [vp, i32, i32, vp, vp, vp, vp, i64, vp, i64, vp, vp],
             "cl_graph_sparse_time": [vp, vp],
+            "cl_graph_restore": [vp, i32, C.POINTER(C.c_void_p)],
+            "cl_graph_seed_info_of": [vp, vp],
+            "cl_graph_restore_time": [vp, vp, vp],
             "cl_graph_part_begin": [vp, i32, i32],
             "cl_graph_part_snapshot": [vp, i32, vp],
             "cl_graph_part_pick": [vp, vp, i64, vp],
@@ -370,6 +373,11 @@ class MarkerTree:
 SPARSE_INFO_FIELDS = ("n_sids", "n_complete", "n_entries", "n_msgs", "unit_payloads", "node_lo", "node_hi",
                       "reserved")
 SPARSE_INFO_DTYPE = np.dtype([(f, np.int64) for f in SPARSE_INFO_FIELDS])
+
+# cl_graph_seed_info (include/clgraph.h): 8 x int64.
+SEED_INFO_FIELDS = ("source_sid", "channels", "msgs", "tokens", "max_ch_msgs", "unit_payloads", "node_tokens",
+                    "reserved")
+SEED_INFO_DTYPE = np.dtype([(f, np.int64) for f in SEED_INFO_FIELDS])
 
 _U64 = np.uint64
 
@@ -914,6 +922,37 @@ class GraphSim:
     def sparse_time(self):
         """Device ms of the latest collect_sparse call's kernels (HIP events)."""
         return self._get(self._L.cl_graph_sparse_time, C.c_double)
+
+    # ---- restore: a run that begins in a recorded cut (cl_graph_restore) ----------------
+    def restore(self, sid):
+        """A new, independent GraphSim whose time-0 state is the completed snapshot sid of this
+        run: the same topology, node tokens = the snapshot's tokenMap, every channel's queue
+        holding its recorded messages (head first, delay draws in (channel, position) order
+        under the new graph's delay source), built and seeded by kernels on the device.  It
+        inherits the device, limits, push lanes and delay source; traffic, trace and further
+        events are set on it like on any graph.  ClSnapError: E_INVALID for an unknown sid,
+        E_NOT_COMPLETE if it has not completed, E_STATE for a partitioned source or a run that is
+        not OK."""
+        h = C.c_void_p()
+        _check(self._L.cl_graph_restore(self._h, sid, C.byref(h)))
+        r = object.__new__(GraphSim)
+        r._L, r._h, r.device, r._ids = self._L, h, self.device, self._ids
+        return r
+
+    @property
+    def seed_info(self):
+        """The seed of a restored graph as a dict (SEED_INFO_FIELDS); ClSnapError for a graph
+        not made by restore."""
+        info = np.zeros(1, dtype=SEED_INFO_DTYPE)
+        _check(self._L.cl_graph_seed_info_of(self._h, _p(info)))
+        return {f: int(info[0][f]) for f in SEED_INFO_FIELDS if f != "reserved"}
+
+    def restore_time(self):
+        """(device ms of the kernels of the restore call that made this graph, device ms of the
+        seed kernel of its latest run from the initial state -- 0.0 before any)."""
+        build, seed = C.c_double(0), C.c_double(0)
+        _check(self._L.cl_graph_restore_time(self._h, C.byref(build), C.byref(seed)))
+        return build.value, seed.value
 
     # ---- device event trace: the reference's debug Logger (logger.go:12-76) ------------
     def trace_enable(self, capacity=1 << 16):

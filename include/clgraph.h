@@ -297,6 +297,60 @@ int cl_graph_collect_sparse(cl_graph* g, int32_t sid_lo, int32_t sid_hi,
 /* Device ms of the latest sparse collect's kernels (HIP events on the engine's stream). */
 int cl_graph_sparse_time(cl_graph* g, double* ms);
 
+/* ---- restore: a new run that begins in a recorded cut, seeded on the device ---------
+ * g: an unpartitioned graph whose run has status CL_INST_OK; sid: one of its completed
+ * snapshots, with tokenMap T[v] and recorded messages m[c][0..k_c) per channel c in delivery
+ * order (what cl_graph_collect_snapshot(g, sid) returns), M = sum of k_c.  *out is a new,
+ * independent graph r:
+ *   - the same topology (node ids, ranks, channel order), frozen: topology calls return
+ *     CL_E_STATE;
+ *   - initial node tokens T[v];
+ *   - at simulator time 0, before step 0's synthetic traffic and before any host event, channel
+ *     c's queue holds m[c][0..k_c), head first.  Message j of channel c was pushed with delay
+ *     draw index off(c) + j, off = the exclusive prefix of k_c over channel order, and has
+ *     receiveTime = GetReceiveTime(that draw, time 0) under r's delay source;
+ *   - the draw counter and CL_CNT_PUSH start at M (pushes == draws stays true);
+ *   - no Logger record of the seed, no snapshots, no history: snapshot ids start at 0;
+ *   - r owns copies of all it needs: g may be rerun, advanced or destroyed afterwards;
+ *   - cl_graph_rerun(r) resets to the seeded state.
+ * With no synthetic traffic on r, r is indistinguishable -- status, time, node tokens after every
+ * tick, counters, checksums, completion ticks, collected snapshots, table, wave -- from a fresh
+ * graph of the same topology with node tokens T[v] + (payloads recorded on v's out-channels)
+ * whose first host events of step 0 are SendTokens(src(c), dest(c), m[c][j]) in (c, j) order;
+ * only that graph's M SENT_TOKEN Logger records differ.  With traffic the seed still comes first.
+ *
+ * r inherits g's device, fifo_slots, max_snapshots, max_drain_ticks, push lanes and delay source
+ * (hash seed, Go seed or a copy of the schedule); not its traffic, trace or bound stream.  Until
+ * its first flush r takes cl_graph_set_limits, _set_delay_*, _set_traffic, _set_push_lanes and
+ * _trace_enable like any graph; cl_graph_set_device and cl_graph_part_begin return CL_E_STATE.
+ * A seeded channel with more messages than r's fifo_slots gives r's run CL_INST_FIFO_OVERFLOW, a
+ * delay schedule shorter than M gives it CL_INST_DELAY_EXHAUSTED, either from before its first
+ * event (only the status is specified then); exactly fifo_slots messages are fine.
+ *
+ * The seed is built by kernels from g's planes (the sparse collect's scan and write for one sid,
+ * a prefix scan, a reduction) and stays on the device; the topology's device arrays are copied
+ * device to device.  Every run of r from its initial state seeds its queues with one kernel.
+ * Errors (*out = NULL): CL_E_INVALID, before any device work, on a NULL g or out or a sid outside
+ * [0, num_snapshots); CL_E_STATE on a partitioned source or one whose run status is not
+ * CL_INST_OK; CL_E_NOT_COMPLETE if the snapshot has not completed. */
+int cl_graph_restore(cl_graph* g, int32_t sid, cl_graph** out);
+typedef struct cl_graph_seed_info {     /* 8 x int64 = 64 B */
+  int64_t source_sid;      /* the sid restored from */
+  int64_t channels;        /* seeded channels (k_c > 0) */
+  int64_t msgs;            /* M */
+  int64_t tokens;          /* sum of the seeded payloads */
+  int64_t max_ch_msgs;     /* the largest k_c */
+  int64_t unit_payloads;   /* 1: every seeded payload is 1 */
+  int64_t node_tokens;     /* sum of T[v] */
+  int64_t reserved;        /* 0 */
+} cl_graph_seed_info;
+/* The seed of a restored graph; CL_E_STATE for a graph not made by cl_graph_restore. */
+int cl_graph_seed_info_of(cl_graph* r, cl_graph_seed_info* info);
+/* Device ms (HIP events): build_ms of the kernels of the restore call that made r, seed_ms of the
+ * seed kernel of r's latest run from its initial state (0 before any).  CL_E_STATE for a graph
+ * not made by cl_graph_restore.  cl_graph_device_bytes(r) counts the seed's buffers. */
+int cl_graph_restore_time(cl_graph* r, double* build_ms, double* seed_ms);
+
 /* ---- device event trace: the reference's debug Logger (logger.go:12-76) ---------- */
 /* Record up to `capacity` LogEvents from the next run on (0 = off, the default); the next
  * flush replays the program with tracing.  A debugging aid: records go through one device
