@@ -344,6 +344,19 @@ int cg_launch_restore_reduce(const int32_t* count, int64_t n_ent, const int32_t*
 // or (schedule mode) n_msgs above the schedule's length sets the status and queues nothing.
 // No Logger record.  Any grid gives the same result.
 int cg_launch_seed(const GParams& p, const GSeed& s, void* stream);
+// The check of a seed's arrays that came from the host (cg_cut.hip; cl_graph_restore_cut), all on
+// the device: tokens[n], channel / count[n_ent] and msgs[n_msgs] (nullptr: every payload is 1) of
+// a graph of e channels.  *verdict (set to kCutClean by the caller) becomes the least
+// (rule << 56) | index over the elements that break a rule, under any grid:
+constexpr uint32_t kCutRuleTokens = 1;   // tokens[v] >= 0
+constexpr uint32_t kCutRuleChannel = 2;  // 0 <= channel[i] < e, strictly ascending
+constexpr uint32_t kCutRuleCount = 3;    // 1 <= count[i] <= kCutMaxCount
+constexpr uint32_t kCutRulePayload = 4;  // msgs[j] <= kGPayload as unsigned (bit 31 is the marker's)
+constexpr int32_t kCutMaxCount = 32768;  // the largest fifo_slots
+constexpr uint64_t kCutClean = ~0ull;
+int cg_launch_cut_check(const int32_t* tokens, int64_t n, const int32_t* channel, const int32_t* count, int64_t n_ent,
+                        const int32_t* msgs, int64_t n_msgs, int32_t e, unsigned long long* verdict, int32_t n_cus,
+                        void* stream);
 // Marker-wave profile and marker tree (cg_wave.hip).  A row is rw = CL_WV_HEAD + lat_bins +
 // depth_bins int64 words (clgraph.h).  wave_init leaves rows[n_rows] of the snapshots sid_lo + r at
 // their identities with the origin set: org[r] is the origin itself (user != 0) or the rank of

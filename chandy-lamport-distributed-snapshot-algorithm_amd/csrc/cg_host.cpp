@@ -827,6 +827,21 @@ int clsnap::graph_clone_frozen(const cl_graph* g, cl_graph** out) {
   return CL_OK;
 }
 
+int clsnap::graph_topology(cl_graph* g, GraphTopo* out) {
+  const int rc = g->freeze();
+  if (!rc) *out = GraphTopo{g->n, g->e};
+  return rc;
+}
+
+int clsnap::graph_topology_resident(cl_graph* g, hipStream_t* stream, int32_t* n_cus) {
+  const int rc = g->ensure_device();
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(g->device));
+  *stream = g->stream;
+  *n_cus = g->n_cus;
+  return CL_OK;
+}
+
 void clsnap::graph_adopt_seed(cl_graph* r, GraphSeed* seed) {
   r->seed = seed;
   r->total_tokens = seed->info.node_tokens + seed->info.tokens;

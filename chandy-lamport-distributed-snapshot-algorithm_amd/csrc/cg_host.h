@@ -66,8 +66,20 @@ struct GraphSeed {
 };
 // A new graph on g's device with g's frozen topology (host arrays copied, device arrays copied
 // device to device) and g's limits, push lanes and delay source; no traffic, trace, program or
-// bound stream.  g has run (graph_view succeeded).
+// bound stream.  g's topology is resident: g has run (graph_view succeeded), or
+// graph_topology_resident has.
 int graph_clone_frozen(const cl_graph* g, cl_graph** out);
+// The topology of a graph that serves as a template only (cl_graph_restore_cut): it need never
+// have had an event.  graph_topology freezes it like any call that needs rank order, on the
+// host alone; graph_topology_resident makes g's device current, uploads the topology's arrays if
+// they are not there yet, allocates none of g's run planes, and returns the stream to build on
+// and the CU count.
+struct GraphTopo {
+  int32_t n;  // nodes
+  int64_t e;  // channels
+};
+int graph_topology(cl_graph* g, GraphTopo* out);
+int graph_topology_resident(cl_graph* g, hipStream_t* stream, int32_t* n_cus);
 // Hands r its seed (r owns it from here on): r's runs start from it, its initial tokens are the
 // seed's plane and its token total counts the seeded payloads.
 void graph_adopt_seed(cl_graph* r, GraphSeed* seed);

@@ -9,6 +9,8 @@ reference's own test_data scenarios as well.  There is no CPU fallback: without 
 HIP library or a gfx950 GPU, calls that need them raise ``ClSnapError``.
 """
 import ctypes as C
+import hashlib
+import os
 
 import numpy as np
 
@@ -22,6 +24,14 @@ SNAP_ROW_FIELDS = ("sid", "initiator", "start_tick", "complete_tick", "nodes_cre
                    "node_tokens", "min_node_tokens", "max_node_tokens", "rec_msgs", "rec_tokens", "rec_channels",
                    "max_ch_msgs", "digest")
 SNAP_ROW_DTYPE = np.dtype([(f, np.int64) for f in SNAP_ROW_FIELDS] + [("reserved", np.int64, (2,))])
+
+
+class GraphCut(C.Structure):
+    """cl_graph_cut (include/clgraph.h): 64 bytes."""
+    _fields_ = [("source_sid", C.c_int64), ("n_nodes", C.c_int64), ("tokens", C.POINTER(C.c_int32)),
+                ("n_entries", C.c_int64), ("channel", C.POINTER(C.c_int32)), ("count", C.POINTER(C.c_int32)),
+                ("n_msgs", C.c_int64), ("msg_tokens", C.POINTER(C.c_int32))]
+
 
 _SIGS = None
 
@@ -90,6 +100,7 @@ def glib():
             "cl_graph_restore": [vp, i32, C.POINTER(C.c_void_p)],
             "cl_graph_seed_info_of": [vp, vp],
             "cl_graph_restore_time": [vp, vp, vp],
+            "cl_graph_restore_cut": [vp, C.POINTER(GraphCut), C.POINTER(C.c_void_p)],
             "cl_graph_part_begin": [vp, i32, i32],
             "cl_graph_part_snapshot": [vp, i32, vp],
             "cl_graph_part_pick": [vp, vp, i64, vp],
@@ -539,6 +550,30 @@ class SparseSnapshots:
         msgs = [MsgSnapshot(ids[src[ch[i]]], ids[dst[ch[i]]], int(t)) for i in order for t in pay[i]]
         return GlobalSnapshot(sid, dict(zip(ids, self.tokens[r].tolist())), msgs)
 
+    def cut(self, sid, sim=None, topology=False):
+        """Snapshot sid as a SnapshotCut: what GraphSim.restore_cut takes and SnapshotCut.save
+        writes.  Needs the token plane of all nodes and the payloads (ValueError otherwise, like
+        snapshot), so the merged result of PartitionedGraphSim.collect_sparse(tokens=True) serves;
+        ClSnapError(E_NOT_COMPLETE) if sid has not completed.  sim (any GraphSim of the topology,
+        a fresh template included) supplies n_channels and the topology key, and with
+        topology=True the channel list and node ids that GraphSim.from_cut needs."""
+        r = self._need_complete(sid)
+        if self.tokens is None or self.node_lo != 0 or (sim is not None and self.node_hi != sim.num_nodes):
+            raise ValueError("cut needs the token plane of every node (collect_sparse(tokens=True))")
+        if self.msg_tokens is None:
+            raise ValueError("cut needs the payloads (collect_sparse(payloads=True))")
+        if topology and sim is None:
+            raise ValueError("cut needs a sim to take the topology from")
+        a, b = int(self.row_offsets[r]), int(self.row_offsets[r + 1])
+        msg = self.msg_tokens[self.msg_offsets[a]:self.msg_offsets[b]]
+        src = dst = ids = None
+        if topology:
+            src, dst = sim.channels()
+            ids = _ids_array(sim)
+        return SnapshotCut(sid, self.tokens[r], self.channel[a:b], self.count[a:b], msg,
+                           n_channels=None if sim is None else sim.num_channels,
+                           topology_key=None if sim is None else sim.topology_key(), src=src, dst=dst, ids=ids)
+
     @staticmethod
     def merge(parts):
         """The SparseSnapshots of a partitioned run from its parts' (the same sids; disjoint
@@ -590,11 +625,169 @@ class SparseSnapshots:
                                parts[0].node_lo, parts[-1].node_hi)
 
 
+def _ids_array(sim):
+    """sim.node_ids() as a numpy S array (kept on the sim: the ids of a graph never change)."""
+    a = getattr(sim, "_ids_s", None)
+    if a is None:
+        a = np.array([i.encode() for i in sim.node_ids()], dtype="S")
+        try:
+            sim._ids_s = a
+        except AttributeError:
+            pass
+    return a
+
+
+def _bulk_id_width(ids):
+    """w if the S array ids is exactly "N" + the rank zero-padded to one width w (what
+    set_topology(id_width=w) names its nodes), else 0."""
+    w = ids.dtype.itemsize - 1
+    n = ids.size
+    if not 1 <= w <= 10 or n == 0 or len(str(n - 1)) > w:
+        return 0
+    b = np.ascontiguousarray(ids).view(np.uint8).reshape(n, w + 1)
+    digits = b[:, 1:].astype(np.int64) - 48
+    if (b[:, 0] != ord("N")).any() or (digits < 0).any() or (digits > 9).any():
+        return 0
+    value = digits @ (10 ** np.arange(w - 1, -1, -1, dtype=np.int64))
+    return w if np.array_equal(value, np.arange(n, dtype=np.int64)) else 0
+
+
+def topology_key(n, src, dst):
+    """A 64-bit key of a topology in rank order: the 8-byte blake2b digest, read as a
+    little-endian unsigned int, of int64 N, int64 E and the int32 bytes of the channel list
+    (src, then dst) as GraphSim.channels returns it.  A pure host function."""
+    s = np.ascontiguousarray(src, dtype="<i4").reshape(-1)
+    d = np.ascontiguousarray(dst, dtype="<i4").reshape(-1)
+    if s.size != d.size:
+        raise ValueError("src and dst differ in length")
+    h = hashlib.blake2b(digest_size=8)
+    h.update(np.array([n, s.size], dtype="<i8").tobytes())
+    h.update(s.tobytes())
+    h.update(d.tobytes())
+    return int.from_bytes(h.digest(), "little")
+
+
+class SnapshotCut:
+    """One recorded cut held on the host: what a completed snapshot contains, in the layout
+    GraphSim.restore_cut (cl_graph_restore_cut) takes and save / load keep in a file.
+
+      source_sid      the snapshot id it came from (reported back by seed_info, not interpreted)
+      tokens          int32[N] the tokenMap, rank order
+      channel, count  int32 per entry: the channels with recorded messages (index into
+                      GraphSim.channels(), strictly ascending) and how many each holds
+      msg_tokens      int32 payloads in entry order, delivery order within; None: all ones
+      n_channels      E of the topology it belongs to, topology_key its key (topology_key());
+                      None when unknown -- restore_cut refuses such a cut
+      src, dst, ids   optionally the topology itself: the channel list and the node ids in rank
+                      order (numpy S array), all three or none; GraphSim.from_cut needs them
+
+    The constructor checks only that the lengths agree (ValueError); the contents are checked on
+    the device by restore_cut."""
+
+    _ARRAYS = ("tokens", "channel", "count", "msg_tokens", "src", "dst", "ids")
+
+    def __init__(self, source_sid, tokens, channel, count, msg_tokens=None, n_channels=None, topology_key=None,
+                 src=None, dst=None, ids=None):
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)  # noqa: E731
+        self.source_sid = int(source_sid)
+        self.tokens, self.channel, self.count = i32(tokens), i32(channel), i32(count)
+        self.msg_tokens = None if msg_tokens is None else i32(msg_tokens)
+        self.n_channels = None if n_channels is None else int(n_channels)
+        self.topology_key = None if topology_key is None else int(topology_key)
+        if self.channel.size != self.count.size:
+            raise ValueError("channel and count differ in length")
+        if self.msg_tokens is not None and self.msg_tokens.size != self.msgs:
+            raise ValueError("msg_tokens does not hold the entries' messages")
+        if self.n_channels is not None and not 0 <= self.channel.size <= self.n_channels:
+            raise ValueError("more entries than channels")
+        if len({src is None, dst is None, ids is None}) != 1:
+            raise ValueError("src, dst and ids come together or not at all")
+        self.src = self.dst = self.ids = None
+        if src is not None:
+            self.src, self.dst = i32(src), i32(dst)
+            self.ids = np.ascontiguousarray(ids).reshape(-1)
+            if self.ids.dtype.kind != "S":
+                self.ids = np.array([str(i).encode() for i in self.ids.tolist()], dtype="S")
+            if self.src.size != self.dst.size or (self.n_channels is not None and self.src.size != self.n_channels):
+                raise ValueError("src and dst do not list n_channels channels")
+            if self.ids.size != self.tokens.size:
+                raise ValueError("ids and tokens differ in length")
+
+    @property
+    def msgs(self):
+        return int(self.count.sum(dtype=np.int64))
+
+    @property
+    def channels(self):
+        return int(self.channel.size)
+
+    @property
+    def payload_tokens(self):
+        return self.msgs if self.msg_tokens is None else int(self.msg_tokens.sum(dtype=np.int64))
+
+    @property
+    def has_topology(self):
+        return self.src is not None
+
+    def info(self):
+        """What seed_info of a graph restored from this cut must report."""
+        return {"source_sid": self.source_sid, "channels": self.channels, "msgs": self.msgs,
+                "tokens": self.payload_tokens, "max_ch_msgs": int(self.count.max()) if self.count.size else 0,
+                "unit_payloads": int(self.msg_tokens is None or bool((self.msg_tokens == 1).all())),
+                "node_tokens": int(self.tokens.sum(dtype=np.int64))}
+
+    def dense(self):
+        """(tokens, offsets[n_channels + 1], messages) as int64, like GraphSim.collect_arrays."""
+        if self.n_channels is None:
+            raise ValueError("dense needs n_channels")
+        cnt = np.zeros(self.n_channels, dtype=np.int64)
+        cnt[self.channel] = self.count
+        off = np.zeros(self.n_channels + 1, dtype=np.int64)
+        np.cumsum(cnt, out=off[1:])
+        msg = np.ones(self.msgs, dtype=np.int64) if self.msg_tokens is None else self.msg_tokens.astype(np.int64)
+        return self.tokens.astype(np.int64), off, msg
+
+    def __eq__(self, other):
+        if not isinstance(other, SnapshotCut):
+            return NotImplemented
+        same = lambda a, b: (a is None) == (b is None) and (a is None or np.array_equal(a, b))  # noqa: E731
+        return (self.source_sid, self.n_channels, self.topology_key) == \
+            (other.source_sid, other.n_channels, other.topology_key) and \
+            all(same(getattr(self, f), getattr(other, f)) for f in self._ARRAYS)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return (f"SnapshotCut(sid {self.source_sid}, {self.tokens.size} nodes, {self.channels} entries, "
+                f"{self.msgs} messages{', with topology' if self.has_topology else ''})")
+
+    def save(self, path):
+        """Writes the cut to path with numpy.savez (an .npz of plain arrays, no pickle)."""
+        d = {f: getattr(self, f) for f in self._ARRAYS if getattr(self, f) is not None}
+        d["source_sid"] = np.array(self.source_sid, dtype=np.int64)
+        if self.n_channels is not None:
+            d["n_channels"] = np.array(self.n_channels, dtype=np.int64)
+        if self.topology_key is not None:
+            d["topology_key"] = np.array(self.topology_key, dtype=np.uint64)
+        with open(path, "wb") as f:
+            np.savez(f, **d)
+
+    @staticmethod
+    def load(path):
+        """The cut save wrote to path (numpy.load, allow_pickle=False)."""
+        with np.load(path, allow_pickle=False) as z:
+            get = lambda f: z[f] if f in z.files else None  # noqa: E731
+            scalar = lambda f: None if f not in z.files else int(z[f])  # noqa: E731
+            return SnapshotCut(int(z["source_sid"]), z["tokens"], z["channel"], z["count"], get("msg_tokens"),
+                               scalar("n_channels"), scalar("topology_key"), get("src"), get("dst"), get("ids"))
+
+
 class GraphSim:
     """One reference simulator (sim.go ChandyLamportSim) on the GPU, state in HBM."""
 
     def __init__(self, device=0, fifo_slots=16, max_snapshots=0, max_drain_ticks=10000):
         self._L = glib()
+        self._pid = os.getpid()
         h = C.c_void_p()
         _check(self._L.cl_graph_create(C.byref(h)))
         self._h = h
@@ -603,11 +796,22 @@ class GraphSim:
         _check(self._L.cl_graph_set_limits(self._h, fifo_slots, max_snapshots, max_drain_ticks))
         self._ids = None
 
+    @classmethod
+    def _of_handle(cls, L, h, device, ids=None):
+        """The GraphSim that owns the native graph h (made by a restore call)."""
+        r = object.__new__(cls)
+        r._L, r._h, r.device, r._ids, r._pid = L, h, device, ids, os.getpid()
+        return r
+
     def __del__(self):
+        # Only the process that made the graph destroys it.  A forked child (a multiprocessing
+        # manager, a worker pool) holds copies of its parent's objects, and its garbage collector
+        # may finalise them; the native graph's streams and buffers are the parent's, and a HIP
+        # call on them from the child crashes it.
         h = getattr(self, "_h", None)
-        if h:
+        if h and getattr(self, "_pid", None) == os.getpid():
             self._L.cl_graph_destroy(h)
-            self._h = None
+        self._h = None
 
     # ---- topology -----------------------------------------------------------------
     def AddNode(self, node_id, tokens):             # sim.go:40
@@ -750,6 +954,11 @@ class GraphSim:
         d = np.zeros(e, dtype=np.int32)
         _check(self._L.cl_graph_channels(self._h, _p(s), _p(d)))
         return s, d
+
+    def _node_id(self, rank, cap):
+        buf = C.create_string_buffer(cap)
+        _check(self._L.cl_graph_node_id(self._h, rank, buf, cap))
+        return buf.value.decode()
 
     def node_ids(self):
         if self._ids is None:
@@ -932,12 +1141,74 @@ class GraphSim:
         inherits the device, limits, push lanes and delay source; traffic, trace and further
         events are set on it like on any graph.  ClSnapError: E_INVALID for an unknown sid,
         E_NOT_COMPLETE if it has not completed, E_STATE for a partitioned source or a run that is
-        not OK."""
+        not OK.  A partitioned run is restored from through its merged cut:
+        PartitionedGraphSim.collect_sparse(tokens=True), SparseSnapshots.cut, restore_cut."""
         h = C.c_void_p()
         _check(self._L.cl_graph_restore(self._h, sid, C.byref(h)))
-        r = object.__new__(GraphSim)
-        r._L, r._h, r.device, r._ids = self._L, h, self.device, self._ids
-        return r
+        return GraphSim._of_handle(self._L, h, self.device, self._ids)
+
+    def topology_key(self):
+        """topology_key of this graph's own topology (freezes it like any call that needs rank
+        order; host only)."""
+        if getattr(self, "_key", None) is None:
+            self._key = topology_key(self.num_nodes, *self.channels())
+        return self._key
+
+    def cut(self, sid, topology=False):
+        """The completed snapshot sid as a SnapshotCut on the host (collect_sparse of the one
+        sid with tokens and payloads); with topology=True it carries the channel list and the
+        node ids, which SnapshotCut.save then keeps and from_cut needs.
+        ClSnapError(E_NOT_COMPLETE) if the snapshot has not completed."""
+        return self.collect_sparse(sid, sid + 1, tokens=True).cut(sid, sim=self, topology=topology)
+
+    def restore_cut(self, cut):
+        """restore from a cut held on the host (cl_graph_restore_cut): a saved one, the merged
+        cut of a partitioned run, or one written by hand.  This graph is the template: it
+        supplies the topology, device, limits, push lanes and delay source, need never have run,
+        is not changed, and may be destroyed afterwards.  ValueError if the cut's topology key
+        or channel count is not this topology's; the arrays are then uploaded and checked by a
+        kernel, and ClSnapError(E_INVALID) names the first element that breaks a rule
+        (include/clgraph.h).  The result is a graph as restore returns it."""
+        if not isinstance(cut, SnapshotCut):
+            raise TypeError("restore_cut takes a SnapshotCut")
+        if cut.n_channels != self.num_channels or cut.topology_key != self.topology_key():
+            raise ValueError("the cut belongs to another topology (n_channels or topology_key differ)")
+        ip = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        rec = GraphCut(cut.source_sid, cut.tokens.size, ip(cut.tokens), cut.channel.size, ip(cut.channel),
+                       ip(cut.count), cut.msgs if cut.msg_tokens is None else cut.msg_tokens.size, ip(cut.msg_tokens))
+        h = C.c_void_p()
+        _check(self._L.cl_graph_restore_cut(self._h, C.byref(rec), C.byref(h)))
+        return GraphSim._of_handle(self._L, h, self.device, self._ids)
+
+    @classmethod
+    def from_cut(cls, cut, device=0, fifo_slots=16, max_snapshots=0, max_drain_ticks=10000):
+        """A graph restored from a cut that carries its topology (GraphSim.cut(sid,
+        topology=True), SnapshotCut.load): what a fresh process starts from.  The template is
+        built from the saved channel list and ids -- in bulk (set_topology) when the ids are "N" +
+        the rank zero-padded to one width, else node by node -- and must come out in the saved
+        rank order (ValueError otherwise).  Set the delay source on the result before its first flush, as on
+        any restored graph."""
+        if not cut.has_topology:
+            raise ValueError("from_cut needs a cut saved with topology=True")
+        n = cut.tokens.size
+        t = cls(device, fifo_slots, max_snapshots, max_drain_ticks)
+        w = _bulk_id_width(cut.ids)
+        if w:
+            t.set_topology(cut.tokens, cut.src, cut.dst, id_width=w)
+            # (set_topology names rank r "N" + r padded to w: the saved ids, as just checked; the
+            # ends are read back, the rest are the engine's by the same rule)
+            same = t.num_nodes == n and all(t._get(t._L.cl_graph_node_id_length, C.c_int32, r) == w + 1 and
+                                            t._node_id(r, w + 2) == cut.ids[r].decode() for r in (0, n - 1))
+        else:
+            ids = [i.decode() for i in cut.ids.tolist()]
+            for v in range(n):
+                t.AddNode(ids[v], int(cut.tokens[v]))
+            for a, b in zip(cut.src.tolist(), cut.dst.tolist()):
+                t.AddLink(ids[a], ids[b])
+            same = n > 0 and t.node_ids() == ids
+        if not same:
+            raise ValueError("the saved node ids are not in rank order")
+        return t.restore_cut(cut)
 
     @property
     def seed_info(self):

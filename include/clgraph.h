@@ -332,7 +332,9 @@ int cl_graph_sparse_time(cl_graph* g, double* ms);
  * device to device.  Every run of r from its initial state seeds its queues with one kernel.
  * Errors (*out = NULL): CL_E_INVALID, before any device work, on a NULL g or out or a sid outside
  * [0, num_snapshots); CL_E_STATE on a partitioned source or one whose run status is not
- * CL_INST_OK; CL_E_NOT_COMPLETE if the snapshot has not completed. */
+ * CL_INST_OK; CL_E_NOT_COMPLETE if the snapshot has not completed.  A partitioned run is
+ * restored from through its merged cut: cl_graph_collect_sparse with tokens on every part,
+ * merged by channel, into cl_graph_restore_cut below. */
 int cl_graph_restore(cl_graph* g, int32_t sid, cl_graph** out);
 typedef struct cl_graph_seed_info {     /* 8 x int64 = 64 B */
   int64_t source_sid;      /* the sid restored from */
@@ -350,6 +352,49 @@ int cl_graph_seed_info_of(cl_graph* r, cl_graph_seed_info* info);
  * seed kernel of r's latest run from its initial state (0 before any).  CL_E_STATE for a graph
  * not made by cl_graph_restore.  cl_graph_device_bytes(r) counts the seed's buffers. */
 int cl_graph_restore_time(cl_graph* r, double* build_ms, double* seed_ms);
+
+/* ---- restore from a cut held on the host: saved, merged from a partitioned run, or hand-made ----
+ * The cut takes the place of the snapshot's contents in cl_graph_restore: T = tokens, and the
+ * recorded messages as the sparse collect lays them out -- one entry (channel, count) per channel
+ * with messages, in channel order, the payloads back to back in entry order and delivery order
+ * within an entry.  *out is a graph exactly as cl_graph_restore specifies it, with `topo` in the
+ * place of g for all that is inherited (topology, device, fifo_slots, max_snapshots,
+ * max_drain_ticks, push lanes, delay source; not traffic, trace, program or bound stream), and
+ * cl_graph_seed_info_of, cl_graph_restore_time (build_ms: the check, offsets and sums kernels, the
+ * uploads excluded), cl_graph_rerun and cl_graph_device_bytes work on it unchanged.
+ *
+ * topo needs only a topology: it may never have had an event or a flush, and may equally have
+ * run.  The call freezes its topology like any call that needs rank order and uploads the
+ * topology's arrays if they are not resident; it allocates none of topo's run state and changes
+ * nothing else of it.  topo may be destroyed afterwards and serves any number of cuts.
+ *
+ * The arrays are uploaded and checked by a kernel before anything uses them; a graph is made
+ * only from a cut that passed:
+ *   (a) tokens[v] >= 0;
+ *   (b) 0 <= channel[i] < E and channel[i-1] < channel[i];
+ *   (c) 1 <= count[i] <= 32768 (the largest fifo_slots);
+ *   (d) 0 <= msg_tokens[j] <= 0x7fffffff (bit 31 of a queued word marks a marker);
+ *   (e) sum(count) == n_msgs.
+ * A breach returns CL_E_INVALID with cl_last_error() naming the element as <field>[<index>] and
+ * its value ((e): n_msgs and the sum); of several, the lowest rule in this order, then the lowest
+ * index.  A count above r's fifo_slots but at most 32768 is valid and gives r's run
+ * CL_INST_FIFO_OVERFLOW, a short schedule CL_INST_DELAY_EXHAUSTED, as in cl_graph_restore.
+ * unit_payloads is 1 when msg_tokens is NULL or every payload is 1.
+ * Errors answered before any device work (*out = NULL in every case): CL_E_INVALID on a NULL topo,
+ * cut or out, a negative length, a NULL array with a positive length (msg_tokens excepted),
+ * n_nodes != N, n_entries > E, n_msgs < n_entries or n_msgs > n_entries * 32768; CL_E_STATE on a
+ * topo with no nodes or a partitioned one. */
+typedef struct cl_graph_cut {       /* 64 B */
+  int64_t source_sid;               /* reported back in cl_graph_seed_info.source_sid, not interpreted */
+  int64_t n_nodes;
+  const int32_t* tokens;            /* [n_nodes]   the tokenMap T */
+  int64_t n_entries;
+  const int32_t* channel;           /* [n_entries] channel index (cl_graph_channels), strictly ascending */
+  const int32_t* count;             /* [n_entries] recorded messages, >= 1 */
+  int64_t n_msgs;                   /* == sum of count */
+  const int32_t* msg_tokens;        /* [n_msgs] payloads in entry order, delivery order within; NULL: all 1 */
+} cl_graph_cut;
+int cl_graph_restore_cut(cl_graph* topo, const cl_graph_cut* cut, cl_graph** out);
 
 /* ---- device event trace: the reference's debug Logger (logger.go:12-76) ---------- */
 /* Record up to `capacity` LogEvents from the next run on (0 = off, the default); the next
