@@ -344,6 +344,16 @@ int cg_launch_restore_reduce(const int32_t* count, int64_t n_ent, const int32_t*
 // or (schedule mode) n_msgs above the schedule's length sets the status and queues nothing.
 // No Logger record.  Any grid gives the same result.
 int cg_launch_seed(const GParams& p, const GSeed& s, void* stream);
+// The same for one device of a partitioned run (p.part_lo, p.part_hi), in the place of cg_launch_seed.
+// seed_share writes share[4] = e_lo, e_hi, m_lo, m_hi: the entries whose channel is one of the owned
+// nodes' out-channels [out_off[part_lo], out_off[part_hi]) -- a contiguous slice, the channels being
+// ascending -- and their messages [moff[e_lo], moff[e_hi]) (moff[n_ent] = n_msgs).  seed_range reads
+// the share from the device and queues those messages alone, each with its draw index among all
+// n_msgs, so an owned channel gets the words cg_launch_seed writes for it; the draw counter starts
+// at n_msgs on every device, GC_PUSH at m_hi - m_lo.  What cannot be seeded is judged on the whole
+// seed as above, the same on every device.
+int cg_launch_seed_share(const GParams& p, const GSeed& s, long long* share, void* stream);
+int cg_launch_seed_range(const GParams& p, const GSeed& s, const long long* share, void* stream);
 // The check of a seed's arrays that came from the host (cg_cut.hip; cl_graph_restore_cut), all on
 // the device: tokens[n], channel / count[n_ent] and msgs[n_msgs] (nullptr: every payload is 1) of
 // a graph of e channels.  *verdict (set to kCutClean by the caller) becomes the least

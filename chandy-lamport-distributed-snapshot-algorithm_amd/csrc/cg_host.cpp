@@ -607,12 +607,17 @@ struct cl_graph {
   }
 
   // The seed of a restored graph, between the reset and the run's first event.
-  int launch_seed() {
+  // (share: the partitioned run's -- this device's slice alone, found by a kernel before it)
+  int launch_seed(bool share = false) {
     const GSeed s{seed->channel.p, seed->count.p, seed->moff.p, seed->info.unit_payloads ? nullptr : seed->msgs.p,
                   seed->info.channels, seed->info.msgs, seed->info.max_ch_msgs};
     seed->seed_t.done = 0;
-    int rc = seed->seed_t.mark(0, stream);
-    if (rc || (rc = launch_err(cg_launch_seed(P, s, stream))) || (rc = seed->seed_t.mark(1, stream))) return rc;
+    int rc;
+    if (share && (rc = launch_err(cg_launch_seed_share(P, s, seed->d_share.p, stream)))) return rc;
+    if ((rc = seed->seed_t.mark(0, stream))) return rc;
+    if ((rc = launch_err(share ? cg_launch_seed_range(P, s, seed->d_share.p, stream) : cg_launch_seed(P, s, stream))) ||
+        (rc = seed->seed_t.mark(1, stream)))
+      return rc;
     seed->seed_t.done = 1;
     return CL_OK;
   }
@@ -1545,11 +1550,13 @@ int cl_graph_get_checksums(cl_graph* g, int64_t* out) {
 #define G_PART(g) \
   if (!(g)->part) return set_err(CL_E_STATE, "not a partitioned run (cl_graph_part_begin)")
 
-int cl_graph_part_begin(cl_graph* g, int32_t node_lo, int32_t node_hi) {
-  G_FROZEN(g);
+// The body of cl_graph_part_begin and cl_graph_part_begin_seeded (the caller has frozen the
+// topology and decided which of the two the graph takes): the refusals, the mode's buffers, the
+// reset -- from the seed's token plane and followed by this device's share of the seed when
+// `seeded` -- and one synchronisation, which also brings the share's four words back.
+static int part_begin(cl_graph* g, int32_t node_lo, int32_t node_hi, bool seeded) {
   int rc;
   if (g->part) return set_err(CL_E_STATE, "the partitioned run has begun");
-  if (g->seed) return set_err(CL_E_STATE, "a restored graph does not run partitioned");
   if (!g->prog.empty()) return set_err(CL_E_STATE, "a partitioned run starts from an empty program");
   if (g->trace_cap > 0) return set_err(CL_E_STATE, "the event trace is not available in the partitioned mode");
   if (g->go_seed) return set_err(CL_E_STATE, "the partitioned mode takes the counter hash or an explicit delay schedule");
@@ -1566,17 +1573,49 @@ int cl_graph_part_begin(cl_graph* g, int32_t node_lo, int32_t node_hi) {
       (rc = g->d_reports.ensure(N)) || (rc = g->d_trigv.ensure(N)) || (rc = g->d_rdraw.ensure(N)) ||
       (rc = g->d_pop.ensure(1)))
     return rc;
+  if (seeded && (rc = g->seed->d_share.ensure(4))) return rc;
   g->part = true;
   g->part_lo = node_lo;
   g->part_hi = node_hi;
   g->fill_params();
-  if ((rc = launch_err(cg_launch_reset(g->P, g->d_init_tok.p, g->stream)))) return rc;
+  if ((rc = launch_err(cg_launch_reset(g->P, seeded ? g->seed->init_tok.p : g->d_init_tok.p, g->stream)))) return rc;
+  long long share[4] = {0, 0, 0, 0};
+  if (seeded) {  // the recorded cut, before anything else: the owned channels' messages alone
+    if ((rc = g->launch_seed(true))) return rc;
+    HIP_TRY(hipMemcpyAsync(share, g->seed->d_share.p, sizeof share, hipMemcpyDeviceToHost, g->stream));
+  }
   HIP_TRY(hipMemsetAsync(g->d_trigv.p, 0, N * sizeof(int32_t), g->stream));
   HIP_TRY(hipStreamSynchronize(g->stream));
+  if (seeded) {
+    for (int i = 0; i < 4; ++i) g->seed->share[i] = share[i];
+    g->seed->shared = true;
+  }
   g->time = 0;
   g->hang = false;
   g->executed = g->prog.size();
   g->state_valid = true;
+  return CL_OK;
+}
+
+int cl_graph_part_begin(cl_graph* g, int32_t node_lo, int32_t node_hi) {
+  G_FROZEN(g);
+  if (g->seed)
+    return set_err(CL_E_STATE, "a restored graph does not run partitioned from here (cl_graph_part_begin_seeded)");
+  return part_begin(g, node_lo, node_hi, false);
+}
+
+int cl_graph_part_begin_seeded(cl_graph* r, int32_t node_lo, int32_t node_hi) {
+  G_FROZEN(r);
+  if (!r->seed) return set_err(CL_E_STATE, "not a restored graph (cl_graph_restore, cl_graph_restore_cut)");
+  return part_begin(r, node_lo, node_hi, true);
+}
+
+int cl_graph_part_seed_share(cl_graph* r, int64_t out[4]) {
+  GRAPH_CALL(r);
+  if (!out) return set_err(CL_E_INVALID, "null output");
+  if (!r->seed || !r->seed->shared)
+    return set_err(CL_E_STATE, "not a partitioned run begun from a seed (cl_graph_part_begin_seeded)");
+  for (int i = 0; i < 4; ++i) out[i] = r->seed->share[i];
   return CL_OK;
 }
 

@@ -60,8 +60,12 @@ struct GraphSeed {
   DevBuf<int32_t> msgs;            // [info.msgs]; empty with unit payloads
   double build_ms = 0;
   GraphTimer<2> seed_t;            // around the seed kernel of the latest run from the initial state
+  // a partitioned run begun from the seed (cl_graph_part_begin_seeded): this device's slice
+  DevBuf<long long> d_share;       // [4] entry lo, entry hi, message lo, message hi
+  int64_t share[4] = {0, 0, 0, 0};
+  bool shared = false;
   int64_t device_bytes() const {
-    return (int64_t)(init_tok.bytes() + channel.bytes() + count.bytes() + moff.bytes() + msgs.bytes());
+    return (int64_t)(init_tok.bytes() + channel.bytes() + count.bytes() + moff.bytes() + msgs.bytes() + d_share.bytes());
   }
 };
 // A new graph on g's device with g's frozen topology (host arrays copied, device arrays copied

@@ -20,6 +20,11 @@
 //                     payload, position 0 also writes the channel's hq word.  Plain stores; no two
 //                     threads write the same word, and nothing else runs between the reset and the
 //                     kernel after this one.
+// and, for a partitioned run that starts from the seed (cl_graph_part_begin_seeded):
+//   k_seed_share      this device's slice of the entries and of the messages, by two binary
+//                     searches of the entries' channels at the bounds of the owned channel range.
+//   k_seed_range      k_seed over that slice: the same search and stores per message (one device
+//                     function serves both), global draw indices, the draw counter past the whole seed.
 #include <hip/hip_runtime.h>
 
 #include "cg_engine.h"
@@ -142,11 +147,32 @@ __device__ __forceinline__ uint32_t seed_receive_time(const GParams& p, uint64_t
   return 1u + d;
 }
 
+// What cannot be seeded, judged on the whole seed: it freezes the run before its first event, and
+// queues nothing.
+__device__ __forceinline__ int32_t seed_unseedable(const GParams& p, const GSeed& s) {
+  if (s.max_count > ((int64_t)1 << p.cap_log2)) return ST_FIFO_OVERFLOW;
+  if (p.delay_mode != 0 && s.n_msgs > p.sched_len) return ST_DELAY_EXHAUSTED;
+  return ST_OK;
+}
+
+// Message j of the seed, whose entry lies in [lo, hi) with moff[lo] <= j: the last entry with
+// moff <= j, then the ring slot and, at position 0, the channel's hq word.
+__device__ __forceinline__ void seed_message(const GParams& p, const GSeed& s, int64_t j, int64_t lo, int64_t hi) {
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (s.moff[mid] <= j) lo = mid;
+    else hi = mid;
+  }
+  const uint32_t q = (uint32_t)(j - s.moff[lo]);
+  const int32_t c = s.channel[lo];
+  const uint32_t rt = seed_receive_time(p, (uint64_t)j);
+  const uint32_t pay = s.msgs ? (uint32_t)s.msgs[j] : 1u;
+  p.fifo[((size_t)c << p.cap_log2) + q] = ((uint64_t)rt << 32) | pay;
+  if (q == 0) p.hq[c] = ((uint64_t)((uint32_t)s.count[lo] << 16) << 32) | rt;  // head 0, count, head receiveTime
+}
+
 __global__ void __launch_bounds__(kRsThreads) k_seed(GParams p, GSeed s) {
-  // what cannot be seeded freezes the run before its first event, and queues nothing
-  int32_t bad = ST_OK;
-  if (s.max_count > ((int64_t)1 << p.cap_log2)) bad = ST_FIFO_OVERFLOW;
-  else if (p.delay_mode != 0 && s.n_msgs > p.sched_len) bad = ST_DELAY_EXHAUSTED;
+  const int32_t bad = seed_unseedable(p, s);
   const int64_t gid = (int64_t)blockIdx.x * kRsThreads + threadIdx.x;
   if (gid == 0) {  // (after the reset: status 0, draw 0, counters 0)
     if (bad) {
@@ -158,20 +184,47 @@ __global__ void __launch_bounds__(kRsThreads) k_seed(GParams p, GSeed s) {
   }
   if (bad) return;
   const int64_t stride = (int64_t)gridDim.x * kRsThreads;
-  for (int64_t j = gid; j < s.n_msgs; j += stride) {
-    int64_t lo = 0, hi = s.n_ent;  // the last entry with moff <= j (moff[0] = 0)
-    while (hi - lo > 1) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (s.moff[mid] <= j) lo = mid;
-      else hi = mid;
-    }
-    const uint32_t q = (uint32_t)(j - s.moff[lo]);
-    const int32_t c = s.channel[lo];
-    const uint32_t rt = seed_receive_time(p, (uint64_t)j);
-    const uint32_t pay = s.msgs ? (uint32_t)s.msgs[j] : 1u;
-    p.fifo[((size_t)c << p.cap_log2) + q] = ((uint64_t)rt << 32) | pay;
-    if (q == 0) p.hq[c] = ((uint64_t)((uint32_t)s.count[lo] << 16) << 32) | rt;  // head 0, count, head receiveTime
+  for (int64_t j = gid; j < s.n_msgs; j += stride) seed_message(p, s, j, 0, s.n_ent);  // (moff[0] = 0)
+}
+
+// The share of a partitioned run's device (cl_graph_part_begin_seeded): the owned channels are
+// [out_off[part_lo], out_off[part_hi]), so its entries are [e_lo, e_hi) = the first entries with
+// a channel at or above either bound, and its messages [moff[e_lo], moff[e_hi]) of the global
+// draw order (moff[n_ent] = n_msgs).  Lane 0 finds the lower pair, lane 1 the upper:
+// share[0..4) = e_lo, e_hi, m_lo, m_hi.
+__global__ void __launch_bounds__(64) k_seed_share(GParams p, GSeed s, long long* __restrict__ share) {
+  if (threadIdx.x > 1 || blockIdx.x) return;
+  const int32_t bound = p.out_off[threadIdx.x ? p.part_hi : p.part_lo];
+  int64_t lo = 0, hi = s.n_ent;  // the first entry with channel >= bound (n_ent: none)
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (s.channel[mid] < bound) lo = mid + 1;
+    else hi = mid;
   }
+  share[threadIdx.x] = lo;
+  share[2 + threadIdx.x] = lo < s.n_ent ? s.moff[lo] : s.n_msgs;
+}
+
+// k_seed over this device's share alone: message j of [m_lo, m_hi) keeps its global draw index j
+// and searches the entries [e_lo, e_hi) only (moff[e_lo] = m_lo <= j), so an owned channel gets
+// the very words k_seed writes for it and every other channel none.  The verdict on what cannot
+// be seeded is the whole seed's, the same on every device; the draw counter starts past all n_msgs
+// draws and GC_PUSH counts the messages queued here -- also when the share is empty.
+__global__ void __launch_bounds__(kRsThreads) k_seed_range(GParams p, GSeed s, const long long* __restrict__ share) {
+  const int32_t bad = seed_unseedable(p, s);
+  const int64_t e_lo = share[0], e_hi = share[1], m_lo = share[2], m_hi = share[3];
+  const int64_t gid = (int64_t)blockIdx.x * kRsThreads + threadIdx.x;
+  if (gid == 0) {  // (after the reset: status 0, draw 0, counters 0)
+    if (bad) {
+      p.sc->status = bad;
+    } else {
+      p.sc->draw = (unsigned long long)s.n_msgs;
+      p.cpart[GC_PUSH] += (unsigned long long)(m_hi - m_lo);
+    }
+  }
+  if (bad) return;
+  const int64_t stride = (int64_t)gridDim.x * kRsThreads;
+  for (int64_t j = m_lo + gid; j < m_hi; j += stride) seed_message(p, s, j, e_lo, e_hi);
 }
 
 inline unsigned grid_for(int64_t n, int64_t most) {
@@ -211,6 +264,18 @@ int cg_launch_restore_reduce(const int32_t* count, int64_t n_ent, const int32_t*
 
 int cg_launch_seed(const GParams& p, const GSeed& s, void* stream) {
   hipLaunchKernelGGL(k_seed, dim3(grid_for(s.n_msgs, 65535)), dim3(kRsThreads), 0, (hipStream_t)stream, p, s);
+  return (int)hipGetLastError();
+}
+
+int cg_launch_seed_share(const GParams& p, const GSeed& s, long long* share, void* stream) {
+  hipLaunchKernelGGL(k_seed_share, dim3(1), dim3(64), 0, (hipStream_t)stream, p, s, share);
+  return (int)hipGetLastError();
+}
+
+int cg_launch_seed_range(const GParams& p, const GSeed& s, const long long* share, void* stream) {
+  // (the share is on the device only: the grid covers the whole seed, of which it is a slice)
+  hipLaunchKernelGGL(k_seed_range, dim3(grid_for(s.n_msgs, 65535)), dim3(kRsThreads), 0, (hipStream_t)stream, p, s,
+                     share);
   return (int)hipGetLastError();
 }
 

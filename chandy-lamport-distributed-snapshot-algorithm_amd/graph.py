@@ -102,6 +102,8 @@ def glib():
             "cl_graph_restore_time": [vp, vp, vp],
             "cl_graph_restore_cut": [vp, C.POINTER(GraphCut), C.POINTER(C.c_void_p)],
             "cl_graph_part_begin": [vp, i32, i32],
+            "cl_graph_part_begin_seeded": [vp, i32, i32],
+            "cl_graph_part_seed_share": [vp, vp],
             "cl_graph_part_snapshot": [vp, i32, vp],
             "cl_graph_part_pick": [vp, vp, i64, vp],
             "cl_graph_part_receive": [vp, vp, i64, vp, i64, vp],
@@ -1142,7 +1144,8 @@ class GraphSim:
         events are set on it like on any graph.  ClSnapError: E_INVALID for an unknown sid,
         E_NOT_COMPLETE if it has not completed, E_STATE for a partitioned source or a run that is
         not OK.  A partitioned run is restored from through its merged cut:
-        PartitionedGraphSim.collect_sparse(tokens=True), SparseSnapshots.cut, restore_cut."""
+        PartitionedGraphSim.collect_sparse(tokens=True), SparseSnapshots.cut, restore_cut; and a
+        restored graph runs partitioned when PartitionedGraphSim is made of it (from_cut, restore)."""
         h = C.c_void_p()
         _check(self._L.cl_graph_restore(self._h, sid, C.byref(h)))
         return GraphSim._of_handle(self._L, h, self.device, self._ids)
@@ -1188,6 +1191,12 @@ class GraphSim:
         the rank zero-padded to one width, else node by node -- and must come out in the saved
         rank order (ValueError otherwise).  Set the delay source on the result before its first flush, as on
         any restored graph."""
+        return cls.template_of_cut(cut, device, fifo_slots, max_snapshots, max_drain_ticks).restore_cut(cut)
+
+    @classmethod
+    def template_of_cut(cls, cut, device=0, fifo_slots=16, max_snapshots=0, max_drain_ticks=10000):
+        """The template from_cut restores on: a fresh graph of the topology the cut carries, never
+        flushed (host only).  ValueError for a cut without topology or ids out of rank order."""
         if not cut.has_topology:
             raise ValueError("from_cut needs a cut saved with topology=True")
         n = cut.tokens.size
@@ -1208,7 +1217,7 @@ class GraphSim:
             same = n > 0 and t.node_ids() == ids
         if not same:
             raise ValueError("the saved node ids are not in rank order")
-        return t.restore_cut(cut)
+        return t
 
     @property
     def seed_info(self):
@@ -1269,7 +1278,12 @@ class PartitionedGraphSim:
 
     There is no reference counterpart (the reference runs one process); the exchange
     steps restate the tick of sim.go:71-95 across ranks (tests/partition_model.py is the
-    same protocol on the CPU)."""
+    same protocol on the CPU).
+
+    sim is a GraphSim before its first event.  A restored one (GraphSim.restore / restore_cut /
+    from_cut) begins in its cut: this rank queues the messages of its own nodes' out-channels
+    (cl_graph_part_begin_seeded), and seed_share is the slice (entry lo, entry hi, message lo,
+    message hi) of the cut it took -- None for a run from the topology's initial state."""
 
     def __init__(self, sim, rank, world, exchange_device="cpu", transport="host"):
         from . import dist as D
@@ -1287,7 +1301,16 @@ class PartitionedGraphSim:
             raise ValueError(f"{world} ranks over {blocks} node blocks of 256: rank {rank} would own no nodes")
         self.n = n
         self._L = sim._L
-        _check(self._L.cl_graph_part_begin(sim._h, self.lo, self.hi))
+        # a restored graph begins in its cut: this rank queues its own channels' share of the seed
+        info = np.zeros(1, dtype=SEED_INFO_DTYPE)
+        self.seed_share = None
+        if self._L.cl_graph_seed_info_of(sim._h, _p(info)) == 0:
+            _check(self._L.cl_graph_part_begin_seeded(sim._h, self.lo, self.hi))
+            share = np.zeros(4, dtype=np.int64)
+            _check(self._L.cl_graph_part_seed_share(sim._h, _p(share)))
+            self.seed_share = tuple(int(x) for x in share)
+        else:
+            _check(self._L.cl_graph_part_begin(sim._h, self.lo, self.hi))
         self.time = 0
         self.n_sids = 0
         self._frozen = 0
@@ -1519,6 +1542,43 @@ class PartitionedGraphSim:
         allp = [None] * self.world
         dist.all_gather_object(allp, tuple(getattr(mine, f) for f in fields))
         return SparseSnapshots.merge([SparseSnapshots(*p) for p in allp])
+
+    # ---- restore: a partitioned run that begins in a recorded cut (cl_graph_part_begin_seeded) ----
+    def cut(self, sid, topology=False):
+        """The completed snapshot sid of the whole run as a SnapshotCut, on every rank (a
+        collective: collect_sparse of the one sid with tokens, merged); GraphSim.cut's arguments."""
+        return self.collect_sparse(sid, sid + 1, tokens=True).cut(sid, sim=self.g, topology=topology)
+
+    @classmethod
+    def from_cut(cls, cut, rank, world, template=None, configure=None, exchange_device="cpu", transport="host",
+                 **limits):
+        """This rank's part of a partitioned run whose time-0 state is the cut: every rank holds
+        the whole cut (like every array of the mode), restores it on its own unpartitioned
+        template and queues the messages of its own nodes' out-channels, with their draw indices
+        among all of the cut's (seed_share: the slice of entries and messages).  world need not
+        be that of the run that wrote the cut: GraphSim.cut of an unpartitioned run serves too.
+        template: a GraphSim of the topology, as restore_cut takes it (limits, push lanes, delay
+        source); None builds one from a cut with topology=True (GraphSim.template_of_cut, **limits
+        its device, fifo_slots, max_snapshots, max_drain_ticks).  configure(r) runs on the restored
+        GraphSim before the partition begins: set_delay_hash / set_delay_schedule, set_traffic,
+        set_limits.  start() then runs the step-0 traffic and, for a cut that cannot be seeded
+        (status FIFO_OVERFLOW or DELAY_EXHAUSTED), stops every rank at time 0."""
+        if template is None:
+            if not cut.has_topology:
+                raise ValueError("from_cut needs a template, or a cut saved with topology=True")
+            template = GraphSim.template_of_cut(cut, **limits)
+        elif limits:
+            raise ValueError("the limits are the template's")
+        r = template.restore_cut(cut)
+        if configure is not None:
+            configure(r)
+        return cls(r, rank, world, exchange_device=exchange_device, transport=transport)
+
+    def restore(self, sid, template=None, configure=None, **limits):
+        """A new partitioned run over the same ranks, transport and exchange device whose time-0
+        state is the completed snapshot sid of this one (a collective: cut, then from_cut)."""
+        return PartitionedGraphSim.from_cut(self.cut(sid, topology=template is None), self.rank, self.world, template,
+                                            configure, self.dev, self.transport, **limits)
 
     def results(self):
         """(status, final tokens[n], completion ticks, counters, {sid: (tokens[n], offsets,

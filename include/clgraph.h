@@ -323,6 +323,8 @@ int cl_graph_sparse_time(cl_graph* g, double* ms);
  * (hash seed, Go seed or a copy of the schedule); not its traffic, trace or bound stream.  Until
  * its first flush r takes cl_graph_set_limits, _set_delay_*, _set_traffic, _set_push_lanes and
  * _trace_enable like any graph; cl_graph_set_device and cl_graph_part_begin return CL_E_STATE.
+ * r runs partitioned through cl_graph_part_begin_seeded (below, with the partitioned mode), on any
+ * number of devices, each of which holds the whole seed and queues its own channels' share of it.
  * A seeded channel with more messages than r's fifo_slots gives r's run CL_INST_FIFO_OVERFLOW, a
  * delay schedule shorter than M gives it CL_INST_DELAY_EXHAUSTED, either from before its first
  * event (only the status is specified then); exactly fifo_slots messages are fine.
@@ -435,6 +437,36 @@ int cl_graph_trace_read(cl_graph* g, cl_log_event* out, int32_t cap, int32_t* n_
  * the channels into them, completion over its nodes; the program calls (tick, send,
  * flush of a program) return CL_E_STATE once the partitioned run began. */
 int cl_graph_part_begin(cl_graph* g, int32_t node_lo, int32_t node_hi);
+/* The same for a restored graph r (cl_graph_restore, cl_graph_restore_cut) before its first flush:
+ * the partitioned run's time-0 state is the recorded cut.  Every device restores the whole cut
+ * (like every other array of the mode, the seed is graph-sized on each) and calls this with its
+ * own range; the number of devices need not be that of the run that wrote the cut.  A device
+ * owns the queues of its nodes' out-channels, and channels are ordered by (src rank, dest rank):
+ * its channels are [out_off[node_lo], out_off[node_hi]), its entries a contiguous slice [e_lo,
+ * e_hi) of the cut's ascending entries, and its messages the slice [m_lo, m_hi) = [moff(e_lo),
+ * moff(e_hi)) of the draw order of cl_graph_restore (moff = the exclusive prefix of the counts).
+ * The effect is cl_graph_part_begin's, except that
+ *   - the node tokens are the cut's T[v];
+ *   - after the reset and before anything else every owned channel holds exactly what the
+ *     unpartitioned r's queue holds at time 0: message q of entry i has receiveTime
+ *     GetReceiveTime(draw moff(i) + q, time 0) under r's delay source (counter hash or explicit
+ *     schedule) -- the global draw index, whichever device queues it; other devices' channels
+ *     get nothing;
+ *   - the draw counter starts at M on every device, and CL_CNT_PUSH at m_hi - m_lo, so the
+ *     devices' counters sum to the unpartitioned run's M.
+ * What cannot be seeded is judged on the whole cut, the same on every device: max_ch_msgs above
+ * fifo_slots sets CL_INST_FIFO_OVERFLOW, a schedule shorter than M CL_INST_DELAY_EXHAUSTED, at
+ * begin and with nothing queued; the first part_tally / dev_bases (the step-0 traffic) then stops
+ * every device at time 0.  The slice is found and queued by two kernels; one synchronisation.
+ * cl_graph_seed_info_of(r) still describes the whole cut, cl_graph_restore_time's seed_ms is this
+ * device's seed kernel.  Errors: CL_E_STATE, before any device work, for a graph that is not
+ * restored; every refusal of cl_graph_part_begin otherwise (begun already, a non-empty program,
+ * the trace, a Go-seed delay source: CL_E_STATE; an unaligned or out-of-bounds range:
+ * CL_E_INVALID), after which r is what it was and still runs unpartitioned. */
+int cl_graph_part_begin_seeded(cl_graph* r, int32_t node_lo, int32_t node_hi);
+/* out = (e_lo, e_hi, m_lo, m_hi): the slice of the cut's entries and messages this device
+ * queued.  CL_E_STATE before cl_graph_part_begin_seeded and for a graph that is not restored. */
+int cl_graph_part_seed_share(cl_graph* r, int64_t out[4]);
 int cl_graph_part_snapshot(cl_graph* g, int32_t node, int32_t* out_sid);
 int cl_graph_part_pick(cl_graph* g, int32_t* rows, int64_t cap, int64_t* n_rows);
 int cl_graph_part_receive(cl_graph* g, const int32_t* rows, int64_t n, int32_t* reports, int64_t cap,
