@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "cg_host.h"
+#include "cl_delays.h"
 #include "cl_text.h"
 
 using namespace clsnap;
@@ -350,20 +351,13 @@ struct cl_graph {
   // ---- device ----------------------------------------------------------------------
   int ensure_device() {
     if (dev_ready) return CL_OK;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-      return set_err(CL_E_DEVICE, "no HIP device available (the engine needs a gfx950 GPU)");
-    if (device < 0 || device >= count) return set_err(CL_E_DEVICE, "device %d out of range (%d)", device, count);
-    HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-      return set_err(CL_E_DEVICE, "device %d is %s, the engine is built for gfx950", device, prop.gcnArchName);
+    int rc = open_gfx950(device, &prop);
+    if (rc) return rc;
     n_cus = prop.multiProcessorCount;
     HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     own_stream = stream;
     dev_ready = true;
-    int rc;
     std::vector<int2> route((size_t)e);
     for (int64_t c = 0; c < e; ++c) route[c] = make_int2(ch_dst[c], ch_inpos[c]);
     // out-link index at the sender of every in-channel (expansions match it against the
@@ -439,9 +433,8 @@ struct cl_graph {
     const int64_t need = std::max<int64_t>(16, draws_bound());
     if (sched_len >= need) return CL_OK;
     std::vector<uint8_t> s((size_t)need);
-    int rc = cl_go_delay_schedule(go_seed_val, 1, need, s.data());  // instance 0 of the Go streams
-    if (rc) return rc;
-    if ((rc = d_sched.upload(s))) return rc;
+    go_schedule(go_seed_val, nullptr, 1, need, s.data());  // instance 0 of the Go streams
+    if (int rc = d_sched.upload(s)) return rc;
     sched_len = need;
     return CL_OK;
   }

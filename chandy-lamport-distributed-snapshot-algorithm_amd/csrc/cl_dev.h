@@ -1,7 +1,8 @@
-// cl_dev.h -- what every host unit (cl_host.cpp, cl_analytics.cpp, cg_host.cpp, cg_readout.cpp) owns on the
-// device: the error return of a failed HIP call, a buffer that frees itself, and a set of timing
-// events that destroy themselves.  Nothing here orders the frees against work in flight: an owner
-// synchronises its streams in its destructor's body, and its members go after that.
+// cl_dev.h -- what every host unit (cl_host.cpp, cl_delays.cpp, cl_analytics.cpp, cg_host.cpp,
+// cg_readout.cpp) owns on the device: the error return of a failed HIP call, the one way a device
+// is opened, a buffer that frees itself, and a set of timing events that destroy themselves.
+// Nothing here orders the frees against work in flight: an owner synchronises its streams in its
+// destructor's body, and its members go after that.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,10 @@ int set_err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3))
     hipError_t e_ = (expr);                                                                         \
     if (e_ != hipSuccess) return clsnap::set_err(CL_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
+
+// Makes `device` current and reads its properties; CL_E_DEVICE where there is no device, the
+// ordinal is out of range, or the device is not a gfx950 (defined in cl_host.cpp).
+int open_gfx950(int device, hipDeviceProp_t* prop);
 
 // n elements of T on the device, grown on demand (the contents do not survive a growth).
 template <class T>

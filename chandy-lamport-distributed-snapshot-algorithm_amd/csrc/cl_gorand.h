@@ -1,7 +1,7 @@
 // cl_gorand.h -- Go math/rand (Go 1.22 rngSource, rng.go) in closed form, for host and device.
 //
 // The engine replays rand.Intn(5) of rand.Seed(seed) per instance.  The sequential generator
-// (cl_host.cpp GoRand) seeds a 607-word state with 1,841 Lehmer steps and then runs an additive
+// (cl_delays.cpp GoRand) seeds a 607-word state with 1,841 Lehmer steps and then runs an additive
 // lagged Fibonacci recurrence over it.  Both parts have a form that needs no sequential state:
 //
 //   seeding  seedrand is Schrage's form of x <- 48271 x mod M, M = 2^31 - 1, so the n-th x after the

@@ -7,13 +7,12 @@
 //   * events: SendTokens / StartSnapshot / Tick / drain become an op program that the
 //     gfx950 kernel executes for every instance (cl_kernels.hip);
 //   * delays: the reference's rand.Intn(5) (sim.go:101) is replayed from a per-instance
-//     schedule, by default Go's own math/rand stream for seed_base + i, restated here;
+//     schedule, by default Go's own math/rand stream for seed_base + i (cl_delays.cpp);
 //   * results: snapshots are packed back into the reference's {tokenMap, messages}
 //     shape (sim.go:134-173) per instance.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstdarg>
@@ -24,13 +23,12 @@
 #include <mutex>
 #include <sstream>
 #include <string>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/clsnap.h"
+#include "cl_delays.h"
 #include "cl_engine.h"
-#include "cl_gorand.h"
 #include "cl_host.h"
 #include "cl_text.h"
 
@@ -54,6 +52,18 @@ int set_err(int code, const char* fmt, ...) {
   return rc;
 }
 const char* last_error() { return g_last_error.c_str(); }
+
+int open_gfx950(int device, hipDeviceProp_t* prop) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+    return set_err(CL_E_DEVICE, "no HIP device available (the engine needs a gfx950 GPU)");
+  if (device < 0 || device >= count) return set_err(CL_E_DEVICE, "device %d out of range (%d)", device, count);
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipGetDeviceProperties(prop, device));
+  if (std::strncmp(prop->gcnArchName, "gfx950", 6) != 0)
+    return set_err(CL_E_DEVICE, "device %d is %s, the engine is built for gfx950", device, prop->gcnArchName);
+  return CL_OK;
+}
 }  // namespace clsnap
 
 // Per-wave LDS words available for staging the wave's delay rows (kernel reads the
@@ -73,184 +83,6 @@ constexpr int64_t kMapPct = 92;
 // CL_PROGRAM_AUTO: replays of a planned program on the lanes kernels run kernels specialized on
 // the program where AUTO's own lanes condition holds (DESIGN §9 round 9 has the A/B this rests on)
 constexpr bool kProgramKernelsByDefault = true;
-
-namespace {
-
-// ---------------------------------------------------------------------------
-// Go math/rand (Go 1.22, go.mod:3): rngSource seeded as in rng.go, Intn -> Int31n.
-// rngCooked (cl_gorand.h) is regenerated offline by oracle/gen_go_rng_cooked.py (KAT-pinned).
-// ---------------------------------------------------------------------------
-using gorand::kRngCooked;
-
-struct GoRand {
-  int tap = 0, feed = 334;
-  uint64_t vec[607];
-
-  static int32_t seedrand(int32_t x) {
-    const int32_t hi = x / 44488, lo = x % 44488;
-    x = 48271 * lo - 3399 * hi;
-    if (x < 0) x += 2147483647;
-    return x;
-  }
-  explicit GoRand(int64_t seed) {
-    seed %= 2147483647LL;
-    if (seed < 0) seed += 2147483647LL;
-    if (seed == 0) seed = 89482311;
-    int32_t x = (int32_t)seed;
-    for (int i = -20; i < 607; ++i) {
-      x = seedrand(x);
-      if (i >= 0) {
-        uint64_t u = (uint64_t)(int64_t)x << 40;
-        x = seedrand(x);
-        u ^= (uint64_t)(int64_t)x << 20;
-        x = seedrand(x);
-        u ^= (uint64_t)(int64_t)x;
-        vec[i] = u ^ (uint64_t)kRngCooked[i];
-      }
-    }
-  }
-  uint64_t uint64() {
-    if (--tap < 0) tap += 607;
-    if (--feed < 0) feed += 607;
-    vec[feed] += vec[tap];
-    return vec[feed];
-  }
-  int64_t int63() { return (int64_t)(uint64() & 0x7fffffffffffffffULL); }
-  int32_t int31() { return (int32_t)(int63() >> 32); }
-  int32_t int31n(int32_t n) {
-    if ((n & (n - 1)) == 0) return int31() & (n - 1);
-    const int32_t max = (int32_t)((1LL << 31) - 1 - (int64_t)((1ULL << 31) % (uint32_t)n));
-    int32_t v = int31();
-    while (v > max) v = int31();
-    return v % n;
-  }
-};
-
-int host_threads() {
-  unsigned n = std::thread::hardware_concurrency();
-  if (n == 0) n = 1;
-  return (int)std::min(n, 16u);  // the GPU box grants 16 host cores per GPU
-}
-
-// seed of instance i: seeds[i], or seed_base + i (wrapping) without a list
-inline int64_t seed_of(int64_t seed_base, const int64_t* seeds, int64_t i) {
-  return seeds ? seeds[i] : (int64_t)((uint64_t)seed_base + (uint64_t)i);
-}
-
-void go_row(int64_t seed, int64_t draws, uint8_t* o) {
-  GoRand r(seed);
-  for (int64_t k = 0; k < draws; ++k) o[k] = (uint8_t)r.int31n(5);  // rand.Intn(maxDelay)
-}
-
-void go_schedule(int64_t seed_base, const int64_t* seeds, int64_t n, int64_t draws, uint8_t* out) {
-  const int T = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), (n + 255) / 256));
-  std::vector<std::thread> th;
-  for (int t = 0; t < T; ++t) {
-    th.emplace_back([=] {
-      for (int64_t i = n * t / T; i < n * (t + 1) / T; ++i) go_row(seed_of(seed_base, seeds, i), draws, out + i * draws);
-    });
-  }
-  for (auto& x : th) x.join();
-}
-
-// The same plane from the closed form of cl_gorand.h, row by row as the device generator computes
-// it; a row that met a rejection is regenerated sequentially.  Returns the number of such rows.
-int64_t go_schedule_jump(int64_t seed_base, const int64_t* seeds, int64_t n, int64_t draws, uint8_t* out) {
-  static const std::vector<uint32_t> pw = [] {
-    std::vector<uint32_t> t(gorand::kPowN);
-    gorand::build_pow_table(t.data());
-    return t;
-  }();
-  const int T = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), (n + 255) / 256));
-  std::atomic<int64_t> rejected{0};
-  std::vector<std::thread> th;
-  for (int t = 0; t < T; ++t) {
-    th.emplace_back([=, &rejected] {
-      std::vector<uint64_t> o((size_t)draws + 1);
-      for (int64_t i = n * t / T; i < n * (t + 1) / T; ++i) {
-        const int64_t seed = seed_of(seed_base, seeds, i);
-        const uint32_t x0 = gorand::norm_seed(seed);
-        uint8_t* row = out + i * draws;
-        bool rej = false;
-        for (int64_t k = 1; k <= draws; ++k) {
-          o[(size_t)k] = gorand::output(x0, (int32_t)k, pw.data(), kRngCooked, o.data());
-          row[k - 1] = (uint8_t)gorand::intn5(o[(size_t)k], &rej);
-        }
-        if (rej) {
-          go_row(seed, draws, row);
-          ++rejected;
-        }
-      }
-    });
-  }
-  for (auto& x : th) x.join();
-  return rejected.load();
-}
-
-// ---- the device generator (cl_gorand.hip) and its host-side patching ---------------------------
-// Shapes it takes: rows up to the documented cap, a plane of fewer than 2^31 dwords.
-bool delaygen_fits(int64_t n, int64_t row) {
-  return n >= 1 && row >= 4 && row <= CL_DELAYGEN_MAX_DRAWS && n * (row / 4) < (1ll << 31);
-}
-
-struct DeviceGen {
-  double device_ms = 0, host_ms = 0;
-  int64_t patched = 0;
-  bool overflow = false;  // more flagged rows than the list holds: nothing was patched
-};
-
-// Generate the [n][row] plane at d_plane on `stream` (seeds: d_seeds, a device array, or
-// seed_base + i), wait, and regenerate the rows that met a rejection among their first `draws`
-// outputs with the sequential generator.  d_flag has 1 + kDelayGenFlagCap words; `tm` times the kernel.
-int device_generate(int device, hipStream_t stream, int32_t n_cus, int64_t seed_base, const long long* d_seeds,
-                    int64_t n, int64_t row, int64_t draws, uint8_t* d_plane, unsigned long long* d_flag,
-                    DevTimer<2>* tm, DeviceGen* g) {
-  const void* tables = nullptr;
-  int e = gorand::delaygen_tables(device, &tables);
-  if (e) return set_err(CL_E_DEVICE, "delay generator tables: %s", hipGetErrorString((hipError_t)e));
-  HIP_TRY(hipSetDevice(device));
-  HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(unsigned long long), stream));
-  gorand::DelayGenParams p{};
-  p.plane = d_plane;
-  p.seeds = d_seeds;
-  p.seed_base = seed_base;
-  p.n_inst = n;
-  p.row = (int32_t)row;
-  p.draws = (int32_t)draws;
-  p.flagged = d_flag;
-  p.flag_cap = gorand::kDelayGenFlagCap;
-  p.tables = tables;
-  if (int rc = tm->mark(0, stream)) return rc;
-  e = gorand::launch_delaygen(p, n_cus, stream);
-  if (e) return set_err(CL_E_DEVICE, "delay generator launch failed: %s", hipGetErrorString((hipError_t)e));
-  if (int rc = tm->mark(1, stream)) return rc;
-  unsigned long long cnt = 0;
-  HIP_TRY(hipMemcpyAsync(&cnt, d_flag, sizeof cnt, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  const auto t0 = std::chrono::steady_clock::now();
-  *g = DeviceGen{};
-  if (cnt > (unsigned long long)gorand::kDelayGenFlagCap) {
-    g->overflow = true;
-  } else if (cnt) {
-    std::vector<unsigned long long> rows((size_t)cnt);
-    HIP_TRY(hipMemcpy(rows.data(), d_flag + 1, (size_t)cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    std::sort(rows.begin(), rows.end());
-    rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
-    std::vector<uint8_t> buf((size_t)row);
-    for (unsigned long long i : rows) {
-      if (i >= (unsigned long long)n) return set_err(CL_E_DEVICE, "delay generator flagged row %llu of %lld", i, (long long)n);
-      long long seed = (long long)((uint64_t)seed_base + (uint64_t)i);
-      if (d_seeds) HIP_TRY(hipMemcpy(&seed, d_seeds + i, sizeof seed, hipMemcpyDeviceToHost));
-      go_row((int64_t)seed, row, buf.data());
-      HIP_TRY(hipMemcpy(d_plane + (size_t)i * (size_t)row, buf.data(), (size_t)row, hipMemcpyHostToDevice));
-    }
-    g->patched = (int64_t)rows.size();
-  }
-  g->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return tm->ms(0, 1, &g->device_ms);
-}
-
-}  // namespace
 
 // ---------------------------------------------------------------------------
 // cl_sim
@@ -317,24 +149,8 @@ struct cl_sim {
   bool auto_cap = true;  // choose cap_log2 per layout (cl_set_limits with slots > 0 pins it)
   int64_t max_drain = 10000;
 
-  // delays
-  bool go_seeds = true;
-  int64_t seed_base = 8053172852482175524LL;  // snapshot_test.go:9,20 (seed + 1)
-  std::vector<uint8_t> user_sched;
-  int64_t user_draws = 0;
-  int64_t dev_draws = -1;  // valid draws per instance of the schedule resident on the device
-  int64_t dev_row = 0;     // its row stride (multiple of 16)
-  // Go streams: which generator makes the rows (cl_set_delay_generator) and which made the rows
-  // now on the device; per-instance seeds (cl_set_delay_go_seed_list) replace seed_base + i.  The
-  // list lives on the host until the device generator first needs it, then in d_seeds only (the
-  // host generator fetches it back).
-  int32_t delaygen = CL_DELAYGEN_HOST;
-  int32_t dev_gen = -1;
-  bool seed_list = false, seeds_on_dev = false;
-  std::vector<int64_t> h_seeds;
-  bool dg_timed = false;  // a generation has run: the three figures of cl_delay_gen_time
-  double dg_device_ms = 0, dg_host_ms = 0;
-  int64_t dg_patched = 0;
+  // delays: the source and its rows on the device (cl_delays.h)
+  DelaySource delays;
 
   // device
   bool dev_ready = false;
@@ -395,10 +211,6 @@ struct cl_sim {
   int32_t dops_begin = -1;
   DevBuf<uint32_t> d_topo;
   DevBuf<int32_t> d_fin_tok;
-  DevBuf<uint8_t> d_sched;
-  DevBuf<long long> d_seeds;              // [n_inst] the seed list, once the device generator ran with it
-  DevBuf<unsigned long long> d_dg_flag;   // device generator: count, then the rows that met a rejection
-  DevTimer<2> dg_tm;
   DevBuf<uint32_t> d_state;
   DevBuf<int32_t> d_regs;
   DevBuf<uint32_t> d_snap_nod;  // [s_cap][stride][n][lay.rw] node snapshot records
@@ -452,10 +264,10 @@ struct cl_sim {
   DevBuf<int32_t> d_rec_slot;
   // The plan's delay rows packed for the instance-per-lane kernel (ExecParams::sched_pk,
   // cl_rowpack.hip): made at the first replay through the slot map, valid for the plan (plan_gen)
-  // and the rows on the device (sched_gen: every write of d_sched advances it) it was packed
-  // from; a replay that finds another plan or other rows packs again.
+  // and the rows on the device (delays.rows().gen) it was packed from; a replay that finds another
+  // plan or other rows packs again.
   DevBuf<uint32_t> d_sched_pk;
-  int64_t sched_gen = 0, pk_plan_gen = -1, pk_sched_gen = -1;
+  int64_t pk_plan_gen = -1, pk_rows_gen = -1;
   DevBuf<int32_t> d_hist;
   DevBuf<unsigned long long> d_sums;
   // device event trace (cl_trace_enable): instances [trace_lo, trace_lo + trace_n)
@@ -584,15 +396,8 @@ struct cl_sim {
 
   int ensure_device() {
     if (dev_ready) return CL_OK;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-      return set_err(CL_E_DEVICE, "no HIP device available (the engine needs a gfx950 GPU)");
-    if (device < 0 || device >= count) return set_err(CL_E_DEVICE, "device %d out of range (%d)", device, count);
-    HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-      return set_err(CL_E_DEVICE, "device %d is %s, the engine is built for gfx950", device, prop.gcnArchName);
+    if (int rc = open_gfx950(device, &prop)) return rc;
     HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     dev_ready = true;
     return CL_OK;
@@ -628,105 +433,13 @@ struct cl_sim {
     return CL_OK;
   }
 
-  // (the generator's kernel has finished whenever an ABI call returns: nothing reads d_seeds then)
-  void drop_seed_list() {
-    seed_list = seeds_on_dev = false;
-    std::vector<int64_t>().swap(h_seeds);
-    if (dev_ready && d_seeds.p) {
-      (void)hipSetDevice(device);
-      d_seeds.release();
-    }
-  }
-
-  // Rows of D draws from the device generator, on the sim's stream, straight into d_sched.
-  // *done = false when more rows met a rejection than its list holds (the caller then takes the
-  // host generator).
-  int generate_on_device(int64_t D, bool* done) {
-    int rc;
-    HIP_TRY(hipStreamSynchronize(stream));  // (an async launch may read d_sched)
-    dev_draws = -1;                         // (the rows on the device are about to be overwritten)
-    sched_gen += 1;
-    if ((rc = d_sched.ensure((size_t)(D * n_inst)))) return rc;
-    if ((rc = d_dg_flag.ensure(1 + (size_t)gorand::kDelayGenFlagCap))) return rc;
-    if (seed_list && !seeds_on_dev) {
-      if ((rc = d_seeds.ensure((size_t)n_inst))) return rc;
-      HIP_TRY(hipMemcpy(d_seeds.p, h_seeds.data(), (size_t)n_inst * sizeof(int64_t), hipMemcpyHostToDevice));
-      std::vector<int64_t>().swap(h_seeds);
-      seeds_on_dev = true;
-    }
-    if ((rc = cu_count())) return rc;
-    DeviceGen g;
-    if ((rc = device_generate(device, stream, n_cus, seed_base, seed_list ? d_seeds.p : nullptr, n_inst, D, D,
-                              d_sched.p, d_dg_flag.p, &dg_tm, &g)))
-      return rc;
-    *done = !g.overflow;
-    if (g.overflow) return CL_OK;
-    dg_device_ms = g.device_ms;
-    dg_host_ms = g.host_ms;
-    dg_patched = g.patched;
-    dg_timed = true;
-    dev_gen = CL_DELAYGEN_DEVICE;
-    return CL_OK;
-  }
-
-  int ensure_delays() {
-    int64_t need = draws_needed();
-    if (go_seeds) {
-      int64_t D = std::max<int64_t>(16, (need + 15) / 16 * 16);
-      if (dev_draws >= D) return CL_OK;
-      int rc;
-      bool on_device = delaygen == CL_DELAYGEN_DEVICE && delaygen_fits(n_inst, D);
-      if (on_device) {
-        if ((rc = generate_on_device(D, &on_device))) return rc;
-      }
-      if (!on_device) {
-        const auto t0 = std::chrono::steady_clock::now();
-        if (seed_list && seeds_on_dev) {  // (the list goes back to the host generator's side)
-          h_seeds.resize((size_t)n_inst);
-          HIP_TRY(hipMemcpy(h_seeds.data(), d_seeds.p, (size_t)n_inst * sizeof(int64_t), hipMemcpyDeviceToHost));
-          d_seeds.release();
-          seeds_on_dev = false;
-        }
-        std::vector<uint8_t> sched((size_t)(D * n_inst));
-        go_schedule(seed_base, seed_list ? h_seeds.data() : nullptr, n_inst, D, sched.data());
-        if (dev_ready) HIP_TRY(hipStreamSynchronize(stream));  // (an async launch may read d_sched)
-        if ((rc = d_sched.ensure(sched.size()))) return rc;
-        HIP_TRY(hipMemcpy(d_sched.p, sched.data(), sched.size(), hipMemcpyHostToDevice));
-        sched_gen += 1;
-        dg_device_ms = 0;
-        dg_host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        dg_patched = 0;
-        dg_timed = true;
-        dev_gen = CL_DELAYGEN_HOST;
-      }
-      dev_draws = D;  // longer rows of the same streams: saved draw cursors stay valid
-      plan_ops = plan_tried = -1;
-      dev_row = D;
-      return CL_OK;
-    }
-    if (dev_draws == user_draws) return CL_OK;
-    const int64_t row = (user_draws + 15) / 16 * 16;
-    std::vector<uint8_t> padded((size_t)(row * n_inst), 0);
-    for (int64_t i = 0; i < n_inst; ++i)
-      std::memcpy(&padded[(size_t)(i * row)], &user_sched[(size_t)(i * user_draws)], (size_t)user_draws);
-    if (dev_ready) HIP_TRY(hipStreamSynchronize(stream));  // (an async launch may read d_sched)
-    int rc = d_sched.ensure(padded.size());
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(d_sched.p, padded.data(), padded.size(), hipMemcpyHostToDevice));
-    sched_gen += 1;
-    dev_draws = user_draws;
-    dev_row = row;
-    plan_ops = plan_tried = -1;
-    return CL_OK;
-  }
-
   // The layout the next launch would use: s_cap, the LDS ring size and the delay row (no
   // allocation; ensure_layout applies it).
   Layout plan_layout(int32_t* s_cap_out, int32_t* cap_log2_out, int64_t* row_out) const {
     const int n = (int)ids.size();
     const int32_t want_s = std::max<int32_t>(4, (n_sids + 3) / 4 * 4);
     const int32_t sc = std::max(want_s, s_cap);
-    const int64_t row = go_seeds ? std::max<int64_t>(16, (draws_needed() + 15) / 16 * 16) : (user_draws + 15) / 16 * 16;
+    const int64_t row = delays.row_for(draws_needed());
     const int32_t od = std::max(max_out, 1), id = std::max(max_in, 1);
     int32_t cl = cap_log2;
     if (auto_cap) {
@@ -762,7 +475,7 @@ struct cl_sim {
     int32_t want_s = std::max<int32_t>(4, (n_sids + 3) / 4 * 4);
     int ocap = ocap_log2_needed();
     if (!need_fresh && lay.wave_words && want_s <= s_cap && ocap <= lay.ocap_log2 && lay.cap_log2 == cap_log2 &&
-        layout_row == (go_seeds ? std::max<int64_t>(16, (draws_needed() + 15) / 16 * 16) : (user_draws + 15) / 16 * 16))
+        layout_row == delays.row_for(draws_needed()))
       return CL_OK;
     if (dev_ready) HIP_TRY(hipStreamSynchronize(stream));  // (buffers below may be reallocated or rewritten)
     if (n == 0) return set_err(CL_E_STATE, "the topology has no nodes");
@@ -906,8 +619,8 @@ struct cl_sim {
     p.lay = lay;
     p.n_started_before = n_started_before;
     p.topo_w = 3 + max_in;  // ensure_layout guarantees lay.od == lay.id >= every node's degree
-    p.draws = dev_draws;
-    p.sched_row = dev_row;
+    p.draws = delays.rows().draws;
+    p.sched_row = delays.rows().row;
     p.n_inst = n_inst;
     p.stride = stride;
     p.fresh = op_begin == 0 ? 1 : 0;
@@ -934,13 +647,17 @@ struct cl_sim {
   int launch(bool force_fresh, bool save_state) {
     int rc = freeze();
     if (rc) return rc;
-    if ((rc = ensure_device())) return rc;
-    HIP_TRY(hipSetDevice(device));
+    SimDevice dev;
+    if ((rc = sim_device(this, &dev))) return rc;
     if (!d_topo.p && (rc = upload_topology())) return rc;
     if ((rc = ensure_layout())) return rc;
-    if ((rc = ensure_delays())) return rc;
-    if (lay.x_delay && dev_row != layout_row)
-      return set_err(CL_E_STATE, "delay rows (%lld) differ from the staged layout (%lld)", (long long)dev_row,
+    bool rewritten = false;
+    rc = delays.ensure(dev, n_inst, draws_needed(), &rewritten);
+    if (rewritten) plan_ops = plan_tried = -1;  // (the plan is of a run on the old rows)
+    if (rc) return rc;
+    const DelayRows rows = delays.rows();
+    if (lay.x_delay && rows.row != layout_row)
+      return set_err(CL_E_STATE, "delay rows (%lld) differ from the staged layout (%lld)", (long long)rows.row,
                      (long long)layout_row);
     if (force_fresh || !state_valid) need_fresh = true;
     if (!need_fresh && executed == (int32_t)ops.size()) return CL_OK;
@@ -986,17 +703,17 @@ struct cl_sim {
     // a lanes replay through the slot map reads its delay rows from the plan's packed copy
     // (CLSNAP_ROW_PACK=0 in a dbg build: the byte rows, for A/Bs)
     if (lanes && planned && p.inst_map && debug_knob("CLSNAP_ROW_PACK", 1)) {
-      if (pk_plan_gen != plan_gen || pk_sched_gen != sched_gen) {
+      if (pk_plan_gen != plan_gen || pk_rows_gen != rows.gen) {
         // (an earlier replay's halves may still read the plane; stream2's half of the coming one
         // does not wait for `stream`, so the packing is finished before it is launched)
         if ((rc = join_stream2())) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
-        if ((rc = d_sched_pk.ensure(row_pack_words(n_inst, dev_row)))) return rc;
-        const int pe = launch_row_pack(d_sched.p, dev_row, d_map.p, n_inst, d_sched_pk.p, stream);
+        if ((rc = d_sched_pk.ensure(row_pack_words(n_inst, rows.row)))) return rc;
+        const int pe = launch_row_pack(rows.d, rows.row, d_map.p, n_inst, d_sched_pk.p, stream);
         if (pe != 0) return set_err(CL_E_DEVICE, "row pack launch failed: %s", hipGetErrorString((hipError_t)pe));
         HIP_TRY(hipStreamSynchronize(stream));
         pk_plan_gen = plan_gen;
-        pk_sched_gen = sched_gen;
+        pk_rows_gen = rows.gen;
       }
       p.sched_pk = d_sched_pk.p;
     }
@@ -1073,7 +790,7 @@ struct cl_sim {
     }
     if (blocked) p.rec_blocked = 1;
     bool used_lanes = lanes;
-    int e = lanes ? launch_lanes(p, d_topo.p, d_ops.p, d_sched.p, el) : launch_exec(p, d_topo.p, d_ops.p, d_sched.p, el);
+    int e = lanes ? launch_lanes(p, d_topo.p, d_ops.p, rows.d, el) : launch_exec(p, d_topo.p, d_ops.p, rows.d, el);
     if (lanes && e == (int)hipErrorInvalidImage) {
       if (engine == CL_ENGINE_LANES)
         return set_err(CL_E_DEVICE, "instance-per-lane kernel compilation failed: %s", lanes_error());
@@ -1083,7 +800,7 @@ struct cl_sim {
       // kernel -- cl_exec_engine reports the kernel each launch used)
       lanes_unavailable = true;
       used_lanes = false;
-      e = launch_exec(p, d_topo.p, d_ops.p, d_sched.p, el);
+      e = launch_exec(p, d_topo.p, d_ops.p, rows.d, el);
     }
     last_engine = used_lanes ? CL_ENGINE_LANES : CL_ENGINE_NODES;
     last_prog = used_lanes ? prog_used : 0;
@@ -1576,10 +1293,7 @@ int cl_set_limits(cl_sim* sim, int32_t fifo_lds_slots, int64_t max_drain_ticks) 
 int cl_set_delay_go_seeds(cl_sim* sim, int64_t seed_base) {
   SIM_CALL(sim);
   sim->plan_ops = sim->plan_tried = -1;
-  sim->go_seeds = true;
-  sim->seed_base = seed_base;
-  sim->drop_seed_list();
-  sim->dev_draws = -1;
+  sim->delays.set_go_seeds(seed_base);
   sim->need_fresh = true;
   return CL_OK;
 }
@@ -1588,11 +1302,7 @@ int cl_set_delay_go_seed_list(cl_sim* sim, const int64_t* seeds, int64_t n) {
   SIM_CALL(sim);
   if (!seeds || n != sim->n_inst) return set_err(CL_E_INVALID, "the seed list must have one seed per instance");
   sim->plan_ops = sim->plan_tried = -1;
-  sim->drop_seed_list();
-  sim->h_seeds.assign(seeds, seeds + n);
-  sim->seed_list = true;
-  sim->go_seeds = true;
-  sim->dev_draws = -1;
+  sim->delays.set_seed_list(seeds, n);
   sim->need_fresh = true;
   return CL_OK;
 }
@@ -1600,10 +1310,8 @@ int cl_set_delay_go_seed_list(cl_sim* sim, const int64_t* seeds, int64_t n) {
 int cl_set_delay_generator(cl_sim* sim, int32_t mode) {
   SIM_CALL(sim);
   if (mode != CL_DELAYGEN_HOST && mode != CL_DELAYGEN_DEVICE) return set_err(CL_E_INVALID, "unknown delay generator %d", mode);
-  if (mode == sim->delaygen) return CL_OK;
-  sim->delaygen = mode;
+  if (!sim->delays.set_generator(mode)) return CL_OK;
   sim->plan_ops = sim->plan_tried = -1;
-  sim->dev_draws = -1;  // the next launch generates the rows again, with this generator
   sim->need_fresh = true;
   return CL_OK;
 }
@@ -1611,17 +1319,13 @@ int cl_set_delay_generator(cl_sim* sim, int32_t mode) {
 int cl_delay_generator(cl_sim* sim, int32_t* mode) {
   SIM_CALL(sim);
   if (!mode) return set_err(CL_E_INVALID, "null output");
-  *mode = sim->go_seeds && sim->dev_draws >= 0 ? sim->dev_gen : -1;
+  *mode = sim->delays.generator_used();
   return CL_OK;
 }
 
 int cl_delay_gen_time(cl_sim* sim, double* device_ms, double* host_ms, int64_t* patched_rows) {
   SIM_CALL(sim);
-  if (!sim->dg_timed) return set_err(CL_E_STATE, "no delay generation has run");
-  if (device_ms) *device_ms = sim->dg_device_ms;
-  if (host_ms) *host_ms = sim->dg_host_ms;
-  if (patched_rows) *patched_rows = sim->dg_patched;
-  return CL_OK;
+  return sim->delays.gen_time(device_ms, host_ms, patched_rows);
 }
 
 int cl_set_delay_schedule(cl_sim* sim, const uint8_t* delays, int64_t draws_per_instance) {
@@ -1631,11 +1335,7 @@ int cl_set_delay_schedule(cl_sim* sim, const uint8_t* delays, int64_t draws_per_
   const size_t n = (size_t)(draws_per_instance * sim->n_inst);
   for (size_t i = 0; i < n; ++i)
     if (delays[i] >= 5) return set_err(CL_E_INVALID, "delay %u at %zu outside [0, maxDelay)", delays[i], i);
-  sim->user_sched.assign(delays, delays + n);
-  sim->user_draws = draws_per_instance;
-  sim->go_seeds = false;
-  sim->drop_seed_list();
-  sim->dev_draws = -1;
+  sim->delays.set_schedule(delays, draws_per_instance, sim->n_inst);
   sim->need_fresh = true;
   return CL_OK;
 }
@@ -1977,10 +1677,10 @@ int cl_delay_draws_needed(const cl_sim* sim, int64_t* draws) {
 int cl_device_bytes(const cl_sim* sim, int64_t* bytes) {
   SIM_CALL(sim);
   int64_t b = 0;
-  b += sim->d_ops.n * sizeof(Op) + sim->d_topo.n * 4 + sim->d_sched.n + sim->d_sched_pk.n * 4 + sim->d_state.n * 4 + sim->d_regs.n * 4;
+  b += sim->d_ops.n * sizeof(Op) + sim->d_topo.n * 4 + sim->d_sched_pk.n * 4 + sim->d_state.n * 4 + sim->d_regs.n * 4;
   b += sim->d_snap_nod.n * 4 + sim->d_snap_tick.n * 4 + sim->d_ovf.n * 4;
   b += sim->d_ovh.n * 4 + sim->d_hist.n * 4 + sim->d_sums.n * 8 + sim->d_fin_tok.n * 4;
-  b += sim->d_seeds.n * 8 + sim->d_dg_flag.n * 8;  // (the seed list and the device generator's flagged rows)
+  b += sim->delays.device_bytes();  // (the delay rows, the seed list and the device generator's flagged rows)
   b += analytics_device_bytes(sim->analytics);  // (selection scratch, sets alive, crosstab words)
   *bytes = b;
   return CL_OK;
@@ -2257,85 +1957,6 @@ int cl_instance_hashes(cl_sim* sim, int64_t lo, int64_t n, uint64_t* out) {
   if (e) return set_err(CL_E_DEVICE, "checksum kernel launch failed: %s", hipGetErrorString((hipError_t)e));
   HIP_TRY(hipMemcpyAsync(out, hb.p + lo, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, sim->stream));
   HIP_TRY(hipStreamSynchronize(sim->stream));
-  return CL_OK;
-}
-
-int cl_go_delay_schedule(int64_t seed_base, int64_t n, int64_t draws, uint8_t* out) {
-  if (!out || n < 0 || draws < 0) return set_err(CL_E_INVALID, "bad arguments");
-  go_schedule(seed_base, nullptr, n, draws, out);
-  return CL_OK;
-}
-
-int cl_go_delay_schedule_jump(int64_t seed_base, const int64_t* seeds, int64_t n, int64_t draws, uint8_t* out,
-                              int64_t* rejected_rows) {
-  if (!out || n < 0 || draws < 0 || draws > (1 << 30)) return set_err(CL_E_INVALID, "bad arguments");
-  const int64_t r = go_schedule_jump(seed_base, seeds, n, draws, out);
-  if (rejected_rows) *rejected_rows = r;
-  return CL_OK;
-}
-
-int cl_go_delay_schedule_device(int32_t device, int64_t seed_base, const int64_t* seeds, int64_t n, int64_t draws,
-                                uint8_t* out, int64_t* patched_rows, double* device_ms) {
-  if (!out || n < 0 || draws < 0) return set_err(CL_E_INVALID, "bad arguments");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return set_err(CL_E_DEVICE, "no HIP device available (the engine needs a gfx950 GPU)");
-  if (device < 0 || device >= count) return set_err(CL_E_DEVICE, "device %d out of range (%d)", device, count);
-  HIP_TRY(hipSetDevice(device));
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, device));
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return set_err(CL_E_DEVICE, "device %d is %s, the engine is built for gfx950", device, prop.gcnArchName);
-  if (patched_rows) *patched_rows = 0;
-  if (device_ms) *device_ms = 0;
-  if (n == 0 || draws == 0) return CL_OK;
-  const int64_t row = std::max<int64_t>(16, (draws + 15) / 16 * 16);  // the engine's row padding
-  if (!delaygen_fits(n, row)) {  // above the cap: the host generator, as in the engine
-    go_schedule(seed_base, seeds, n, draws, out);
-    return CL_OK;
-  }
-  struct Scratch {  // (the buffers and the timer free themselves on every return path)
-    DevBuf<uint8_t> plane;
-    DevBuf<long long> seeds;
-    DevBuf<unsigned long long> flag;
-    DevTimer<2> tm;
-    hipStream_t stream = nullptr;
-    ~Scratch() {
-      if (stream) (void)hipStreamDestroy(stream);
-    }
-  } s;
-  int rc;
-  if ((rc = s.plane.ensure((size_t)(n * row))) || (rc = s.flag.ensure(1 + (size_t)gorand::kDelayGenFlagCap))) return rc;
-  if (seeds) {
-    if ((rc = s.seeds.ensure((size_t)n))) return rc;
-    HIP_TRY(hipMemcpy(s.seeds.p, seeds, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
-  }
-  HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-  DeviceGen g;
-  if ((rc = device_generate(device, s.stream, prop.multiProcessorCount, seed_base, seeds ? s.seeds.p : nullptr, n, row,
-                            draws, s.plane.p, s.flag.p, &s.tm, &g)))
-    return rc;
-  if (g.overflow) {  // more flagged rows than the list holds: the host generator, as in the engine
-    go_schedule(seed_base, seeds, n, draws, out);
-    return CL_OK;
-  }
-  HIP_TRY(hipMemcpy2D(out, (size_t)draws, s.plane.p, (size_t)row, (size_t)draws, (size_t)n, hipMemcpyDeviceToHost));
-  if (patched_rows) *patched_rows = g.patched;
-  if (device_ms) *device_ms = g.device_ms;
-  return CL_OK;
-}
-
-int cl_go_int63(int64_t seed, int64_t n, int64_t* out) {
-  if (!out || n < 0) return set_err(CL_E_INVALID, "bad arguments");
-  GoRand r(seed);
-  for (int64_t i = 0; i < n; ++i) out[i] = r.int63();
-  return CL_OK;
-}
-
-int cl_go_intn(int64_t seed, int32_t bound, int64_t n, int32_t* out) {
-  if (!out || n < 0 || bound <= 0) return set_err(CL_E_INVALID, "bad arguments");
-  GoRand r(seed);
-  for (int64_t i = 0; i < n; ++i) out[i] = r.int31n(bound);
   return CL_OK;
 }
 
