@@ -1,5 +1,5 @@
 // cg_engine.h -- data layout shared by the graph engine's host runtime (cg_host.cpp)
-// and its gfx950 kernels (cg_kernels.hip, cg_table.hip, cg_sparse.hip, cg_wave.hip, cg_restore.hip).  DESIGN.md §10 draws the same layout.
+// and its gfx950 kernels (cg_kernels.hip, cg_table.hip, cg_sparse.hip, cg_wave.hip, cg_profile.hip, cg_restore.hip).  DESIGN.md §10 draws the same layout.
 //
 // The graph engine runs ONE reference simulation over a large topology (BASELINE
 // configs 4 and 5: 2^20-node regular digraph, 100k-node power-law graph with 4,096
@@ -384,5 +384,37 @@ int cg_launch_wave(const GParams& p, int32_t sid_lo, int32_t n_rows, int32_t rw,
 int cg_launch_wave_link(const GParams& p, int32_t sid_lo, int32_t n_rows, unsigned long long* pairs, void* stream);
 int cg_launch_wave_jump(const GParams& p, int32_t n_rows, unsigned long long* pairs, int32_t* changed, void* stream);
 int cg_launch_wave_pack(const GParams& p, int32_t sid_lo, int32_t n_rows, int32_t* parent, int32_t* tick, void* stream);
+// Node and channel profile over the used snapshots of sid_lo + [0, ns) (cg_profile.hip; clgraph.h
+// cl_graph_snapshot_profile draws the head, the node rows and the entries).  The scratch of a call:
+struct GProfile {
+  int32_t* list;            // [ns] the used rows, ascending; head[CL_PF_N_USED] of them
+  int32_t* used;            // [ns] 1 / 0 per row
+  long long* org;           // [ns] the origin of every row
+  long long* head;          // [CL_PF_HEAD + msg_bins]
+  unsigned long long* acc;  // [4][k_hi - k_lo] per owned in-position: msgs, tokens, (peak << 32 | ~row), snaps
+  long long* rows;          // [(part_hi - part_lo) * kProfileNodeWords] the node rows (the node pass only)
+  unsigned long long* tiles;  // [cg_profile_tiles(e)] entries of the channel tiles before each tile
+};
+constexpr int32_t kProfileNodeWords = 8;   // CL_PF_NODE_WORDS
+constexpr int32_t kProfileMaxBins = 1024;  // CL_GRAPH_PROFILE_MAX_BINS
+constexpr int32_t kProfileEntryBytes = 32;
+// The segmented sum of a node's in-channels (k_profile_in) by in-degree: up to kProfileLaneDeg the
+// node's own lane walks the range, up to kProfileWaveDeg a wave does, above it the workgroup.
+constexpr int32_t kProfileLaneDeg = 8;
+constexpr int32_t kProfileWaveDeg = 256;
+// profile_reduce: the used list (use[ns] or nullptr; org_in[ns] the origins with user != 0, else the
+// initiators' ranks), the channel pass over the in-positions [k_lo, k_hi) in `slices` slices of the
+// used list (0: automatic), then the head's sums, maxima and histogram and the tiles' entry
+// offsets with head[CL_PF_ENTRIES] their total.  profile_nodes: the node pass and the in-channel
+// sums into s.rows.  profile_fill: the entries (32 bytes each) in ascending channel order.  The
+// host fills the head words that need no device.  Any grid and any slice count give the same result.
+int32_t cg_profile_tiles(int64_t e);
+int cg_launch_profile_reduce(const GParams& p, int32_t k_lo, int32_t k_hi, int32_t sid_lo, int32_t ns,
+                             const int32_t* use, const long long* org_in, int32_t user, int32_t slices, int32_t min_msgs,
+                             int32_t bins, int32_t width, const GProfile& s, int32_t n_cus, void* stream);
+int cg_launch_profile_nodes(const GParams& p, int32_t k_lo, int32_t k_hi, int32_t sid_lo, int32_t ns, int32_t slices,
+                            const GProfile& s, int32_t n_cus, void* stream);
+int cg_launch_profile_fill(const GParams& p, int32_t k_lo, int32_t k_hi, int32_t sid_lo, int32_t min_msgs,
+                           const GProfile& s, void* entries, void* stream);
 
 }  // namespace clsnap

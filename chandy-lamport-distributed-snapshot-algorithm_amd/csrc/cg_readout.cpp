@@ -1,6 +1,6 @@
 // cg_readout.cpp -- the graph engine's device-side readouts behind include/clgraph.h: the per-snapshot
-// summary table (cg_table.hip), the sparse packed collect (cg_sparse.hip) and the marker-wave profile and
-// tree (cg_wave.hip).  Each is written against the view of a cl_graph that cg_host.h gives and owns what it allocates.
+// summary table (cg_table.hip), the sparse packed collect (cg_sparse.hip), the marker-wave profile and
+// tree (cg_wave.hip) and the node and channel profile over a snapshot range (cg_profile.hip).  Each is written against the view of a cl_graph that cg_host.h gives and owns what it allocates.
 #include <algorithm>
 #include <vector>
 
@@ -42,16 +42,29 @@ struct clsnap::Readouts {
   GraphTimer<2> wv;
   int32_t wv_rounds = 0;
   size_t wv_budget = kWaveScratchBytes;  // bytes of scratch per chunk of sids (cl_graph_set_wave_scratch)
+  // node and channel profile (cl_graph_snapshot_profile): the mask, the used list and the used flags
+  // ([3][ns]); the origins as given and as used ([2][ns]); the head and histogram; the accumulator
+  // planes of the owned in-positions; the node rows; the channel tiles' entry offsets; the entries;
+  // the events around the reduction ([0], [1]) and around the node pass and the fill ([2], [3]);
+  // done: the pairs of the latest call that completed
+  DevBuf<int32_t> d_pf_i32;
+  DevBuf<long long> d_pf_org, d_pf_head, d_pf_rows;
+  DevBuf<unsigned long long> d_pf_acc, d_pf_tiles;
+  DevBuf<cl_graph_profile_entry> d_pf_ent;
+  GraphTimer<4> pf;
+  int32_t pf_slices = 0;  // slices of the used list (cl_graph_set_profile_slices), 0: automatic
 };
 
 Readouts* clsnap::readouts_new() { return new Readouts(); }
 void clsnap::readouts_delete(Readouts* r) { delete r; }
 
 // What cl_graph_device_bytes counts of the readouts: the wave's pairs (or the tree's planes), rows
-// and origins.  Known gap: the table's rows, the whole sparse scratch and the wave's round flag are
-// not counted.
+// and origins, and the whole scratch of the range profile.  Known gap: the table's rows, the whole
+// sparse scratch and the wave's round flag are not counted.
 int64_t clsnap::readouts_device_bytes(const Readouts* r) {
-  return (int64_t)(r->d_wv_scratch.bytes() + r->d_wv_rows.bytes() + r->d_wv_org.bytes());
+  return (int64_t)(r->d_wv_scratch.bytes() + r->d_wv_rows.bytes() + r->d_wv_org.bytes() + r->d_pf_i32.bytes() +
+                   r->d_pf_org.bytes() + r->d_pf_head.bytes() + r->d_pf_rows.bytes() + r->d_pf_acc.bytes() +
+                   r->d_pf_tiles.bytes() + r->d_pf_ent.bytes());
 }
 
 extern "C" {
@@ -287,6 +300,121 @@ int cl_graph_sparse_time(cl_graph* g, double* ms) {
   double a = 0, b = 0;
   int rc = r->sp.ms(0, 1, &a);
   if (!rc && r->sp.done > 1) rc = r->sp.ms(2, 3, &b);
+  *ms = a + b;
+  return rc;
+}
+
+// ---- node and channel profile over a snapshot range (cg_profile.hip) -------------------------
+int cl_graph_set_profile_slices(cl_graph* g, int32_t slices) {
+  GRAPH_CALL(g);
+  if (slices < 0) return set_err(CL_E_INVALID, "negative slice count");
+  graph_readouts(g)->pf_slices = slices;
+  return CL_OK;
+}
+
+int cl_graph_snapshot_profile(cl_graph* g, int32_t sid_lo, int32_t sid_hi, const cl_graph_profile_spec* spec,
+                              const int32_t* use, const int64_t* origins, int64_t* head, int32_t* used,
+                              int64_t* node_rows, cl_graph_profile_entry* entries, int64_t ent_cap) {
+  GRAPH_CALL(g);
+  static_assert(sizeof(cl_graph_profile_spec) == 4 * sizeof(int32_t), "cl_graph_profile_spec is 4 x int32");
+  static_assert(sizeof(cl_graph_profile_entry) == kProfileEntryBytes, "cl_graph_profile_entry is 32 bytes");
+  static_assert(CL_PF_NODE_WORDS == kProfileNodeWords && CL_GRAPH_PROFILE_MAX_BINS == kProfileMaxBins, "cg_engine.h");
+  if (!spec || !head) return set_err(CL_E_INVALID, "null %s", !spec ? "spec" : "head");
+  if (spec->msg_bins < 1 || spec->msg_bins > CL_GRAPH_PROFILE_MAX_BINS || spec->msg_width < 1 || spec->min_msgs < 1 ||
+      spec->reserved)
+    return set_err(CL_E_INVALID, "profile spec: msg_bins %d (1..%d), msg_width %d (>= 1), min_msgs %d (>= 1), reserved %d",
+                spec->msg_bins, CL_GRAPH_PROFILE_MAX_BINS, spec->msg_width, spec->min_msgs, spec->reserved);
+  int rc = sid_range_ok(g, sid_lo, sid_hi);
+  if (rc) return rc;
+  if (ent_cap < 0) return set_err(CL_E_INVALID, "negative capacity");
+  if (ent_cap > 0 && !entries) return set_err(CL_E_INVALID, "null entries with ent_cap > 0");
+  const GraphFacts f = graph_facts(g);
+  if (f.part && node_rows && !origins)
+    return set_err(CL_E_STATE, "a partitioned run needs the origins: only the initiator's owner knows the start");
+  const int32_t ns = sid_hi - sid_lo, bins = spec->msg_bins;
+  const size_t head_words = (size_t)CL_PF_HEAD + (size_t)bins;
+  if (ns == 0) {
+    std::fill(head, head + head_words, 0);
+    head[CL_PF_NODE_LO] = f.node_lo;
+    head[CL_PF_NODE_HI] = f.node_hi;
+    return CL_OK;
+  }
+  GraphView v;
+  if ((rc = graph_view(g, &v))) return rc;
+  Readouts* r = graph_readouts(g);
+  const GParams& P = *v.P;
+  const size_t nsz = (size_t)ns, ke = (size_t)(v.k_hi - v.k_lo), width = (size_t)(P.part_hi - P.part_lo);
+  if ((rc = r->d_pf_i32.ensure(3 * nsz)) || (rc = r->d_pf_org.ensure(2 * nsz)) || (rc = r->d_pf_head.ensure(head_words)) ||
+      (rc = r->d_pf_acc.ensure(4 * ke)) || (rc = r->d_pf_tiles.ensure((size_t)cg_profile_tiles(P.e))))
+    return rc;
+  if (node_rows && (rc = r->d_pf_rows.ensure(width * (size_t)CL_PF_NODE_WORDS))) return rc;
+  int32_t* d_use = r->d_pf_i32.p;
+  long long* d_org_in = r->d_pf_org.p;
+  GProfile s{};
+  s.list = d_use + nsz;
+  s.used = d_use + 2 * nsz;
+  s.org = d_org_in + nsz;
+  s.head = r->d_pf_head.p;
+  s.acc = r->d_pf_acc.p;
+  s.rows = r->d_pf_rows.p;
+  s.tiles = r->d_pf_tiles.p;
+  // the mask, and the origins or the initiators' ranks
+  std::vector<long long> org(nsz);
+  if (origins) std::copy(origins, origins + ns, org.begin());
+  else graph_initiators(g, sid_lo, sid_hi, org.data());
+  if (use) HIP_TRY(hipMemcpyAsync(d_use, use, nsz * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+  HIP_TRY(hipMemcpyAsync(d_org_in, org.data(), nsz * sizeof(long long), hipMemcpyHostToDevice, v.stream));
+  HIP_TRY(hipStreamSynchronize(v.stream));  // (`org` is a local, `use` the caller's)
+  r->pf.done = 0;
+  if ((rc = r->pf.mark(0, v.stream))) return rc;
+  if ((rc = launch_err(cg_launch_profile_reduce(P, v.k_lo, v.k_hi, sid_lo, ns, use ? d_use : nullptr, d_org_in,
+                                                origins ? 1 : 0, r->pf_slices, spec->min_msgs, bins, spec->msg_width, s,
+                                                v.n_cus, v.stream))))
+    return rc;
+  if ((rc = r->pf.mark(1, v.stream))) return rc;
+  // the head decides the sizes: the host reads it between the reduction and the fill
+  std::vector<long long> h(head_words);
+  std::vector<int32_t> h_used(nsz);
+  HIP_TRY(hipMemcpyAsync(h.data(), s.head, head_words * sizeof(long long), hipMemcpyDeviceToHost, v.stream));
+  HIP_TRY(hipMemcpyAsync(h_used.data(), s.used, nsz * sizeof(int32_t), hipMemcpyDeviceToHost, v.stream));
+  HIP_TRY(hipStreamSynchronize(v.stream));
+  r->pf.done = 1;
+  h[CL_PF_N_SIDS] = ns;
+  h[CL_PF_NODE_LO] = f.node_lo;
+  h[CL_PF_NODE_HI] = f.node_hi;
+  h[CL_PF_CHANNELS] = (long long)ke;
+  h[CL_PF_UNIT_PAYLOADS] = v.hist == 0 ? 1 : 0;
+  std::copy(h.begin(), h.end(), head);
+  if (used) std::copy(h_used.begin(), h_used.end(), used);
+  const int64_t n_entries = h[CL_PF_ENTRIES];
+  if (n_entries > ent_cap)
+    return set_err(CL_E_LIMIT, "%lld entries exceed ent_cap %lld", (long long)n_entries, (long long)ent_cap);
+  if ((rc = r->d_pf_ent.ensure((size_t)n_entries))) return rc;
+  if ((rc = r->pf.mark(2, v.stream))) return rc;
+  if (node_rows && (rc = launch_err(cg_launch_profile_nodes(P, v.k_lo, v.k_hi, sid_lo, ns, r->pf_slices, s, v.n_cus, v.stream))))
+    return rc;
+  if (n_entries > 0 &&
+      (rc = launch_err(cg_launch_profile_fill(P, v.k_lo, v.k_hi, sid_lo, spec->min_msgs, s, r->d_pf_ent.p, v.stream))))
+    return rc;
+  if ((rc = r->pf.mark(3, v.stream))) return rc;
+  if (node_rows && width > 0)
+    HIP_TRY(hipMemcpyAsync(node_rows, s.rows, width * CL_PF_NODE_WORDS * sizeof(int64_t), hipMemcpyDeviceToHost, v.stream));
+  if (n_entries > 0)
+    HIP_TRY(hipMemcpyAsync(entries, r->d_pf_ent.p, (size_t)n_entries * sizeof(cl_graph_profile_entry),
+                           hipMemcpyDeviceToHost, v.stream));
+  HIP_TRY(hipStreamSynchronize(v.stream));
+  r->pf.done = 2;
+  return CL_OK;
+}
+
+int cl_graph_profile_time(cl_graph* g, double* ms) {
+  GRAPH_CALL(g);
+  if (!ms) return set_err(CL_E_INVALID, "null output");
+  const Readouts* r = graph_readouts(g);
+  if (!r->pf.done) return set_err(CL_E_STATE, "no snapshot profile has been computed");
+  double a = 0, b = 0;
+  int rc = r->pf.ms(0, 1, &a);
+  if (!rc && r->pf.done > 1) rc = r->pf.ms(2, 3, &b);
   *ms = a + b;
   return rc;
 }

@@ -97,6 +97,9 @@ def glib():
             "cl_graph_snapshot_tree": [vp, i32, i32, vp, vp],
             "cl_graph_collect_sparse": [vp, i32, i32, vp, vp, vp, vp, i64, vp, i64, vp, vp],
             "cl_graph_sparse_time": [vp, vp],
+            "cl_graph_snapshot_profile": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64],
+            "cl_graph_profile_time": [vp, vp],
+            "cl_graph_set_profile_slices": [vp, i32],
             "cl_graph_restore": [vp, i32, C.POINTER(C.c_void_p)],
             "cl_graph_seed_info_of": [vp, vp],
             "cl_graph_restore_time": [vp, vp, vp],
@@ -627,6 +630,144 @@ class SparseSnapshots:
                                parts[0].node_lo, parts[-1].node_hi)
 
 
+# cl_graph_snapshot_profile (include/clgraph.h): head word i is PROFILE_HEAD[i] (CL_PF_*), hist[msg_bins]
+# follows; one 32-byte entry per channel, one row of CL_PF_NODE_WORDS int64 per node.
+PROFILE_HEAD = ("n_sids", "n_used", "node_lo", "node_hi", "channels", "active", "entries", "msgs", "tokens",
+                "max_msgs", "max_peak", "max_snaps", "unit_payloads", "reserved13", "reserved14", "reserved15")
+PROFILE_MAX_BINS = 1024   # CL_GRAPH_PROFILE_MAX_BINS
+PROFILE_SPEC_DTYPE = np.dtype([(f, np.int32) for f in ("msg_bins", "msg_width", "min_msgs", "reserved")])
+PROFILE_ENTRY_DTYPE = np.dtype([("channel", np.int32), ("snaps", np.int32), ("peak", np.int32), ("peak_sid", np.int32),
+                                ("msgs", np.int64), ("tokens", np.int64)])
+PROFILE_NODE_FIELDS = ("tok_sum", "tok_sumsq", "tok_min", "tok_max", "lat_sum", "lat_max", "in_msgs", "in_tokens")
+PROFILE_NODE_DTYPE = np.dtype([(f, np.int64) for f in PROFILE_NODE_FIELDS])
+_PF = {f: i for i, f in enumerate(PROFILE_HEAD)}
+
+
+class SnapshotProfile:
+    """Node and channel profile of GraphSim.snapshot_profile, reduced on the device over the used
+    snapshots of a range -- the transposed view of the table, the wave and the sparse collect.
+
+      sid_lo    first snapshot id of the range; used int32[ns]: 1 where row r (sid_lo + r) was used
+                (the caller's mask and the snapshot's completion), n_used their count
+      head      int64[len(PROFILE_HEAD)], by name through word(name); hist int64[msg_bins]: owned
+                channels by min(msgs // msg_width, msg_bins - 1)
+      entries   PROFILE_ENTRY_DTYPE, one per owned channel with msgs >= min_msgs, ascending channel
+      node      PROFILE_NODE_DTYPE over the owned nodes [node_lo, node_hi), or None
+      origins   what the latencies were measured from: the caller's int64[ns], None for the
+                snapshots' start ticks"""
+
+    def __init__(self, sid_lo, used, head, hist, entries, node=None, origins=None, msg_width=1, min_msgs=1):
+        self.sid_lo = int(sid_lo)
+        self.used = np.ascontiguousarray(used, dtype=np.int32).reshape(-1)
+        self.head = np.ascontiguousarray(head, dtype=np.int64).reshape(-1)
+        if self.head.size != len(PROFILE_HEAD):
+            raise ValueError(f"a profile head has {len(PROFILE_HEAD)} words")
+        self.hist = np.ascontiguousarray(hist, dtype=np.int64).reshape(-1)
+        self.entries = np.ascontiguousarray(entries, dtype=PROFILE_ENTRY_DTYPE).reshape(-1)
+        self.node = None if node is None else np.ascontiguousarray(node, dtype=PROFILE_NODE_DTYPE).reshape(-1)
+        self.origins = None if origins is None else np.ascontiguousarray(origins, dtype=np.int64).reshape(-1)
+        self.msg_width, self.min_msgs = int(msg_width), int(min_msgs)
+
+    @property
+    def spec(self):
+        return self.hist.size, self.msg_width, self.min_msgs
+
+    def word(self, name):
+        """Head word `name` (PROFILE_HEAD)."""
+        return int(self.head[_PF[name]])
+
+    n_used = property(lambda self: self.word("n_used"))
+    node_lo = property(lambda self: self.word("node_lo"))
+    node_hi = property(lambda self: self.word("node_hi"))
+
+    def __len__(self):
+        return self.used.size
+
+    def _same_call(self, other):
+        """The same range, spec, used rows and origins."""
+        return (self.sid_lo == other.sid_lo and self.spec == other.spec and np.array_equal(self.used, other.used)
+                and (self.origins is None) == (other.origins is None)
+                and (self.origins is None or np.array_equal(self.origins, other.origins)))
+
+    def __eq__(self, other):
+        return (isinstance(other, SnapshotProfile) and self._same_call(other)
+                and np.array_equal(self.head, other.head) and np.array_equal(self.hist, other.hist)
+                and np.array_equal(self.entries, other.entries) and (self.node is None) == (other.node is None)
+                and (self.node is None or np.array_equal(self.node, other.node)))
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"SnapshotProfile(sids {self.sid_lo}..{self.sid_lo + len(self)}, {self.n_used} used, " \
+               f"nodes {self.node_lo}..{self.node_hi}, {self.entries.size} entries)"
+
+    def _node_mean(self, field):
+        if self.node is None:
+            raise ValueError("the profile was taken without node rows")
+        a = self.node[field].astype(np.float64)
+        return a / self.n_used if self.n_used > 0 else np.full(a.shape, np.nan)
+
+    def mean_tokens(self):
+        """Mean recorded balance of every owned node over the used snapshots; nan with none used."""
+        return self._node_mean("tok_sum")
+
+    def var_tokens(self):
+        """Population variance of every owned node's recorded balance over the used snapshots (how
+        much it swings from cut to cut); nan with none used."""
+        return self._node_mean("tok_sumsq") - self.mean_tokens() ** 2
+
+    def mean_latency(self):
+        """Mean creation tick - origin of every owned node over the used snapshots; nan with none used."""
+        return self._node_mean("lat_sum")
+
+    def hottest(self, k):
+        """The entries of the k largest msgs, ties by lower channel."""
+        e = self.entries
+        return e[np.lexsort((e["channel"], -e["msgs"]))[:max(int(k), 0)]]
+
+    def by_receiver(self, dst):
+        """The entries summed by receiving node: a structured array over the owned nodes (node,
+        channels, msgs, tokens); dst[c] = destination rank of channel c (GraphSim.channels())."""
+        lo, hi = self.node_lo, self.node_hi
+        v = np.asarray(dst, dtype=np.int64)[self.entries["channel"]] - lo
+        out = np.zeros(hi - lo, dtype=[(f, np.int64) for f in ("node", "channels", "msgs", "tokens")])
+        out["node"] = np.arange(lo, hi)
+        out["channels"] = np.bincount(v, minlength=hi - lo)
+        np.add.at(out["msgs"], v, self.entries["msgs"])
+        np.add.at(out["tokens"], v, self.entries["tokens"])
+        return out
+
+    @staticmethod
+    def merge(parts):
+        """The profile of a partitioned run from its parts', in rank order (contiguous node ranges,
+        so every channel belongs to exactly one part): node rows are concatenated, entries merged by
+        ascending channel; hist and the head's counts add, its maxima take the maximum.  ValueError
+        on differing range, spec, used rows or origins, or on node ranges that do not abut."""
+        parts = list(parts)
+        if not parts:
+            raise ValueError("merge needs at least one part")
+        first = parts[0]
+        for a, b in zip(parts, parts[1:]):
+            if not isinstance(b, SnapshotProfile) or not first._same_call(b) or len(first) != len(b):
+                raise ValueError("merge needs parts of the same range, spec, used rows and origins")
+            if b.node_lo != a.node_hi:
+                raise ValueError("merge needs parts of adjacent node ranges, in rank order")
+        head = first.head.copy()
+        for f in ("channels", "active", "entries", "msgs", "tokens"):
+            head[_PF[f]] = sum(p.word(f) for p in parts)
+        for f in ("max_msgs", "max_peak", "max_snaps"):
+            head[_PF[f]] = max(p.word(f) for p in parts)
+        head[_PF["unit_payloads"]] = min(p.word("unit_payloads") for p in parts)
+        head[_PF["node_hi"]] = parts[-1].node_hi
+        entries = np.concatenate([p.entries for p in parts])
+        entries = entries[np.argsort(entries["channel"], kind="stable")]
+        node = None
+        if all(p.node is not None for p in parts):
+            node = np.concatenate([p.node for p in parts])
+        return SnapshotProfile(first.sid_lo, first.used, head, sum(p.hist for p in parts), entries, node, first.origins,
+                               first.msg_width, first.min_msgs)
+
+
 def _ids_array(sim):
     """sim.node_ids() as a numpy S array (kept on the sim: the ids of a graph never change)."""
     a = getattr(sim, "_ids_s", None)
@@ -1134,6 +1275,67 @@ class GraphSim:
         """Device ms of the latest collect_sparse call's kernels (HIP events)."""
         return self._get(self._L.cl_graph_sparse_time, C.c_double)
 
+    def _snapshot_profile(self, sid_lo, sid_hi, spec, use=None, origins=None, head=None, used=None, node_rows=None,
+                          entries=None, ent_cap=0):
+        """One cl_graph_snapshot_profile call: the return code."""
+        ptr = lambda a: None if a is None else _p(a)  # noqa: E731
+        return self._L.cl_graph_snapshot_profile(self._h, sid_lo, sid_hi, ptr(spec), ptr(use), ptr(origins), ptr(head),
+                                                 ptr(used), ptr(node_rows), ptr(entries), ent_cap)
+
+    def snapshot_profile(self, sid_lo=0, sid_hi=None, use=None, nodes=True, min_msgs=1, msg_bins=64, msg_width=1,
+                         origins=None, max_entries=1 << 16):
+        """SnapshotProfile of the snapshots [sid_lo, sid_hi) (default: all), reduced on the device
+        over the used ones (cl_graph_snapshot_profile): per channel the recorded messages, their
+        payloads, the snapshots with one and the peak with its sid; per node (nodes=True) the
+        moments of its recorded balance and of its creation latency.  use (one flag per snapshot)
+        masks the range, e.g. from the table; incomplete snapshots are never used.  Channels with
+        msgs >= min_msgs come back as entries: the call is made with max_entries capacity and once
+        more with the exact size if they do not fit.  origins (one tick per snapshot) replaces
+        the start ticks; a part of a partitioned run needs it with nodes=True."""
+        if sid_hi is None:
+            sid_hi = self.num_snapshots
+        ns = max(sid_hi - sid_lo, 0)
+        spec = np.zeros(1, dtype=PROFILE_SPEC_DTYPE)
+        spec["msg_bins"], spec["msg_width"], spec["min_msgs"] = msg_bins, msg_width, min_msgs
+        nb = min(max(int(msg_bins), 0), PROFILE_MAX_BINS)
+        head = np.zeros(len(PROFILE_HEAD) + nb, dtype=np.int64)
+        used = np.zeros(ns + 1, dtype=np.int32)                                # (never an empty buffer)
+        mask = org = None
+        if use is not None:
+            mask = (np.asarray(use).reshape(-1) != 0).astype(np.int32)
+            if mask.size != ns:
+                raise ValueError(f"{mask.size} use flags for {ns} snapshots")
+            mask = np.concatenate([mask, np.zeros(1, dtype=np.int32)])
+        if origins is not None:
+            org = np.ascontiguousarray(origins, dtype=np.int64).reshape(-1)
+            if org.size != ns:
+                raise ValueError(f"{org.size} origins for {ns} snapshots")
+            org = np.concatenate([org, np.zeros(1, dtype=np.int64)])
+        rows = np.zeros(max(self.num_nodes, 1), dtype=PROFILE_NODE_DTYPE) if nodes else None
+        cap = max(int(max_entries), 0)
+        entries = np.zeros(max(cap, 1), dtype=PROFILE_ENTRY_DTYPE)
+        rc = self._snapshot_profile(sid_lo, sid_hi, spec, mask, org, head, used, rows, entries, cap)
+        if rc == E_LIMIT:                                                      # the head is written: the exact size
+            cap = int(head[_PF["entries"]])
+            entries = np.zeros(max(cap, 1), dtype=PROFILE_ENTRY_DTYPE)
+            rc = self._snapshot_profile(sid_lo, sid_hi, spec, mask, org, head, used, rows, entries, cap)
+        _check(rc)
+        width = int(head[_PF["node_hi"]] - head[_PF["node_lo"]])
+        if nodes and ns == 0:                                                  # (nothing ran: the identities)
+            rows[:] = (0, 0, np.iinfo(np.int64).max, np.iinfo(np.int64).min, 0, np.iinfo(np.int64).min, 0, 0)
+        return SnapshotProfile(sid_lo, used[:ns], head[:len(PROFILE_HEAD)], head[len(PROFILE_HEAD):],
+                               entries[:int(head[_PF["entries"]])], rows[:width] if nodes else None,
+                               None if org is None else org[:ns], msg_width, min_msgs)
+
+    def profile_time(self):
+        """Device ms of the latest snapshot_profile call's kernels (HIP events)."""
+        return self._get(self._L.cl_graph_profile_time, C.c_double)
+
+    def set_profile_slices(self, slices=0):
+        """Slices of the used snapshots the profile's passes run in (0: automatic).  The results
+        do not depend on it."""
+        _check(self._L.cl_graph_set_profile_slices(self._h, slices))
+
     # ---- restore: a run that begins in a recorded cut (cl_graph_restore) ----------------
     def restore(self, sid):
         """A new, independent GraphSim whose time-0 state is the completed snapshot sid of this
@@ -1542,6 +1744,28 @@ class PartitionedGraphSim:
         allp = [None] * self.world
         dist.all_gather_object(allp, tuple(getattr(mine, f) for f in fields))
         return SparseSnapshots.merge([SparseSnapshots(*p) for p in allp])
+
+    def snapshot_profile(self, sid_lo=0, sid_hi=None, use=None, nodes=True, min_msgs=1, msg_bins=64, msg_width=1,
+                         max_entries=1 << 16, parts=False):
+        """The whole run's SnapshotProfile on every rank (a collective): the used snapshots are the
+        caller's mask AND the completion of the merged snapshot_table, the origins its start ticks;
+        each part profiles its own nodes and the channels into them, and the parts are gathered and
+        merged (SnapshotProfile.merge).  parts=True: (merged, [the parts in rank order])."""
+        import torch.distributed as dist
+        if sid_hi is None:
+            sid_hi = self.n_sids
+        rows = self.snapshot_table().rows[sid_lo:sid_hi]
+        mask = rows["complete_tick"] >= 0
+        if use is not None:
+            mask = mask & (np.asarray(use).reshape(-1) != 0)
+        mine = self.g.snapshot_profile(sid_lo, sid_hi, mask, nodes, min_msgs, msg_bins, msg_width, rows["start_tick"],
+                                       max_entries)
+        fields = ("sid_lo", "used", "head", "hist", "entries", "node", "origins", "msg_width", "min_msgs")
+        allp = [None] * self.world
+        dist.all_gather_object(allp, tuple(getattr(mine, f) for f in fields))
+        got = [SnapshotProfile(*p) for p in allp]
+        merged = SnapshotProfile.merge(got)
+        return (merged, got) if parts else merged
 
     # ---- restore: a partitioned run that begins in a recorded cut (cl_graph_part_begin_seeded) ----
     def cut(self, sid, topology=False):

@@ -297,6 +297,85 @@ int cl_graph_collect_sparse(cl_graph* g, int32_t sid_lo, int32_t sid_hi,
 /* Device ms of the latest sparse collect's kernels (HIP events on the engine's stream). */
 int cl_graph_sparse_time(cl_graph* g, double* ms);
 
+/* ---- node and channel profile over a snapshot range, reduced on the device ---------
+ * The table, the wave and the sparse collect give one row per snapshot id.  This call reduces
+ * the other way, over the USED snapshots of [sid_lo, sid_hi): one record per channel into an
+ * owned node and one row per owned node.  ns = sid_hi - sid_lo; row r (snapshot sid_lo + r) is
+ * used iff (use == NULL or use[r] != 0) and the snapshot has completed on this device -- the
+ * cursors of an incomplete snapshot are undefined and are never read.  used[r] = 1 / 0,
+ * CL_PF_N_USED their count.
+ *
+ * Per owned channel c over the used rows, with k_r(c) the messages snapshot r recorded on it and
+ * t_r(c) their token payloads (k_r(c) where the run keeps no payload history): msgs = sum k_r,
+ * tokens = sum t_r, snaps = #{r : k_r > 0}, peak = max k_r, peak_sid = the lowest sid with
+ * k_r == peak (-1 where msgs == 0).  hist[b] counts the owned channels with b == min(msgs /
+ * msg_width, msg_bins - 1): channels without a message fall in bin 0, and the bins sum to
+ * CL_PF_CHANNELS.  `entries` gets one record for every owned channel with msgs >= min_msgs, in
+ * ascending channel index.
+ *
+ * Per owned node v over the used rows (a used snapshot is complete, so v holds a local snapshot
+ * of it), CL_PF_NODE_WORDS int64: tok_sum, tok_sumsq (modulo 2^64), tok_min, tok_max of the
+ * recorded node tokens; lat_sum, lat_max of creation tick - origin[r], signed; in_msgs,
+ * in_tokens = msgs and tokens summed over the channels into v.  With no used row a node row is
+ * 0, 0, INT64_MAX, INT64_MIN, 0, INT64_MIN, 0, 0.  origins == NULL: the origin of a row is the
+ * creation tick of its initiator's record, the table's start_tick; an origins array gives the
+ * origin of every row, whatever its sign.
+ *
+ * Errors, all before any device work and with every output untouched: CL_E_INVALID on a NULL g,
+ * spec or head, msg_bins outside [1, CL_GRAPH_PROFILE_MAX_BINS], msg_width < 1, min_msgs < 1, a
+ * non-zero reserved, a range outside 0 <= sid_lo <= sid_hi <= num_snapshots, a negative ent_cap,
+ * or NULL entries with ent_cap > 0; CL_E_STATE in a partitioned run with node_rows != NULL and
+ * origins == NULL (only the initiator's owner knows the start: pass the merged table's
+ * start_tick).  An empty range returns CL_OK and launches nothing; the head is zeroed but for
+ * CL_PF_NODE_LO / CL_PF_NODE_HI.
+ *
+ * Sizing: head, hist and used are written whenever the reduction has run.  If CL_PF_ENTRIES >
+ * ent_cap the call returns CL_E_LIMIT and leaves entries and node_rows untouched (ent_cap == 0
+ * with NULL entries is the sizing call).  Nothing is cached between calls: a sizing call costs
+ * one reduction.  Everything is an exact integer and a pure function of the run, the range, the
+ * mask, the origins and the spec; nothing depends on the grid or on
+ * cl_graph_set_profile_slices.  Partitioned runs: this device's part -- its nodes and the
+ * channels into them (graph.py SnapshotProfile.merge joins the parts).  The scratch, 32 B per
+ * owned in-position and 64 B per owned node, is counted in cl_graph_device_bytes. */
+#define CL_GRAPH_PROFILE_MAX_BINS 1024
+typedef struct { int32_t msg_bins, msg_width, min_msgs, reserved; } cl_graph_profile_spec;   /* 16 B */
+typedef struct cl_graph_profile_entry {   /* 32 B */
+  int32_t channel;    /* channel index of cl_graph_channels */
+  int32_t snaps;      /* used snapshots with at least one recorded message on it */
+  int32_t peak;       /* most messages one used snapshot recorded on it */
+  int32_t peak_sid;   /* the lowest sid that recorded `peak` */
+  int64_t msgs;       /* recorded messages over the used snapshots */
+  int64_t tokens;     /* their token payloads (== msgs with unit payloads) */
+} cl_graph_profile_entry;
+/* head words, then hist[msg_bins] */
+#define CL_PF_N_SIDS 0
+#define CL_PF_N_USED 1
+#define CL_PF_NODE_LO 2
+#define CL_PF_NODE_HI 3
+#define CL_PF_CHANNELS 4      /* owned channels: those into the owned nodes */
+#define CL_PF_ACTIVE 5        /* owned channels with msgs > 0 */
+#define CL_PF_ENTRIES 6       /* owned channels with msgs >= min_msgs */
+#define CL_PF_MSGS 7
+#define CL_PF_TOKENS 8
+#define CL_PF_MAX_MSGS 9      /* largest msgs of one channel; 0 if none */
+#define CL_PF_MAX_PEAK 10
+#define CL_PF_MAX_SNAPS 11
+#define CL_PF_UNIT_PAYLOADS 12
+#define CL_PF_HEAD 16         /* words 13..15 reserved, 0 */
+#define CL_PF_NODE_WORDS 8    /* tok_sum, tok_sumsq, tok_min, tok_max, lat_sum, lat_max, in_msgs, in_tokens */
+int cl_graph_snapshot_profile(cl_graph* g, int32_t sid_lo, int32_t sid_hi, const cl_graph_profile_spec* spec,
+                              const int32_t* use /* [ns] or NULL */, const int64_t* origins /* [ns] or NULL */,
+                              int64_t* head /* [CL_PF_HEAD + msg_bins] */,
+                              int32_t* used /* [ns] or NULL */,
+                              int64_t* node_rows /* [(node_hi - node_lo) * CL_PF_NODE_WORDS] or NULL */,
+                              cl_graph_profile_entry* entries, int64_t ent_cap);
+/* Device ms of the latest profile call's kernels (HIP events on the engine's stream).
+ * CL_E_STATE before any profile call. */
+int cl_graph_profile_time(cl_graph* g, double* ms);
+/* Slices of the used list the channel and node passes run in (0 = automatic; 1 = plain stores, no
+ * atomics).  The results do not depend on it. */
+int cl_graph_set_profile_slices(cl_graph* g, int32_t slices);
+
 /* ---- restore: a new run that begins in a recorded cut, seeded on the device ---------
  * g: an unpartitioned graph whose run has status CL_INST_OK; sid: one of its completed
  * snapshots, with tokenMap T[v] and recorded messages m[c][0..k_c) per channel c in delivery
