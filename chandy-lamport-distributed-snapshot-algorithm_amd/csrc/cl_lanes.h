@@ -118,6 +118,22 @@ struct Lds {
 __device__ __forceinline__ uint32_t due16(uint32_t e, int32_t time) {
   return (((((uint32_t)time - e) & 0xffu)) - 251u) >> 31;
 }
+// Two 16-bit values in the halves of a register, for the packed 16-bit VALU (v_pk_*_u16).
+typedef uint16_t us2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ us2 as_us2(uint32_t v) { return __builtin_bit_cast(us2, v); }
+__device__ __forceinline__ uint32_t as_u32(us2 v) { return __builtin_bit_cast(uint32_t, v); }
+// due16 of two entries against the time's low 16 bits in both halves of t2: 1 or 0 per half
+__device__ __forceinline__ uint32_t due16x2(uint32_t e2, us2 t2) {
+  const us2 d = as_us2(as_u32(t2 - as_us2(e2)) & 0x00ff00ffu) - (us2)(251);
+  return as_u32(d >> (us2)(15));
+}
+// min(half, 1) per half: a count's non-empty flag in one instruction (the compiler takes a min
+// on a 16-bit pair apart into compares, selects and a v_perm_b32)
+__device__ __forceinline__ uint32_t pk_min1(uint32_t c2) {
+  uint32_t r;
+  asm("v_pk_min_u16 %0, %1, 1 op_sel_hi:[1,0]" : "=v"(r) : "v"(c2));
+  return r;
+}
 // the node-parallel kernel's 32-bit entry (state image, HBM spill rings) and back
 __device__ __forceinline__ uint32_t e16_to_32(uint32_t e, int32_t time) {
   const uint32_t rt = (uint32_t)time + 5u - (((uint32_t)time + 5u - e) & 0xffu);
@@ -238,10 +254,58 @@ __device__ __forceinline__ void sfor(F&& f) {
   }
 }
 
+// Senders in pairs.  Everything phase A does to an out-link works on 16-bit data -- a FIFO entry,
+// a head word, 0/1 flags -- and gfx950 runs packed 16-bit integer VALU at full rate, so two senders
+// share every instruction of the scan: the low halves of the registers are one sender's, the
+// high halves the other's.  The senders are sorted by out-degree (descending, ties by rank) and
+// neighbours paired, so a pair's degrees differ as little as possible; with an odd N the last
+// sender's partner half is inert, and so is the half of a link slot past its sender's out-degree:
+// its head half stays 0 (never non-empty, so never looked at, due or popped) and its entry half
+// is 0.
+template <class T>
+struct Pairs {
+  static constexpr int NP = (T::N + 1) / 2;
+  struct Tab {
+    int snd[NP][2];  // pair p's senders: low half, high half (-1: inert)
+    int pr[T::N], hf[T::N];
+  };
+  static constexpr Tab make() {
+    Tab t{};
+    int ord[T::N] = {};
+    for (int v = 0; v < T::N; ++v) {  // insertion sort, stable
+      int i = v;
+      for (; i > 0 && T::od(ord[i - 1]) < T::od(v); --i) ord[i] = ord[i - 1];
+      ord[i] = v;
+    }
+    for (int p = 0; p < NP; ++p)
+      for (int h = 0; h < 2; ++h) {
+        const int v = 2 * p + h < T::N ? ord[2 * p + h] : -1;
+        t.snd[p][h] = v;
+        if (v >= 0) {
+          t.pr[v] = p;
+          t.hf[v] = h;
+        }
+      }
+    return t;
+  }
+  static constexpr Tab tab = make();
+  static constexpr int snd(int p, int h) { return tab.snd[p][h]; }
+  static constexpr int pr(int v) { return tab.pr[v]; }         // node v's pair
+  static constexpr uint32_t sh(int v) { return 16u * (uint32_t)tab.hf[v]; }  // ... and its half's shift
+  static constexpr int od(int p, int h) { return tab.snd[p][h] < 0 ? 0 : T::od(tab.snd[p][h]); }
+  static constexpr int nk(int p) { return od(p, 0) > od(p, 1) ? od(p, 0) : od(p, 1); }  // link slots
+  // the halves of pair p's link slot k that hold a link: 1 per half
+  static constexpr uint32_t present(int p, int k) { return (k < od(p, 0) ? 1u : 0u) | (k < od(p, 1) ? 0x10000u : 0u); }
+};
+
 // State of one instance.
-//   hw[v][k]  out-link k of node v: bits 6..0 queued packets (LDS ring + HBM spill; the host
-//             admits a program only when no channel ever carries more than 127 packets), bits
-//             7.. the ring head as a free-running counter (hw & CAPM7 = the head slot * 128)
+//   hw[p][k]  link slot k of sender pair p (Pairs): the low half is the first sender's out-link
+//             k, the high half the second's.  Per half: bits 6..0 queued packets (LDS ring + HBM
+//             spill; the host admits a program only when no channel ever carries more than 127
+//             packets), bits 15..7 the ring head as a free-running 9-bit counter (the ring sizes
+//             divide 512, so half & CAPM7 = the head slot * 128 across a wrap).  Pop is + 0x7f per
+//             half, push + 1 per half; the pop is a packed add, so a wrapping head counter does
+//             not carry into the high half's count
 //   cr[v][.]  in-link j's recording cursor (token packets delivered on the channel): u16 j & 1
 //             of word j >> 1
 //   pd[v][w]  per snapshot sid (w = sid >> 3) a nibble at 4 * (sid & 7): 0 not started,
@@ -251,7 +315,7 @@ __device__ __forceinline__ void sfor(F&& f) {
 template <class T>
 struct State {
   int32_t tok[T::N];
-  uint32_t hw[T::N][T::D];
+  uint32_t hw[Pairs<T>::NP][T::D];
   uint32_t cr[T::N][(T::D + 1) / 2];
   uint32_t pd[T::N][T::SW];
   uint32_t done[T::SW];
@@ -260,6 +324,11 @@ struct State {
   bool alive;
 };
 
+// out-link k of node v: its 16-bit head word
+template <class T>
+__device__ __forceinline__ uint32_t hw_get(const State<T>& s, int v, int k) {
+  return (s.hw[Pairs<T>::pr(v)][k] >> Pairs<T>::sh(v)) & 0xffffu;
+}
 template <class T>
 __device__ __forceinline__ uint32_t cur_get(const State<T>& s, int v, int j) {
   return (s.cr[v][j >> 1] >> ((j & 1) * 16)) & 0xffffu;
@@ -287,18 +356,22 @@ __device__ __forceinline__ void pd_set(State<T>& s, int v, uint32_t sid, uint32_
 // or, when the push does not land in the ring, to the lane's scratch word.  SPILL: a full LDS
 // ring spills to the HBM ring under a rare branch.  Failures follow the node-parallel kernel:
 // delay exhaustion, then overflow; the node's last failing push sets nf.
+// hw is the pair's register and sh the channel's half (0 or 16; a caller that extracted the half
+// passes 0): the low half needs no extraction, bits 15..7 of h + (h << 7) depend on it alone.
 template <class T, bool SPILL>
-__device__ __forceinline__ void push(const Ctx& x, uint32_t& hw, uint32_t ch, bool on, uint32_t pl16, int32_t kd,
-                                     uint32_t delay, int32_t time, int32_t& nf) {
+__device__ __forceinline__ void push(const Ctx& x, uint32_t& hw, uint32_t sh, uint32_t ch, bool on, uint32_t pl16,
+                                     int32_t kd, uint32_t delay, int32_t time, int32_t& nf) {
   using Ld = Lds<T>;
-  const uint32_t cnt = hw & 0x7fu;
+  static_assert(T::CAPL <= 9, "a ring's head slot must fit the half's 9-bit head counter");
+  const uint32_t h = hw >> sh;
+  const uint32_t cnt = h & 0x7fu;
   const bool dly_ok = kd < x.draws;
   const bool live = on && dly_ok;
   bool ok = live && cnt < Ld::CAP;
   const uint32_t rt = (uint32_t)(time + 1 + (int32_t)delay);
   const uint32_t e = pl16 | (rt & 0xffu);
   // the ring slot (head + count) mod ring slots, its byte address, or the scratch word
-  const uint32_t slot = (x.lb2 | ((hw + (hw << 7)) & Ld::CAPM7)) + (ch << (T::CAPL + 7));
+  const uint32_t slot = (x.lb2 | ((h + (h << 7)) & Ld::CAPM7)) + (ch << (T::CAPL + 7));
   *lds16_at(ok ? slot : x.lb + (Ld::DUMMY << 8)) = (uint16_t)e;
   if constexpr (SPILL) {
     if (__builtin_expect(live && cnt >= Ld::CAP, 0)) {  // LDS ring full: the HBM spill ring
@@ -325,7 +398,7 @@ __device__ __forceinline__ void push(const Ctx& x, uint32_t& hw, uint32_t ch, bo
       if (p->spill_flag) p->spill_flag[x.inst] = 1;
     }
   }
-  hw += ok ? 1u : 0u;  // (the push count is derived at the epilogue: pops + packets still queued)
+  hw += ok ? 1u << sh : 0u;  // (the push count is derived at the epilogue: pops + packets still queued)
   nf = (on && !ok) ? (dly_ok ? (int32_t)ST_FIFO_OVERFLOW : (int32_t)ST_DELAY_EXHAUSTED) : nf;
 }
 
@@ -333,7 +406,8 @@ __device__ __forceinline__ void push(const Ctx& x, uint32_t& hw, uint32_t ch, bo
 // almost every trigger: does the row still hold this draw, and is the ring full.  Both can be
 // asked once per trigger: is the broadcast's last draw past the row (k0 + od > draws), and does
 // the OR of the node's out-link head words have a bit of FULL, the count bits at or above the
-// ring's slots (a power of two: some count >= CAP).  On the deep-ring kernel the bound is the
+// ring's slots (a power of two: some count >= CAP), masked to the node's own half of its pair's
+// registers.  On the deep-ring kernel the bound is the
 // layout's ring, so the probe's flag store stays in push().
 template <class T>
 struct Guard {
@@ -347,10 +421,11 @@ struct Guard {
 // trigger is off stores nothing (a select against the scratch word per link, as push() has it,
 // compiled to 44 more VALU in the tick and 168 VGPRs), with the channel's constant
 // ch << (CAPL + 7) in the DS instruction's immediate offset as in phase A's read, and add the
-// trigger as a 0/1 integer to the head word.
+// trigger as a 0/1 integer to the head word's half.  (sh as in push(): one shift for a high half.)
 template <class T>
-__device__ __forceinline__ uint32_t sure_slot(const Ctx& x, uint32_t hw) {
-  return x.lb2 | ((hw + (hw << 7)) & Lds<T>::CAPM7);
+__device__ __forceinline__ uint32_t sure_slot(const Ctx& x, uint32_t hw, uint32_t sh) {
+  const uint32_t h = hw >> sh;
+  return x.lb2 | ((h + (h << 7)) & Lds<T>::CAPM7);
 }
 __device__ __forceinline__ uint32_t sure_entry(uint32_t pl16, uint32_t delay, int32_t time) {
   return pl16 | ((uint32_t)(time + 1 + (int32_t)delay) & 0xffu);
@@ -398,65 +473,96 @@ template <class T, bool SPILL>
 __device__ __forceinline__ bool tick(const Ctx& x, State<T>& s, bool act) {
   constexpr int N = T::N, D = T::D;
   s.time += act ? 1 : 0;
-  // ---- A: pick ------------------------------------------------------------------------
-  // every head first (independent LDS reads), then the scan
-  uint32_t e[N][D];
+  // ---- A: pick, two senders per instruction (Pairs) ---------------------------------------
+  // every head first (independent LDS reads: a pair's two entries into the halves of one
+  // register), then the scan
+  using Pr = Pairs<T>;
+  constexpr int NP = Pr::NP;
+  uint32_t e[NP][D];
 #pragma unroll
-  for (int v = 0; v < N; ++v)
-#pragma unroll
-    for (int k = 0; k < D; ++k)
-      if (k < T::od(v))
-        e[v][k] = lds16_at(x.lb2 | (s.hw[v][k] & Lds<T>::CAPM7))[(T::off(v) + k) << (T::CAPL + 6)];
-  uint32_t pk[N];  // sender v's pick: (out-index + 1) << 16 | the 16-bit entry (0: nothing)
-  uint32_t es[N];  // sender v's out-links that were empty when it scanned them
-  // 0/1 integers in VGPRs, kept opaque: as compare masks the compiler would keep every
-  // channel's masks live in SGPR pairs across the phase (and spill them to VGPR lanes)
-#pragma unroll
-  for (int v = 0; v < N; ++v) {
-    pk[v] = 0;
-    es[v] = 0;
-    uint32_t sc = opaque(act ? 1u : 0u);  // still scanning
+  for (int p = 0; p < NP; ++p)
 #pragma unroll
     for (int k = 0; k < D; ++k) {
-      if (k >= T::od(v)) continue;
-      const uint32_t w = s.hw[v][k];
-      uint32_t ne;  // queue non-empty: one v_min (the compiler's 0/1 from a compare is two)
-      asm("v_min_u32 %0, %1, 1" : "=v"(ne) : "v"(w & 0x7fu));
-      const uint32_t le = opaque(due16(e[v][k], s.time));  // receiveTime <= time
-      const uint32_t lk = sc & ne;  // Peek (sim.go:83)
-      s.peek += lk;
-      es[v] |= (sc - lk) << k;
+      if (k >= Pr::nk(p)) continue;
+      const uint32_t w = s.hw[p][k];
+      us2 ev = (us2)(0);
+      if (k < Pr::od(p, 0)) ev.x = lds16_at(x.lb2 | (w & Lds<T>::CAPM7))[(T::off(Pr::snd(p, 0)) + k) << (T::CAPL + 6)];
+      if (k < Pr::od(p, 1))
+        ev.y = lds16_at(x.lb2 | ((w >> 16) & Lds<T>::CAPM7))[(T::off(Pr::snd(p, 1)) + k) << (T::CAPL + 6)];
+      e[p][k] = as_u32(ev);
+    }
+  uint32_t pk[N];  // sender v's pick: (out-index + 1) << 16 | the 16-bit entry (0: nothing)
+  uint32_t es[N];  // sender v's out-links that were empty when it scanned them: their number
+  // Peek (sim.go:83) counts of the tick, per half.  A tick adds at most D per pair and half,
+  // NP * D <= 64 * 128 in all (cl_jit.cpp lanes_fit bounds N and D far below), so a half cannot
+  // overflow before the fold below.
+  uint32_t peek2 = 0;
+  uint32_t any = 0;
+  const us2 t2 = (us2)((uint16_t)s.time);
+  // 0/1 integers per half in VGPRs, kept opaque: as compare masks the compiler would keep every
+  // channel's masks live in SGPR pairs across the phase (and spill them to VGPR lanes)
+  const uint32_t sc0 = opaque(act ? 0x10001u : 0u);
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    uint32_t pke = 0, pki = 0;  // the halves' picked entries, and their out-index + 1
+    uint32_t lks = 0, scs = 0;  // links looked at; links scanned (still scanning when reached)
+    uint32_t sc = sc0;          // still scanning
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      if (k >= Pr::nk(p)) continue;
+      const uint32_t w = s.hw[p][k];
+      const uint32_t ne = pk_min1(w & 0x007f007fu);      // queue non-empty
+      const uint32_t le = opaque(due16x2(e[p][k], t2));  // receiveTime <= time
+      const uint32_t lk = sc & ne;                       // Peek (sim.go:83)
+      lks += lk;  // (plain adds and subtracts where no half can carry or borrow)
+      scs += Pr::present(p, k) == 0x10001u ? sc : sc & Pr::present(p, k);
       const uint32_t due = opaque(lk & le);
       if constexpr (SPILL) {
-        if (__builtin_expect(due && (w & 0x7fu) > Lds<T>::CAP, 0)) {  // refill the freed slot from the spill ring
-          KPar* p = kpar();
-          const uint32_t c = T::off(v) + k;
-          const int32_t ocap = p->lay.ocap_log2;
-          uint32_t* hp = &p->ovh[c * x.stride + x.inst];
-          const uint32_t h = *hp;
-          lds16_at(x.lb2 | (w & Lds<T>::CAPM7))[c << (T::CAPL + 6)] =
-              (uint16_t)e32_to_16(p->ovf[((c << ocap) + h) * x.stride + x.inst]);
-          *hp = (h + 1) & ((1u << ocap) - 1);
+        // a due head whose queue reaches past the LDS ring (some half's count >= CAP, then
+        // exactly per half): refill the freed slot from the spill ring
+        if (__builtin_expect(due != 0 && (w & ((0x7fu & ~(Lds<T>::CAP - 1u)) * 0x10001u)) != 0, 0)) {
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            if (k >= Pr::od(p, h)) continue;
+            const uint32_t wh = w >> (16 * h);
+            if (((due >> (16 * h)) & 1u) && (wh & 0x7fu) > Lds<T>::CAP) {
+              KPar* kp = kpar();
+              const uint32_t c = T::off(Pr::snd(p, h)) + k;
+              const int32_t ocap = kp->lay.ocap_log2;
+              uint32_t* hp = &kp->ovh[c * x.stride + x.inst];
+              const uint32_t hd = *hp;
+              lds16_at(x.lb2 | (wh & Lds<T>::CAPM7))[c << (T::CAPL + 6)] =
+                  (uint16_t)e32_to_16(kp->ovf[((c << ocap) + hd) * x.stride + x.inst]);
+              *hp = (hd + 1) & ((1u << ocap) - 1);
+            }
+          }
         }
       }
-      // Pop: head + 1, count - 1 (a 24-bit multiply-add: `due * 0x7f` became a 64-bit
-      // v_mad_u64_u32 plus a copy; C3 1.563 -> 1.558 ms per step, gpurun_out/r06ab2)
-      s.hw[v][k] = w + __umul24(due, 0x7fu);
-      const uint32_t val = e[v][k] | ((uint32_t)(k + 1) << 16);
-      pk[v] = (val & (0u - due)) | (pk[v] & (due - 1u));
+      // Pop: per half head + 1, count - 1 (one packed multiply-add)
+      s.hw[p][k] = as_u32(as_us2(due) * (us2)(0x7f) + as_us2(w));
+      // a half is due at most once in its scan (it stops scanning), so the pick accumulates
+      pke = as_u32(as_us2(e[p][k]) * as_us2(due) + as_us2(pke));
+      pki = as_u32(as_us2(due) * (us2)((uint16_t)(k + 1)) + as_us2(pki));
       sc -= due;
+    }
+    peek2 += lks;
+    any |= pki;
+    const uint32_t es2 = scs - lks;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int v = Pr::snd(p, h);
+      if (v < 0) continue;
+      // (index + 1) << 16 | entry of this half: one v_perm_b32
+      pk[v] = __builtin_amdgcn_perm(pki, pke, h ? 0x07060302u : 0x05040100u);
+      es[v] = h ? es2 >> 16 : es2 & 0xffffu;
     }
     sched_fence();
   }
+  s.peek += (peek2 & 0xffffu) + (peek2 >> 16);
   // nothing due anywhere in the wave (15 % of C3's wave-ticks, mostly drain tails): the tick
   // ends here -- phase A already counted its peeks, and B, the completion check and C/D
   // would change nothing
-  {
-    uint32_t any = 0;
-#pragma unroll
-    for (int v = 0; v < N; ++v) any |= pk[v];
-    if (!__ballot(any != 0)) return true;
-  }
+  if (!__ballot(any != 0)) return true;
   // ---- B: receive, in-links in ascending sender rank ----------------------------------------
   // Straight-line and predicated: every register update happens on every lane (selects), only
   // the two snapshot-record stores sit in (divergent) branches -- register writes inside a
@@ -494,7 +600,7 @@ __device__ __forceinline__ bool tick(const Ctx& x, State<T>& s, bool act) {
         // the reference scans this sender's links after the pushes when the trigger came
         // from a lower rank: each link that was empty when it scanned it is peeked again
         if (T::src(v, j) < v) {
-          s.peek += first ? (uint32_t)__builtin_popcount(es[v]) : 0u;
+          s.peek += first ? es[v] : 0u;
           es[v] = first ? 0u : es[v];
         }
       }
@@ -597,15 +703,16 @@ __device__ __forceinline__ bool tick(const Ctx& x, State<T>& s, bool act) {
             uint32_t any = 0;
 #pragma unroll
             for (int k = 0; k < D; ++k)
-              if (k < T::od(v)) any |= s.hw[v][k];
-            hard = on && (k0 + T::od(v) > x.draws || (any & Guard<T>::FULL) != 0);
+              if (k < T::od(v)) any |= s.hw[Pr::pr(v)][k];
+            hard = on && (k0 + T::od(v) > x.draws || (any & (Guard<T>::FULL << Pr::sh(v))) != 0);
           }
           if (!FAST || __builtin_expect(__ballot(hard) != 0, 0)) {
             int32_t nf = 0;
 #pragma unroll
             for (int k = 0; k < D; ++k) {
               if (k >= T::od(v)) continue;
-              push<T, SPILL>(x, s.hw[v][k], T::off(v) + k, on, mpl, k0 + k, (dl >> (4 * k)) & 15u, s.time, nf);
+              push<T, SPILL>(x, s.hw[Pr::pr(v)][k], Pr::sh(v), T::off(v) + k, on, mpl, k0 + k, (dl >> (4 * k)) & 15u,
+                             s.time, nf);
             }
             const bool take = nf != 0 && (uint32_t)v <= fv;
             fr = take ? nf : fr;
@@ -615,7 +722,7 @@ __device__ __forceinline__ bool tick(const Ctx& x, State<T>& s, bool act) {
 #pragma unroll
             for (int k = 0; k < D; ++k) {
               if (k >= T::od(v)) continue;
-              sl[k] = sure_slot<T>(x, s.hw[v][k]);
+              sl[k] = sure_slot<T>(x, s.hw[Pr::pr(v)][k], Pr::sh(v));
               en[k] = sure_entry(mpl, (dl >> (4 * k)) & 15u, s.time);
             }
             if (on) {  // (stores only: no register is written under the lane mask)
@@ -623,10 +730,10 @@ __device__ __forceinline__ bool tick(const Ctx& x, State<T>& s, bool act) {
               for (int k = 0; k < D; ++k)
                 if (k < T::od(v)) lds16_at(sl[k])[(T::off(v) + k) << (T::CAPL + 6)] = (uint16_t)en[k];
             }
-            const uint32_t on01 = on ? 1u : 0u;
+            const uint32_t on01 = on ? 1u << Pr::sh(v) : 0u;
 #pragma unroll
             for (int k = 0; k < D; ++k)
-              if (k < T::od(v)) s.hw[v][k] += on01;
+              if (k < T::od(v)) s.hw[Pr::pr(v)][k] += on01;
           }
         }
       }
@@ -659,6 +766,7 @@ __device__ __forceinline__ V pick_slot(const V (&a)[N], int32_t i) {
   for (int v = 1; v < N; ++v) r = v == i ? opaque(a[v]) : r;
   return r;
 }
+// out-link k of node a: its 16-bit head word, extracted from its pair's register
 template <class T>
 __device__ __forceinline__ uint32_t pick_hw(const State<T>& s, int32_t a, int32_t k) {
   uint32_t r = 0;
@@ -666,8 +774,17 @@ __device__ __forceinline__ uint32_t pick_hw(const State<T>& s, int32_t a, int32_
   for (int v = 0; v < T::N; ++v)
 #pragma unroll
     for (int j = 0; j < T::D; ++j)
-      if (j < T::od(v)) r = (v == a && j == k) ? opaque(s.hw[v][j]) : r;
+      if (j < T::od(v)) r = (v == a && j == k) ? opaque(hw_get(s, v, j)) : r;
   return r;
+}
+// ... and `inc` (0 or 1) added to its count
+template <class T>
+__device__ __forceinline__ void bump_hw(State<T>& s, int32_t a, int32_t k, uint32_t inc) {
+#pragma unroll
+  for (int v = 0; v < T::N; ++v)
+#pragma unroll
+    for (int j = 0; j < T::D; ++j)
+      if (j < T::od(v)) s.hw[Pairs<T>::pr(v)][j] += (v == a && j == k) ? inc << Pairs<T>::sh(v) : 0u;
 }
 
 // SendTokens (node.go:112-131) of one send event: balance check, link lookup, push.
@@ -686,15 +803,11 @@ __device__ __forceinline__ void send_one(const Ctx& x, State<T>& s, const Op& op
     for (int v = 0; v < T::N; ++v) o = v == a ? T::off(v) : o;
     return o;
   }();
-  push<T, SPILL>(x, hw, ch, go, (uint32_t)op.c << 8, s.draw, delays8<T>(x, s.draw) & 15u, s.time, nf);
+  push<T, SPILL>(x, hw, 0u, ch, go, (uint32_t)op.c << 8, s.draw, delays8<T>(x, s.draw) & 15u, s.time, nf);
   const uint32_t inc = hw - h0;  // 1 where the push landed
 #pragma unroll
-  for (int v = 0; v < T::N; ++v) {
-    s.tok[v] -= (v == a && go) ? op.c : 0;
-#pragma unroll
-    for (int j = 0; j < T::D; ++j)
-      if (j < T::od(v)) s.hw[v][j] += (v == a && j == b) ? inc : 0u;
-  }
+  for (int v = 0; v < T::N; ++v) s.tok[v] -= (v == a && go) ? op.c : 0;
+  bump_hw(s, a, b, inc);
   s.flag = nf;
   if (s.alive) {
     if (insufficient) {
@@ -765,31 +878,26 @@ __device__ __forceinline__ void start_snapshot(const Ctx& x, State<T>& s, const 
 #pragma unroll
   for (int k = 0; k < T::D; ++k)
     if (k < od) any |= pick_hw(s, a, k);
-  const bool hard = on && (s.draw + od > x.draws || (any & Guard<T>::FULL) != 0);
+  const bool hard = on && (s.draw + od > x.draws || (any & Guard<T>::FULL) != 0);  // (extracted halves)
   if (__builtin_expect(__ballot(hard) != 0, 0)) {
 #pragma unroll
     for (int k = 0; k < T::D; ++k) {
       if (k >= od) continue;  // (uniform)
       uint32_t hw = pick_hw(s, a, k);
       const uint32_t h0 = hw;
-      push<T, SPILL>(x, hw, off + (uint32_t)k, on, 0x8000u | (sid << 8), s.draw + k, (dl >> (4 * k)) & 15u, s.time,
-                     nf);
-      const uint32_t inc = hw - h0;
-#pragma unroll
-      for (int v = 0; v < T::N; ++v)
-        if (k < T::od(v)) s.hw[v][k] += v == a ? inc : 0u;
+      push<T, SPILL>(x, hw, 0u, off + (uint32_t)k, on, 0x8000u | (sid << 8), s.draw + k, (dl >> (4 * k)) & 15u,
+                     s.time, nf);
+      bump_hw(s, a, k, hw - h0);
     }
   } else {
     const uint32_t on01 = on ? 1u : 0u;
 #pragma unroll
     for (int k = 0; k < T::D; ++k) {
       if (k >= od) continue;  // (uniform)
-      const uint32_t sl = sure_slot<T>(x, pick_hw(s, a, k)) + ((off + (uint32_t)k) << (T::CAPL + 7));
+      const uint32_t sl = sure_slot<T>(x, pick_hw(s, a, k), 0u) + ((off + (uint32_t)k) << (T::CAPL + 7));
       const uint32_t en = sure_entry(0x8000u | (sid << 8), (dl >> (4 * k)) & 15u, s.time);
       if (on) *lds16_at(sl) = (uint16_t)en;
-#pragma unroll
-      for (int v = 0; v < T::N; ++v)
-        if (k < T::od(v)) s.hw[v][k] += v == a ? on01 : 0u;
+      bump_hw(s, a, k, on01);
     }
   }
   s.flag = nf;
@@ -821,8 +929,12 @@ __device__ __forceinline__ void send_c(const Ctx& x, State<T>& s) {
   const bool go = s.alive && !insufficient && B >= 0;
   int32_t nf = 0;
   if constexpr (B >= 0) {  // (an unknown destination pushes nothing: go is false)
-    push<T, SPILL>(x, s.hw[A][B], T::off(A) + (uint32_t)B, go, (uint32_t)C << 8, s.draw, delays8<T>(x, s.draw) & 15u,
-                   s.time, nf);
+    push<T, SPILL>(x, s.hw[Pairs<T>::pr(A)][B], Pairs<T>::sh(A), T::off(A) + (uint32_t)B, go, (uint32_t)C << 8, s.draw,
+                   delays8<T>(x, s.draw) & 15u, s.time, nf);
+    // (cut here for the optimizer: over a hundred sends in a row on one high-half channel are a
+    // chain of shifts, adds and selects on one register that took its value tracking tens of
+    // gigabytes to see through)
+    s.hw[Pairs<T>::pr(A)][B] = opaque(s.hw[Pairs<T>::pr(A)][B]);
     s.tok[A] -= go ? C : 0;
   }
   s.flag = nf;
@@ -855,26 +967,27 @@ __device__ __forceinline__ void snap_c(const Ctx& x, State<T>& s) {
     constexpr uint32_t mpl = 0x8000u | ((uint32_t)SID << 8);
     uint32_t any = 0;
 #pragma unroll
-    for (int k = 0; k < od; ++k) any |= s.hw[A][k];
-    const bool hard = on && (s.draw + od > x.draws || (any & Guard<T>::FULL) != 0);
+    for (int k = 0; k < od; ++k) any |= s.hw[Pairs<T>::pr(A)][k];
+    const bool hard = on && (s.draw + od > x.draws || (any & (Guard<T>::FULL << Pairs<T>::sh(A))) != 0);
     if (__builtin_expect(__ballot(hard) != 0, 0)) {
 #pragma unroll
       for (int k = 0; k < od; ++k)
-        push<T, SPILL>(x, s.hw[A][k], T::off(A) + (uint32_t)k, on, mpl, s.draw + k, (dl >> (4 * k)) & 15u, s.time, nf);
+        push<T, SPILL>(x, s.hw[Pairs<T>::pr(A)][k], Pairs<T>::sh(A), T::off(A) + (uint32_t)k, on, mpl, s.draw + k,
+                       (dl >> (4 * k)) & 15u, s.time, nf);
     } else {
       uint32_t sl[od], en[od];
 #pragma unroll
       for (int k = 0; k < od; ++k) {
-        sl[k] = sure_slot<T>(x, s.hw[A][k]);
+        sl[k] = sure_slot<T>(x, s.hw[Pairs<T>::pr(A)][k], Pairs<T>::sh(A));
         en[k] = sure_entry(mpl, (dl >> (4 * k)) & 15u, s.time);
       }
       if (on) {  // (stores only: no register is written under the lane mask)
 #pragma unroll
         for (int k = 0; k < od; ++k) lds16_at(sl[k])[(T::off(A) + k) << (T::CAPL + 6)] = (uint16_t)en[k];
       }
-      const uint32_t on01 = on ? 1u : 0u;
+      const uint32_t on01 = on ? 1u << Pairs<T>::sh(A) : 0u;
 #pragma unroll
-      for (int k = 0; k < od; ++k) s.hw[A][k] += on01;
+      for (int k = 0; k < od; ++k) s.hw[Pairs<T>::pr(A)][k] += on01;
     }
   }
   s.flag = nf;
@@ -913,10 +1026,10 @@ __device__ __forceinline__ void tick_loop(const Ctx& x, State<T>& s, bool drain,
       // drain tail after the last delivery, all of C3's idle wave-ticks) -- add them at once
       uint32_t q = 0;
 #pragma unroll
-      for (int v = 0; v < N; ++v)
+      for (int p = 0; p < Pairs<T>::NP; ++p)
 #pragma unroll
         for (int k = 0; k < D; ++k)
-          if (k < T::od(v)) q |= s.hw[v][k] & 0x7fu;
+          if (k < Pairs<T>::nk(p)) q |= s.hw[p][k] & 0x007f007fu;
       if (!__ballot(q != 0)) {
         if (s.alive) s.time += max(0, until - (iter + 1));
         break;
@@ -1009,12 +1122,14 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
   for (int v = 0; v < N; ++v) {
     s.tok[v] = p.lt.init_tok[v];
 #pragma unroll
-    for (int k = 0; k < D; ++k) s.hw[v][k] = 0;
-#pragma unroll
     for (int k = 0; k < (D + 1) / 2; ++k) s.cr[v][k] = 0;
 #pragma unroll
     for (int w = 0; w < T::SW; ++w) s.pd[v][w] = 0;
   }
+#pragma unroll
+  for (int q = 0; q < Pairs<T>::NP; ++q)
+#pragma unroll
+    for (int k = 0; k < D; ++k) s.hw[q][k] = 0;
   s.time = s.draw = s.status = 0;
   s.peek = s.push = s.ndone = 0;
   if (P::SPEC || p.fresh) {
@@ -1034,7 +1149,7 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
 #pragma unroll
       for (int k = 0; k < D; ++k) {
         const uint32_t lw = S[(b + lay.w_lnk + k) * st];
-        if (k < T::od(v)) s.hw[v][k] = ((lw >> 8) & 0x7fu) | ((lw & 0xffu) << 7);
+        if (k < T::od(v)) s.hw[Pairs<T>::pr(v)][k] |= (((lw >> 8) & 0x7fu) | ((lw & 0xffu) << 7)) << Pairs<T>::sh(v);
         if (k < T::id(v)) s.cr[v][k >> 1] |= (lw >> 16) << ((k & 1) * 16);
       }
       const uint32_t* R = S + (b + lay.priv) * st;
@@ -1149,7 +1264,7 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
     for (int k = 0; k < D; ++k) {
       if (k < T::id(v)) ptok += cur_get(s, v, k);
       if (k >= T::od(v)) continue;
-      const uint32_t w = s.hw[v][k], cnt = w & 0x7fu, head = (w >> 7) & 0xffu;
+      const uint32_t w = hw_get(s, v, k), cnt = w & 0x7fu, head = w >> 7;
       const uint32_t c = T::off(v) + k;
       queued += cnt;
       for (uint32_t q = 0; q < cnt && q < cap; ++q) {
@@ -1206,7 +1321,7 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
     for (int k = 0; k < D; ++k) {
       uint32_t lw = k < T::id(v) ? cur_get(s, v, k) << 16 : 0u;
       if (k < T::od(v)) {
-        const uint32_t w = s.hw[v][k];
+        const uint32_t w = hw_get(s, v, k);
         lw |= ((w >> 7) & (cap - 1)) | ((w & 0x7fu) << 8);
       }
       S[(b + lay.w_lnk + k) * st] = lw;
