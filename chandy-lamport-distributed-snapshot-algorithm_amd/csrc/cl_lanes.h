@@ -298,6 +298,39 @@ struct Pairs {
   static constexpr uint32_t present(int p, int k) { return (k < od(p, 0) ? 1u : 0u) | (k < od(p, 1) ? 0x10000u : 0u); }
 };
 
+// The generic kernels' program type: the program is read from `ops` (the program types that
+// cl_jit.cpp generates are described with send_c / snap_c below).
+struct NoProg {
+  static constexpr bool SPEC = false;
+};
+
+// The in-links that can carry a token.  A program-specialized kernel starts from the initial
+// state and runs exactly the program P, so a token only ever travels on a channel that one of
+// P's OP_SEND host ops names: on(v, j) for in-link j of node v is true when some send has
+// a == src(v, j) and b == oix(v, j).  A send counts wherever it stands (the arm after the last
+// tick op included) and whether or not it succeeds at run time; one with an unknown destination
+// (b < 0) names no channel.  Every other in-link delivers markers only: phase B has no token
+// path there, and its recording cursor is the constant 0.  NoProg: true everywhere.
+template <class T, class P>
+struct TokIn {
+  struct Tab {
+    bool t[T::N][T::D];
+  };
+  static constexpr Tab make() {
+    Tab t{};
+    if constexpr (P::SPEC) {
+      for (int h = 0; h < P::h0(P::NARM); ++h)
+        if (P::hk(h) == OP_SEND && P::hb(h) >= 0) t.t[T::dst(P::ha(h), P::hb(h))][T::ipos(P::ha(h), P::hb(h))] = true;
+    } else {
+      for (int v = 0; v < T::N; ++v)
+        for (int j = 0; j < T::D; ++j) t.t[v][j] = true;
+    }
+    return t;
+  }
+  static constexpr Tab tab = make();
+  static constexpr bool on(int v, int j) { return tab.t[v][j]; }
+};
+
 // State of one instance.
 //   hw[p][k]  link slot k of sender pair p (Pairs): the low half is the first sender's out-link
 //             k, the high half the second's.  Per half: bits 6..0 queued packets (LDS ring + HBM
@@ -432,8 +465,9 @@ __device__ __forceinline__ uint32_t sure_entry(uint32_t pl16, uint32_t delay, in
 }
 
 // CreateLocalSnapshot (node.go:58-84) at node v: record tokens and open every in-channel except
-// the one the first marker arrived on (arrive = -1 at the initiator): one vector store.
-template <class T>
+// the one the first marker arrived on (arrive = -1 at the initiator): one vector store.  An
+// in-link that carries no token under P (TokIn) records the constant 0.
+template <class T, class P>
 __device__ __forceinline__ void create_record(const Ctx& x, uint32_t* snod, const State<T>& s, int v, int arrive,
                                               uint32_t rb) {
   constexpr int RW = rec_w(T::D);
@@ -441,7 +475,8 @@ __device__ __forceinline__ void create_record(const Ctx& x, uint32_t* snod, cons
   r[0] = (uint32_t)s.tok[v];
 #pragma unroll
   for (int j = 0; j < RW - 1; ++j) {
-    const uint32_t c = (j < T::D && j < T::id(v)) ? cur_get(s, v, j < T::D ? j : 0) : 0u;
+    const bool tl = j < T::D && j < T::id(v) && TokIn<T, P>::on(v, j < T::D ? j : 0);
+    const uint32_t c = tl ? cur_get(s, v, j < T::D ? j : 0) : 0u;
     r[1 + j] = j == arrive ? (c | (c << 16)) : c;
   }
   const uint32_t o = rb + node_off<T>(x, (uint32_t)v);
@@ -469,7 +504,9 @@ __device__ __forceinline__ void resolve(State<T>& s) {
 
 // Tick (sim.go:71-95) for a lane whose instance is `act`.  Every lane of the wave calls it.
 // Returns true when no lane of the wave picked a packet (the tick ended after phase A).
-template <class T, bool SPILL>
+// P: the program the kernel is specialized on (phase B's token path exists only on the in-links
+// of TokIn<T, P>).
+template <class T, bool SPILL, class P>
 __device__ __forceinline__ bool tick(const Ctx& x, State<T>& s, bool act) {
   constexpr int N = T::N, D = T::D;
   s.time += act ? 1 : 0;
@@ -579,11 +616,15 @@ __device__ __forceinline__ bool tick(const Ctx& x, State<T>& s, bool act) {
       const int sj = T::src(v, j);
       const uint32_t pkj = pk[sj];
       const bool m = (pkj >> 16) == (uint32_t)(T::oix(v, j) + 1);
-      const bool mk = m && (pkj & 0x8000u);
-      const bool tk = m && !(pkj & 0x8000u);
-      // HandleToken (node.go:174-185): tokens += data, the channel's recording cursor advances
-      s.tok[v] += tk ? (int32_t)((pkj >> 8) & 0x7fu) : 0;
-      s.cr[v][j >> 1] += tk ? (1u << ((j & 1) * 16)) : 0u;
+      // (a constant of (v, j) once the loops are unrolled, like T::id(v): a plain if)
+      const bool tl = TokIn<T, P>::on(v, j);
+      const bool mk = tl ? m && (pkj & 0x8000u) : m;  // (no token on this in-link: a match is a marker)
+      if (tl) {
+        const bool tk = m && !(pkj & 0x8000u);
+        // HandleToken (node.go:174-185): tokens += data, the channel's recording cursor advances
+        s.tok[v] += tk ? (int32_t)((pkj >> 8) & 0x7fu) : 0;
+        s.cr[v][j >> 1] += tk ? (1u << ((j & 1) * 16)) : 0u;
+      }
       // HandleMarker (node.go:149-171): the first marker of a snapshot creates the local
       // snapshot (pending = indeg - 1, nibble indeg) and triggers the broadcast; a later one
       // closes the channel (pending - 1)
@@ -605,14 +646,15 @@ __device__ __forceinline__ bool tick(const Ctx& x, State<T>& s, bool act) {
         }
       }
       const uint32_t rb = plane_off(x, sid) + x.lrec;
-      if (first) create_record<T>(x, snod, s, v, j, rb);
+      if (first) create_record<T, P>(x, snod, s, v, j, rb);
 #ifndef CLSNAP_ABL_NOSTORE
-      if (later)  // the channel's end cursor
+      if (later)  // the channel's end cursor (0 where no token travels; stored all the same, the
+                  // plane holds no zeros of its own)
 #else
       if (later && rb == 0xffffffffu)
 #endif
         st_at(reinterpret_cast<uint16_t*>(snod), rb + node_off<T>(x, (uint32_t)v) + (uint32_t)(4 * (1 + j) + 2),
-              (uint16_t)cur_get(s, v, j));
+              (uint16_t)(tl ? cur_get(s, v, j) : 0u));
     }
     sched_fence();
   }
@@ -919,10 +961,6 @@ __device__ __forceinline__ void start_snapshot(const Ctx& x, State<T>& s, const 
 // send_c / snap_c are send_one / start_snapshot with the node, link, token count and snapshot id
 // as constants: they touch the node's own registers, with no select ladder over node slots and no
 // op fetched, and compute the same values in the same order (the failure paths included).
-struct NoProg {
-  static constexpr bool SPEC = false;
-};
-
 template <class T, bool SPILL, int A, int B, int C>
 __device__ __forceinline__ void send_c(const Ctx& x, State<T>& s) {
   const bool insufficient = s.alive && s.tok[A] < C;
@@ -952,14 +990,14 @@ __device__ __forceinline__ void send_c(const Ctx& x, State<T>& s) {
   resolve(s);
 }
 
-template <class T, bool SPILL, int A, int SID, int C>
+template <class T, bool SPILL, class P, int A, int SID, int C>
 __device__ __forceinline__ void snap_c(const Ctx& x, State<T>& s) {
   constexpr int id = T::id(A), od = T::od(A);
   const bool on = s.alive;
   constexpr uint32_t nib = (id == 0 ? 15u : (uint32_t)id + 1u) << ((SID & 7) * 4);
   s.pd[A][SID >> 3] |= on ? nib : 0u;
   // CreateLocalSnapshot (node.go:58-84) with every in-channel recording
-  if (on) create_record<T>(x, kpar()->snap_nod, s, A, -1, plane_off(x, (uint32_t)SID) + x.lrec);
+  if (on) create_record<T, P>(x, kpar()->snap_nod, s, A, -1, plane_off(x, (uint32_t)SID) + x.lrec);
   // SendToNeighbors (node.go:97-109): one guard, then the push that cannot fail, else push()
   int32_t nf = 0;
   if constexpr (od > 0) {
@@ -998,7 +1036,7 @@ __device__ __forceinline__ void snap_c(const Ctx& x, State<T>& s) {
 // The tick loop of one tick op.  TICK: `a` ticks.  DRAIN: tick until every started snapshot
 // completed (at most `a` ticks, else HANG), then `b` more (test_common.go:123-137).  Per lane: a
 // lane ticks while iter < until (cl_kernels.hip exec_wave).
-template <class T, bool SPILL>
+template <class T, bool SPILL, class P>
 __device__ __forceinline__ void tick_loop(const Ctx& x, State<T>& s, bool drain, int32_t a, int32_t b,
                                           int32_t n_started) {
   constexpr int N = T::N, D = T::D;
@@ -1019,7 +1057,7 @@ __device__ __forceinline__ void tick_loop(const Ctx& x, State<T>& s, bool drain,
     }
     const bool act = s.alive && iter < until;
     if (!__ballot(act)) break;
-    const bool idle = tick<T, SPILL>(x, s, act);
+    const bool idle = tick<T, SPILL, P>(x, s, act);
     if (idle && !anyw) {
       // no lane picked anything: if nothing is queued anywhere in the wave either, every
       // remaining tick of this op is empty for every lane (no peek, draw or delivery; the
@@ -1201,7 +1239,7 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
           sfor<P::h0(g), P::h0(g + 1)>([&](auto hc) {
             constexpr int h = decltype(hc)::value;
             if constexpr (P::hk(h) == OP_SEND) send_c<T, SPILL, P::ha(h), P::hb(h), P::hc(h)>(x, s);
-            else snap_c<T, SPILL, P::ha(h), P::hb(h), P::hc(h)>(x, s);
+            else snap_c<T, SPILL, P, P::ha(h), P::hb(h), P::hc(h)>(x, s);
           });
           if constexpr (g < P::NSEG) {
             drain = P::td(g) != 0;
@@ -1213,7 +1251,7 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
       });
       if (P::NARM > P::NSEG && seg == P::NSEG) break;  // (host ops after the last tick op)
       tl.mark(TL_OPS);
-      tick_loop<T, SPILL>(x, s, drain, ta, tb, n_started);
+      tick_loop<T, SPILL, P>(x, s, drain, ta, tb, n_started);
       tl.mark(TL_LOOP);
       tl.drain();
       tl.mark(TL_WAIT);
@@ -1233,7 +1271,7 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
     // record stores.  This way the spill-free kernel has no scratch (C3: 168 -> 154 VGPRs).
     if (op.kind == OP_TICK || op.kind == OP_DRAIN) {
       tl.mark(TL_OPS);
-      tick_loop<T, SPILL>(x, s, op.kind == OP_DRAIN, op.a, op.b, n_started);
+      tick_loop<T, SPILL, P>(x, s, op.kind == OP_DRAIN, op.a, op.b, n_started);
       tl.mark(TL_LOOP);
       tl.drain();
       tl.mark(TL_WAIT);
@@ -1262,7 +1300,7 @@ __device__ __forceinline__ void program(const ExecParams& p, const Op* __restric
   for (int v = 0; v < N; ++v) {
 #pragma unroll
     for (int k = 0; k < D; ++k) {
-      if (k < T::id(v)) ptok += cur_get(s, v, k);
+      if (k < T::id(v) && TokIn<T, P>::on(v, k)) ptok += cur_get(s, v, k);  // (the others' cursors are 0)
       if (k >= T::od(v)) continue;
       const uint32_t w = hw_get(s, v, k), cnt = w & 0x7fu, head = w >> 7;
       const uint32_t c = T::off(v) + k;
