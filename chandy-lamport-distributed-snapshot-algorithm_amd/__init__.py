@@ -97,6 +97,7 @@ def lib():
         "cl_instance_hashes": [vp, i64, i64, vp],
         "cl_debug_poison_outputs": [vp],
         "cl_replay_split": [vp, vp, vp],
+        "cl_replay_plan_of": [vp, vp, i64, i32, i32, vp, vp, vp, vp],
         "cl_num_nodes": [vp, vp],
         "cl_node_id": [vp, i32, vp],
         "cl_num_channels": [vp, vp],
@@ -228,6 +229,21 @@ def go_delay_schedule(seed_base, n, draws):
     out = np.empty((n, draws), dtype=np.uint8)
     _check(lib().cl_go_delay_schedule(seed_base, n, draws, _p(out)))
     return out
+
+
+def replay_plan_of(final_ticks, spilled, insts_per_wave, can_split):
+    """The replay planning policy on the host (cl_replay_plan_of; no device): (order int32[n],
+    mapped, split_slot, n_spilled) for per-instance final ticks and spill flags (None: none)."""
+    t = np.ascontiguousarray(final_ticks, dtype=np.int32)
+    sp = None if spilled is None else np.ascontiguousarray(spilled, dtype=np.uint8)
+    if sp is not None and sp.shape != t.shape:
+        raise ClSnapError(E_INVALID, "one spill flag per final tick")
+    order = np.empty(t.size, dtype=np.int32)
+    mapped, split, n_sp = C.c_int32(), C.c_int64(), C.c_int64()
+    _check(lib().cl_replay_plan_of(_p(t), None if sp is None else _p(sp), t.size, int(insts_per_wave),
+                                   1 if can_split else 0, _p(order), C.byref(mapped), C.byref(split),
+                                   C.byref(n_sp)))
+    return order, bool(mapped.value), split.value, n_sp.value
 
 
 def _seed_rows(seed_base, n, seeds):

@@ -30,6 +30,7 @@
 #include "cl_delays.h"
 #include "cl_engine.h"
 #include "cl_host.h"
+#include "cl_plan.h"
 #include "cl_text.h"
 
 using namespace clsnap;
@@ -72,14 +73,6 @@ constexpr int32_t kDelayStageWords = 2048;
 // Workgroups (4 waves each) per CU the automatic FIFO sizing keeps LDS from limiting (the
 // spill-free kernels of degree bounds 3-4 run 6 waves per SIMD; deeper queues spill to HBM).
 constexpr int32_t kTargetBlocks = 6;
-// Batches of at least this many instances replay through a length-ordered slot map (a few
-// thousand waves: the grouping pays for its one host sort and 4 B per instance of HBM).
-constexpr int64_t kMapMinInstances = 4096;
-
-// A length-ordered slot map is used when it keeps at most this % of the wave-ticks of the
-// unordered launch (C3 90 %: kept; C2 95 %: measured slower mapped, §9)
-constexpr int64_t kMapPct = 92;
-
 // CL_PROGRAM_AUTO: replays of a planned program on the lanes kernels run kernels specialized on
 // the program where AUTO's own lanes condition holds (DESIGN §9 round 9 has the A/B this rests on)
 constexpr bool kProgramKernelsByDefault = true;
@@ -218,22 +211,9 @@ struct cl_sim {
   DevBuf<int32_t> d_snap_tick;
   DevBuf<uint32_t> d_ovf;
   DevBuf<uint32_t> d_ovh;
-  // Replay plan (build_plan), from the first fresh full run of ops [0, plan_ops) with these
-  // delays and layout -- the probe, run on the spill-capable kernel with per-instance spill
-  // flags.  Its replays (cl_rerun: the same program and delays, hence the same queues and
-  // final ticks) launch through a slot map d_map: instances grouped by their final tick so the
-  // 64 / N instances sharing a wave end their drains together, and the instances that spilled
-  // last; slots [0, split_slot) then run the spill-free kernel (6 waves per SIMD at degree
-  // bounds 3-4) and the rest the spill-capable one, concurrently on stream2.  Results are per
-  // instance and identical on either kernel.
-  DevBuf<uint8_t> d_spill_inst;  // [n_inst] probe: 1 where a push spilled to HBM
-  int64_t plan_ops = -1;         // program length the plan holds for (-1: none)
-  int64_t plan_tried = -1;       // program length a probe last ran for
-  bool probe = false;            // the last launch was a probe (plan built at the next sync)
-  int64_t probe_ops = 0;
-  bool probe_flags = false;      // the probe recorded spill flags
-  bool plan_map = false, plan_nospill = false;
-  int64_t plan_split = 0, plan_spilled = 0;
+  // The replay plan of the program and what it keeps on the device (cl_plan.h)
+  ReplayPlan plan;
+  bool has_plan() const { return plan.holds((int64_t)ops.size()); }
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   // Split replays back to back: the spill-capable half of a replay on stream2
@@ -252,22 +232,6 @@ struct cl_sim {
     HIP_TRY(hipStreamWaitEvent(stream, ev_join, 0));
     return CL_OK;
   }
-  // wave end their drains together; replays of the same program and delays launch through
-  // the map (results are per instance, unchanged).  -1: no map.
-  DevBuf<int32_t> d_map;
-  // Records block-major by replay slot (cl_engine.h rec_word): set by every launch from the
-  // initial state (a replay through the map on the instance-per-lane kernels writes them so;
-  // every other launch instance-major); h_rec_slot / d_rec_slot = the plan's inverse map then.
-  bool rec_blocked = false;
-  std::vector<int32_t> plan_inv, h_rec_slot;
-  int64_t plan_gen = 0, rec_slot_gen = -1;
-  DevBuf<int32_t> d_rec_slot;
-  // The plan's delay rows packed for the instance-per-lane kernel (ExecParams::sched_pk,
-  // cl_rowpack.hip): made at the first replay through the slot map, valid for the plan (plan_gen)
-  // and the rows on the device (delays.rows().gen) it was packed from; a replay that finds another
-  // plan or other rows packs again.
-  DevBuf<uint32_t> d_sched_pk;
-  int64_t pk_plan_gen = -1, pk_rows_gen = -1;
   DevBuf<int32_t> d_hist;
   DevBuf<unsigned long long> d_sums;
   // device event trace (cl_trace_enable): instances [trace_lo, trace_lo + trace_n)
@@ -514,8 +478,7 @@ struct cl_sim {
     const size_t ov = lay.ocap_log2 >= 0 ? ((size_t)C << lay.ocap_log2) * stride : 1;
     if ((rc = d_ovf.ensure(ov))) return rc;
     if ((rc = d_ovh.ensure(lay.ocap_log2 >= 0 ? (size_t)std::max(C, 1) * stride : 1))) return rc;
-    if (lay.ocap_log2 >= 0 && (rc = d_spill_inst.ensure((size_t)n_inst))) return rc;
-    plan_ops = plan_tried = -1;
+    plan.drop();
     need_fresh = true;
     return CL_OK;
   }
@@ -653,7 +616,7 @@ struct cl_sim {
     if ((rc = ensure_layout())) return rc;
     bool rewritten = false;
     rc = delays.ensure(dev, n_inst, draws_needed(), &rewritten);
-    if (rewritten) plan_ops = plan_tried = -1;  // (the plan is of a run on the old rows)
+    if (rewritten) plan.drop();  // (the plan is of a run on the old rows)
     if (rc) return rc;
     const DelayRows rows = delays.rows();
     if (lay.x_delay && rows.row != layout_row)
@@ -683,12 +646,13 @@ struct cl_sim {
     // cl_exec_kernel prologue -- no fill launch before every replay)
     ExecParams p = exec_params(begin, started_before);
     p.save_state = save_state ? 1 : 0;
-    // replays of a planned program (build_plan): slot map, spill-free or split launches
-    const bool planned = begin == 0 && trace_n == 0 && plan_ops == (int64_t)ops.size();
+    // replays of a planned program (cl_plan.h): slot map, spill-free or split launches
+    const bool full_run = begin == 0 && trace_n == 0;
+    const bool planned = full_run && has_plan();
     if (planned) {
-      p.inst_map = plan_map ? d_map.p : nullptr;
-      p.nospill = plan_nospill ? 1 : 0;
-      p.split_slot = plan_split;
+      p.inst_map = plan.inst_map();
+      p.nospill = plan.nospill() ? 1 : 0;
+      p.split_slot = plan.split_slot();
     }
     // the instance-per-lane kernel, compiled for this topology, wherever it fits (N <= 16, every
     // degree <= 4) and the batch fills the chip with one instance per lane (AUTO); the
@@ -703,29 +667,18 @@ struct cl_sim {
     // a lanes replay through the slot map reads its delay rows from the plan's packed copy
     // (CLSNAP_ROW_PACK=0 in a dbg build: the byte rows, for A/Bs)
     if (lanes && planned && p.inst_map && debug_knob("CLSNAP_ROW_PACK", 1)) {
-      if (pk_plan_gen != plan_gen || pk_rows_gen != rows.gen) {
-        // (an earlier replay's halves may still read the plane; stream2's half of the coming one
-        // does not wait for `stream`, so the packing is finished before it is launched)
+      if (!plan.rows_packed(rows)) {  // (the caller's rule of cl_plan.h: join, drain, pack, drain)
         if ((rc = join_stream2())) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
-        if ((rc = d_sched_pk.ensure(row_pack_words(n_inst, rows.row)))) return rc;
-        const int pe = launch_row_pack(rows.d, rows.row, d_map.p, n_inst, d_sched_pk.p, stream);
-        if (pe != 0) return set_err(CL_E_DEVICE, "row pack launch failed: %s", hipGetErrorString((hipError_t)pe));
+        if ((rc = plan.pack_rows(rows, n_inst, stream))) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
-        pk_plan_gen = plan_gen;
-        pk_rows_gen = rows.gen;
       }
-      p.sched_pk = d_sched_pk.p;
+      p.sched_pk = plan.packed_rows();
     }
-    // the first fresh full run of a program is the probe: per-instance spill flags (cleared
-    // once per program, not per replay) and final ticks
-    probe = begin == 0 && trace_n == 0 && !planned && plan_tried != (int64_t)ops.size();
-    probe_ops = (int64_t)ops.size();
-    probe_flags = probe && lay.ocap_log2 >= 0;
-    if (probe_flags) {
-      HIP_TRY(hipMemsetAsync(d_spill_inst.p, 0, (size_t)n_inst, stream));
-      p.spill_flag = d_spill_inst.p;
-    }
+    // the first fresh full run of a program is the probe: spill flags and final ticks
+    if ((rc = plan.begin_launch(full_run && !planned, (int64_t)ops.size(), lay.ocap_log2 >= 0, n_inst, stream,
+                                &p.spill_flag)))
+      return rc;
     if (p.split_slot > 0 && !stream2) {
       HIP_TRY(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
       HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
@@ -769,26 +722,11 @@ struct cl_sim {
     // initial state again) writes its records block-major by slot: a wave's stores of one
     // node's records are contiguous (both kernels; C3 2^20 1.636 -> 1.567 ms per replay on the
     // lanes kernels, C2 0.171 -> 0.165 ms node-parallel, gpurun_out/r06m, r06n)
-    const bool blocked_fresh = begin == 0 && !planned && !save_state && debug_knob("CLSNAP_BLK_FRESH", 0);
-    const bool blocked = (planned && p.inst_map && !save_state) || blocked_fresh;
-    if (blocked_fresh && rec_slot_gen != -2) {  // (dbg A/B: the identity slot order)
-      h_rec_slot.resize((size_t)n_inst);
-      for (int64_t i = 0; i < n_inst; ++i) h_rec_slot[(size_t)i] = (int32_t)i;
-      if ((rc = d_rec_slot.ensure(h_rec_slot.size()))) return rc;
-      HIP_TRY(hipMemcpy(d_rec_slot.p, h_rec_slot.data(), h_rec_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      rec_slot_gen = -2;
+    const bool blocked = planned && p.inst_map && !save_state;
+    if (blocked) {
+      if ((rc = plan.slot_table(stream))) return rc;
+      p.rec_blocked = 1;
     }
-    if (blocked && !blocked_fresh) {
-      if (rec_slot_gen != plan_gen) {
-        if ((rc = d_rec_slot.ensure(plan_inv.size()))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_rec_slot.p, plan_inv.data(), plan_inv.size() * sizeof(int32_t),
-                               hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        h_rec_slot = plan_inv;
-        rec_slot_gen = plan_gen;
-      }
-    }
-    if (blocked) p.rec_blocked = 1;
     bool used_lanes = lanes;
     int e = lanes ? launch_lanes(p, d_topo.p, d_ops.p, rows.d, el) : launch_exec(p, d_topo.p, d_ops.p, rows.d, el);
     if (lanes && e == (int)hipErrorInvalidImage) {
@@ -804,7 +742,7 @@ struct cl_sim {
     }
     last_engine = used_lanes ? CL_ENGINE_LANES : CL_ENGINE_NODES;
     last_prog = used_lanes ? prog_used : 0;
-    if (begin == 0) rec_blocked = blocked;
+    if (begin == 0) plan.wrote_records(blocked);
     if (pipe) {
       s2_live = true;
       s_dirty = false;
@@ -836,82 +774,8 @@ struct cl_sim {
       if (jrc) return jrc;
     }
     HIP_TRY(hipStreamSynchronize(stream));
-    if (probe) {
-      probe = false;
-      int rc = build_plan();
-      if (rc) return rc;
-    }
-    return CL_OK;
-  }
-
-  // Sum over waves of the longest instance (wave-ticks) of a slot order.
-  int64_t wave_ticks(const std::vector<int32_t>& t, const std::vector<int32_t>& order, int64_t lo, int64_t hi) const {
-    const int64_t ipw = std::max(lay.ipw, 1);
-    int64_t sum = 0;
-    for (int64_t w = lo; w < hi; w += ipw) {
-      int32_t m = 0;
-      for (int64_t k = w; k < std::min<int64_t>(w + ipw, hi); ++k) m = std::max(m, t[(size_t)order[(size_t)k]]);
-      sum += m;
-    }
-    return sum;
-  }
-
-  // The replay plan from the probe's final ticks and spill flags (see d_spill_inst).
-  int build_plan() {
-    plan_tried = probe_ops;
-    plan_map = plan_nospill = false;
-    plan_split = plan_spilled = 0;
-    // the length of an instance's replay: its final tick (one tick-loop iteration per tick)
-    std::vector<int32_t> t((size_t)n_inst);
-    HIP_TRY(hipMemcpy2D(t.data(), sizeof(int32_t), d_regs.p + R_TIME, R_NUM * sizeof(int32_t), sizeof(int32_t),
-                        t.size(), hipMemcpyDeviceToHost));
-    std::vector<uint8_t> sp((size_t)n_inst, 0);
-    if (probe_flags) HIP_TRY(hipMemcpy(sp.data(), d_spill_inst.p, sp.size(), hipMemcpyDeviceToHost));
-    std::vector<int32_t> clean, spilled, ident((size_t)n_inst);
-    for (int64_t i = 0; i < n_inst; ++i) {
-      ident[(size_t)i] = (int32_t)i;
-      (sp[(size_t)i] ? spilled : clean).push_back((int32_t)i);
-    }
-    plan_spilled = (int64_t)spilled.size();
-    plan_nospill = spilled.empty();
-    // length order of the clean instances: one global counting sort by final tick (sorting
-    // within windows of 64 waves instead, to keep each window's scattered per-instance stores
-    // close in time, measured C3 2.71 -> 2.96 ms: the global order is kept)
-    int32_t mx = 0;
-    for (int32_t x : t) mx = std::max(mx, std::max(x, 0));
-    std::vector<int64_t> start((size_t)mx + 2, 0);
-    for (int32_t i : clean) start[(size_t)std::max(t[(size_t)i], 0) + 1]++;
-    for (size_t k = 1; k < start.size(); ++k) start[k] += start[k - 1];
-    std::vector<int32_t> by_len(clean.size());
-    for (int32_t i : clean) by_len[(size_t)start[(size_t)std::max(t[(size_t)i], 0)]++] = i;
-    // longest waves first (LPT): the dispatcher starts workgroups in slot order as resident
-    // ones retire, so the last to start are the shortest and the grid drains evenly
-    std::reverse(by_len.begin(), by_len.end());
-    // worth it only when it removes enough wave-ticks to pay for the scattered stores (C3:
-    // 43.9 -> 39.5 ticks per wave, kept; C2: 55.8 -> 52.8, measured slower mapped)
-    const int64_t nc = (int64_t)clean.size();
-    const int64_t ipw = std::max(lay.ipw, 1);
-    // split replays: the clean instances' whole waves on the spill-free kernel (a wave that
-    // holds a spilling instance runs spill-capable), when the launcher's kernels can split
-    const bool split = !spilled.empty() && specialized();
-    // a split launches through the map anyway (its scattered result stores are paid), so the
-    // clean instances then go in length order too (C2: 0.1829 -> 0.1807 ms per step)
-    const bool sort = n_inst >= kMapMinInstances &&
-                      (split || wave_ticks(t, by_len, 0, nc) * 100 <= wave_ticks(t, clean, 0, nc) * kMapPct);
-    std::vector<int32_t> order = sort ? by_len : clean;
-    order.insert(order.end(), spilled.begin(), spilled.end());
-    if (split) plan_split = nc / ipw * ipw;
-    plan_map = sort || plan_split > 0;
-    if (plan_map) {
-      int rc = d_map.ensure(order.size());
-      if (rc) return rc;
-      HIP_TRY(hipMemcpy(d_map.p, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      // the inverse (instance -> slot): where a block-major replay puts each instance's records
-      plan_inv.assign(order.size(), 0);
-      for (size_t i = 0; i < order.size(); ++i) plan_inv[(size_t)order[i]] = (int32_t)i;
-      plan_gen += 1;
-    }
-    plan_ops = probe_ops;
+    // (a probe ends here: stream2 is joined and `stream` idle)
+    if (plan.probe_pending()) return plan.end_probe(d_regs.p, n_inst, std::max(lay.ipw, 1), specialized());
     return CL_OK;
   }
 
@@ -982,13 +846,14 @@ struct cl_sim {
   int records(int sid, int64_t inst, std::vector<uint32_t>* out) const {
     const size_t w = ids.size() * (size_t)lay.rw;
     out->resize(w);
-    if (!rec_blocked) {
+    const RecordOrder ro = plan.record_order();
+    if (!ro.blocked) {
       HIP_TRY(hipMemcpy(out->data(), d_snap_nod.p + ((size_t)sid * stride + inst) * w, w * 4, hipMemcpyDeviceToHost));
       return CL_OK;
     }
     for (size_t v = 0; v < ids.size(); ++v)  // (block-major: one record per node)
       HIP_TRY(hipMemcpy(out->data() + v * lay.rw,
-                        d_snap_nod.p + rec_word(stride, (int32_t)ids.size(), lay.rw, sid, inst, h_rec_slot.data(),
+                        d_snap_nod.p + rec_word(stride, (int32_t)ids.size(), lay.rw, sid, inst, ro.h_rec_slot,
                                                 (int32_t)(v * lay.rw)),
                         (size_t)lay.rw * 4, hipMemcpyDeviceToHost));
     return CL_OK;
@@ -1005,7 +870,7 @@ struct cl_sim {
     p.regs = d_regs.p;
     p.rw = lay.rw;
     p.snap_nod = d_snap_nod.p;
-    p.rec_slot = rec_blocked ? d_rec_slot.p : nullptr;
+    p.rec_slot = plan.record_order().rec_slot;
     p.ch_slot = d_ch_slot.p;
     p.snap_tick = d_snap_tick.p;
     p.fin_tok = d_fin_tok.p;
@@ -1045,7 +910,7 @@ struct cl_sim {
     p.stride = stride;
     p.insts = insts && n > 0 ? d_pk_list.p : nullptr;
     p.snap_nod = d_snap_nod.p;
-    p.rec_slot = rec_blocked ? d_rec_slot.p : nullptr;
+    p.rec_slot = plan.record_order().rec_slot;
     p.snap_tick = d_snap_tick.p;
     p.ch_slot = d_ch_slot.p;
     p.hist_off = d_hist.p;
@@ -1089,11 +954,11 @@ struct cl_sim {
     s->regs = d_regs.p;
     s->snap_tick = d_snap_tick.p;
     s->snap_nod = d_snap_nod.p;
-    s->blocked = rec_blocked ? 1 : 0;
-    // (the slot order of the replay that wrote the records; the dbg A/B's is the identity)
-    s->inst_map = rec_blocked && rec_slot_gen != -2 ? d_map.p : nullptr;
+    const RecordOrder ro = plan.record_order();
+    s->blocked = ro.blocked ? 1 : 0;
+    s->inst_map = ro.inst_map;  // (the slot order of the replay that wrote the records)
     *t = SimTables{{d_ch_slot.p, d_hist.p, d_hist.p + hist.size() + 1, d_hist_pre.p}, d_word_ch.p,
-                   rec_blocked ? d_rec_slot.p : nullptr};
+                   ro.rec_slot};
     return CL_OK;
   }
 
@@ -1292,7 +1157,7 @@ int cl_set_limits(cl_sim* sim, int32_t fifo_lds_slots, int64_t max_drain_ticks) 
 
 int cl_set_delay_go_seeds(cl_sim* sim, int64_t seed_base) {
   SIM_CALL(sim);
-  sim->plan_ops = sim->plan_tried = -1;
+  sim->plan.drop();
   sim->delays.set_go_seeds(seed_base);
   sim->need_fresh = true;
   return CL_OK;
@@ -1301,7 +1166,7 @@ int cl_set_delay_go_seeds(cl_sim* sim, int64_t seed_base) {
 int cl_set_delay_go_seed_list(cl_sim* sim, const int64_t* seeds, int64_t n) {
   SIM_CALL(sim);
   if (!seeds || n != sim->n_inst) return set_err(CL_E_INVALID, "the seed list must have one seed per instance");
-  sim->plan_ops = sim->plan_tried = -1;
+  sim->plan.drop();
   sim->delays.set_seed_list(seeds, n);
   sim->need_fresh = true;
   return CL_OK;
@@ -1311,7 +1176,7 @@ int cl_set_delay_generator(cl_sim* sim, int32_t mode) {
   SIM_CALL(sim);
   if (mode != CL_DELAYGEN_HOST && mode != CL_DELAYGEN_DEVICE) return set_err(CL_E_INVALID, "unknown delay generator %d", mode);
   if (!sim->delays.set_generator(mode)) return CL_OK;
-  sim->plan_ops = sim->plan_tried = -1;
+  sim->plan.drop();
   sim->need_fresh = true;
   return CL_OK;
 }
@@ -1330,7 +1195,7 @@ int cl_delay_gen_time(cl_sim* sim, double* device_ms, double* host_ms, int64_t* 
 
 int cl_set_delay_schedule(cl_sim* sim, const uint8_t* delays, int64_t draws_per_instance) {
   SIM_CALL(sim);
-  sim->plan_ops = sim->plan_tried = -1;
+  sim->plan.drop();
   if (!delays || draws_per_instance <= 0) return set_err(CL_E_INVALID, "empty schedule");
   const size_t n = (size_t)(draws_per_instance * sim->n_inst);
   for (size_t i = 0; i < n; ++i)
@@ -1462,7 +1327,7 @@ int cl_replay_spill_free(cl_sim* sim, int32_t* on) {
   if (!on) return set_err(CL_E_INVALID, "null output");
   int rc = sim->sync();
   if (rc) return rc;
-  *on = sim->lay.ocap_log2 < 0 || (sim->plan_ops == (int64_t)sim->ops.size() && sim->plan_nospill) ? 1 : 0;
+  *on = sim->lay.ocap_log2 < 0 || (sim->has_plan() && sim->plan.nospill()) ? 1 : 0;
   return CL_OK;
 }
 
@@ -1471,16 +1336,15 @@ int cl_replay_split(cl_sim* sim, int64_t* spill_instances, int64_t* split_slot) 
   if (!spill_instances || !split_slot) return set_err(CL_E_INVALID, "null output");
   int rc = sim->sync();  // (a pending probe is evaluated here)
   if (rc) return rc;
-  const bool planned = sim->plan_ops == (int64_t)sim->ops.size();
-  *spill_instances = planned ? sim->plan_spilled : -1;
-  *split_slot = planned ? sim->plan_split : 0;
+  *spill_instances = sim->has_plan() ? sim->plan.spilled() : -1;
+  *split_slot = sim->has_plan() ? sim->plan.split_slot() : 0;
   return CL_OK;
 }
 
 int cl_records_blocked(cl_sim* sim, int32_t* on) {
   SIM_CALL(sim);
   if (!on) return set_err(CL_E_INVALID, "null output");
-  *on = sim->rec_blocked ? 1 : 0;
+  *on = sim->plan.record_order().blocked ? 1 : 0;
   return CL_OK;
 }
 
@@ -1489,7 +1353,7 @@ int cl_replay_mapped(cl_sim* sim, int32_t* on) {
   if (!on) return set_err(CL_E_INVALID, "null output");
   int rc = sim->sync();  // (a pending map probe is evaluated here)
   if (rc) return rc;
-  *on = sim->plan_ops == (int64_t)sim->ops.size() && sim->plan_map ? 1 : 0;
+  *on = sim->has_plan() && sim->plan.mapped() ? 1 : 0;
   return CL_OK;
 }
 
@@ -1506,7 +1370,7 @@ int cl_set_exec_engine(cl_sim* sim, int32_t engine) {
     // the next launch replays the program from the start on the chosen kernel (results are the
     // same; the resumable state image is shared by both kernels)
     sim->engine = engine;
-    sim->plan_ops = sim->plan_tried = -1;
+    sim->plan.drop();
   }
   return CL_OK;
 }
@@ -1677,9 +1541,10 @@ int cl_delay_draws_needed(const cl_sim* sim, int64_t* draws) {
 int cl_device_bytes(const cl_sim* sim, int64_t* bytes) {
   SIM_CALL(sim);
   int64_t b = 0;
-  b += sim->d_ops.n * sizeof(Op) + sim->d_topo.n * 4 + sim->d_sched_pk.n * 4 + sim->d_state.n * 4 + sim->d_regs.n * 4;
+  b += sim->d_ops.n * sizeof(Op) + sim->d_topo.n * 4 + sim->d_state.n * 4 + sim->d_regs.n * 4;
   b += sim->d_snap_nod.n * 4 + sim->d_snap_tick.n * 4 + sim->d_ovf.n * 4;
   b += sim->d_ovh.n * 4 + sim->d_hist.n * 4 + sim->d_sums.n * 8 + sim->d_fin_tok.n * 4;
+  b += sim->plan.device_bytes();    // (a mapped lanes replay's packed delay rows)
   b += sim->delays.device_bytes();  // (the delay rows, the seed list and the device generator's flagged rows)
   b += analytics_device_bytes(sim->analytics);  // (selection scratch, sets alive, crosstab words)
   *bytes = b;

@@ -193,6 +193,14 @@ int cl_replay_split(cl_sim* sim, int64_t* spill_instances, int64_t* split_slot);
  * instances sharing a wave finish together, and those that spilled last; engine-internal,
  * results unchanged). */
 int cl_replay_mapped(cl_sim* sim, int32_t* on);
+/* The planning policy behind the three calls above, on the host alone (no sim, no device): from
+ * every instance's final tick and spill flag (spilled NULL: none spilled), the layout's instances
+ * per wave and whether the kernels can split a replay, the slot order (order[n]: slot ->
+ * instance), whether replays launch through it, the split slot and the spilled instances.
+ * CL_E_INVALID for NULL final_ticks, n <= 0 or insts_per_wave <= 0; any output may be NULL.
+ * Engine-internal: it exists so the policy can be tested without a GPU. */
+int cl_replay_plan_of(const int32_t* final_ticks, const uint8_t* spilled, int64_t n, int32_t insts_per_wave,
+                      int32_t can_split, int32_t* order, int32_t* mapped, int64_t* split_slot, int64_t* n_spilled);
 
 /* 1 when the snapshot records in device memory are block-major by replay slot: the latest launch
  * from the initial state was a replay through the slot map that saved no state image (cl_rerun

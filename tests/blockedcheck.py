@@ -1,8 +1,8 @@
 """Helpers of the block-major, ragged-batch tests (test_blocked_ragged_host.py, test_blocked_ragged_gpu.py).
 
-A replay through the slot map writes the snapshot records block-major by slot; build_plan() maps
+A replay through the slot map writes the snapshot records block-major by slot; plan_order() maps
 whenever it sorts the clean instances by length (4096 instances and more) *or* splits the batch into
-a spill-free and a spill-capable half (cl_host.cpp: plan_map = sort || plan_split > 0).  A split
+a spill-free and a spill-capable half (cl_plan.cpp: mapped = sort || split_slot > 0).  A split
 needs one spilled instance, a specialized layout and one wave's worth of clean instances, so a small
 C3 batch with 4 LDS ring slots per channel already replays through the map.
 

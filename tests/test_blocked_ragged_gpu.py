@@ -9,7 +9,7 @@ bitmap is partial, and the node-parallel kernel's last wave is ragged.
 
 Small cases: C3 (8nodes.top, 8nodes-concurrent-snapshots.events) at 63, 65, 130, 200 and 257
 instances with 4 LDS ring slots per channel.  A few instances spill, so the plan splits the batch
-and replays through the map (cl_host.cpp build_plan: plan_map = sort || plan_split > 0); the order
+and replays through the map (cl_plan.cpp plan_order: mapped = sort || split_slot > 0); the order
 is "the clean instances, then the spillers", a shift that displaces every instance after the first
 spiller.  test_blocked_ragged_host.py holds the oracle's prediction; blocked_ragged_sim() asserts
 the regime on the device before anything is read.  The same program without its drain (snapshots

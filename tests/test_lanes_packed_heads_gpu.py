@@ -50,7 +50,7 @@ RECV = (2, 3)   # CL_LOG_RECV_TOKEN, CL_LOG_RECV_MARKER
 def _rows(n, width, seed):
     """Delay rows: an instance draws either 0 throughout or uniformly from 0..4.  The two kinds end
     their drains far enough apart that ordering the large batch by length saves the planner's 8 %
-    of wave-ticks (cl_host.cpp build_plan), so its replays go through the slot map."""
+    of wave-ticks (cl_plan.cpp plan_order), so its replays go through the slot map."""
     rng = np.random.default_rng(seed)
     hi = rng.choice([1, 5], size=(n, 1))
     return (rng.integers(0, 5, size=(n, width)) % hi).astype(np.uint8)
