@@ -15,11 +15,14 @@ that need them raise ``ClSnapError``.
 """
 import ctypes as C
 import os
+from fractions import Fraction
 
 import numpy as np
 
 __all__ = ["ChandyLamportSim", "SnapshotStats", "STATS_LAYOUT_FIELDS", "SnapshotSelection", "SELECT_CLAUSE_DTYPE",
            "InstanceSet", "SnapshotCrosstab", "CROSSTAB_AXIS_DTYPE", "SnapshotGroups", "GROUP_TERM_DTYPE", "group_key",
+           "SnapshotTopK", "SnapshotQuantiles", "QUANTILE_DTYPE", "ORDER_MAX_K", "ORDER_MAX_QUANTILES",
+           "order_plane_device", "quantile_rank",
 "GlobalSnapshot", "MsgSnapshot", "PassTokenEvent", "SnapshotEvent",
            "ClSnapError", "lib", "go_delay_schedule", "go_delay_schedule_device", "go_delay_schedule_jump",
            "DELAYGEN_MAX_DRAWS", "go_int63", "go_intn", "REFERENCE_SEED",
@@ -157,6 +160,15 @@ def lib():
         "cl_snapshot_groups_in": [vp, i64, i64, vp, vp, i32, vp, vp, vp, vp, vp],
         "cl_groups_time": [vp, vp],
         "cl_groups_stage_times": [vp, vp],
+        "cl_snapshot_topk": [vp, i64, i64, vp, i32, i64, vp, vp, vp],
+        "cl_snapshot_topk_in": [vp, i64, i64, vp, vp, i32, i64, vp, vp, vp],
+        "cl_snapshot_quantiles": [vp, i64, i64, vp, vp, i32, vp, vp, vp],
+        "cl_snapshot_quantiles_in": [vp, i64, i64, vp, vp, vp, i32, vp, vp, vp],
+        "cl_snapshot_values": [vp, i64, i64, vp, vp, vp],
+        "cl_snapshot_values_in": [vp, i64, i64, vp, vp, vp, vp],
+        "cl_order_time": [vp, vp],
+        "cl_order_stage_times": [vp, vp],
+        "cl_order_plane_device": [i32, vp, vp, i64, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp],
         "cl_set_delay_go_seed_list": [vp, vp, i64],
         "cl_set_delay_generator": [vp, i32],
         "cl_delay_generator": [vp, vp],
@@ -670,6 +682,187 @@ class SnapshotGroups:
                 and self.values.tobytes() == other.values.tobytes())
 
     __hash__ = None
+
+
+# cl_quantile (include/clsnap.h) and the limits of the ordering calls
+QUANTILE_DTYPE = np.dtype([("num", np.int64), ("den", np.int64)])
+ORDER_DESC = 1
+ORDER_MAX_K = 65536
+ORDER_MAX_QUANTILES = 64
+
+
+def _order_term(term, ids, chans):
+    """The one term of an ordering call, (sid, field, index) or (sid, field), as a GROUP_TERM_DTYPE
+    array of one entry: resolved exactly as a term of snapshot_groups."""
+    if isinstance(term, np.ndarray) and term.dtype == GROUP_TERM_DTYPE and term.size == 1:
+        return _group_terms(term, ids, chans)
+    if not isinstance(term, (tuple, list)):
+        raise ValueError("order term: (sid, field, index)")
+    return _group_terms([tuple(term)], ids, chans)
+
+
+def _quantiles(qs):
+    """`qs` of snapshot_quantiles as a QUANTILE_DTYPE array: each a (num, den) pair, a Fraction, the
+    int 0 or 1, or a float taken through Fraction(q).limit_denominator(10**9)."""
+    if isinstance(qs, np.ndarray) and qs.dtype == QUANTILE_DTYPE:
+        qs = [(int(q["num"]), int(q["den"])) for q in qs.ravel()]
+    if isinstance(qs, (str, bytes)) or not hasattr(qs, "__iter__"):
+        raise ValueError("quantiles: a sequence of (num, den), Fraction, 0, 1 or float")
+    qs = list(qs)
+    if not 1 <= len(qs) <= ORDER_MAX_QUANTILES:
+        raise ValueError(f"quantiles: 1 to {ORDER_MAX_QUANTILES} quantiles")
+    out = np.zeros(len(qs), dtype=QUANTILE_DTYPE)
+    for j, q in enumerate(qs):
+        if isinstance(q, (tuple, list)) and len(q) == 2 and all(
+                isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in q):
+            num, den = int(q[0]), int(q[1])
+        elif isinstance(q, Fraction):
+            num, den = q.numerator, q.denominator
+        elif isinstance(q, (int, np.integer)) and not isinstance(q, bool) and q in (0, 1):
+            num, den = int(q), 1
+        elif isinstance(q, (float, np.floating)) and 0.0 <= q <= 1.0:
+            f = Fraction(float(q)).limit_denominator(10**9)
+            num, den = f.numerator, f.denominator
+        else:
+            raise ValueError(f"quantile {j}: {q!r} is not a (num, den) pair, a Fraction, 0, 1 or a float in [0, 1]")
+        if not (1 <= den < 2**63 and 0 <= num <= den):
+            raise ValueError(f"quantile {j}: den >= 1 and 0 <= num <= den")
+        out[j] = (num, den)
+    return out
+
+
+def quantile_rank(q, sample):
+    """The nearest-rank position of quantile `q` (any form snapshot_quantiles takes) in a sample of
+    `sample` values, as cl_snapshot_quantiles computes it: 0 if num == 0 else
+    ceil(num * sample / den) - 1; -1 on an empty sample.  Host only."""
+    num, den = (int(x) for x in _quantiles([q])[0].tolist())
+    if sample <= 0:
+        return -1
+    return 0 if num == 0 else -((-num * int(sample)) // den) - 1
+
+
+def _order_keys(values, descending):
+    """The uint64 keys whose ascending order is the order of an ordering call: the value with its
+    sign bit flipped, complemented for descending (csrc/cl_analytics.h order_key)."""
+    k = np.ascontiguousarray(values, dtype=np.int64).view(np.uint64) ^ np.uint64(1 << 63)
+    return ~k if descending else k
+
+
+class SnapshotTopK:
+    """The result of ``ChandyLamportSim.snapshot_topk``: ORDER BY a snapshot quantity LIMIT k.
+
+    ``term`` is the GROUP_TERM_DTYPE array (one entry) of the call, ``descending`` its direction,
+    ``k`` what was asked for.  ``insts`` (int64, absolute) are the first ``n_returned = min(k,
+    sample)`` instances of the order -- ascending by (value, instance), or value descending with
+    the instance still ascending -- and ``values`` their values.  ``instances``, ``ok`` and
+    ``sample`` are those of snapshot_stats over the same range."""
+
+    def __init__(self, term, descending, k, instances, ok, sample, insts, values):
+        self.term = np.ascontiguousarray(term, dtype=GROUP_TERM_DTYPE).ravel()
+        self.descending, self.k = bool(descending), int(k)
+        self.instances, self.ok, self.sample = int(instances), int(ok), int(sample)
+        self.insts = np.ascontiguousarray(insts, dtype=np.int64).ravel()
+        self.values = np.ascontiguousarray(values, dtype=np.int64).ravel()
+        if self.term.size != 1 or self.insts.shape != self.values.shape:
+            raise ValueError("SnapshotTopK: one term, and one value per instance")
+
+    @property
+    def n_returned(self):
+        return int(self.insts.shape[0])
+
+    @property
+    def snapshot_id(self):
+        return int(self.term["sid"][0])
+
+    def collect(self, sim):
+        """The contents of the listed instances: sim.collect_snapshot_list(sid, insts)."""
+        return sim.collect_snapshot_list(self.snapshot_id, self.insts)
+
+    def instance_set(self, sim):
+        """The listed instances as an InstanceSet of `sim`."""
+        return sim.instance_set_from(self.insts)
+
+    def seeds(self, seed_base):
+        """seed_base + insts: what set_delay_go_seed_list takes to re-run exactly these instances."""
+        return np.int64(seed_base) + self.insts
+
+    def merge(self, other, offset=0):
+        """The top-k over the union of two disjoint instance sets (other ranks, other ranges);
+        ``offset`` is added to ``other``'s instance indices.  Exact: the top-k of a union lies within
+        the union of the parts' top-k.  Raises ValueError unless both are of the same term,
+        direction and k."""
+        if (not isinstance(other, SnapshotTopK) or other.term.tobytes() != self.term.tobytes()
+                or other.descending != self.descending or other.k != self.k):
+            raise ValueError("SnapshotTopK.merge: not the top-k of the same term, direction and k")
+        insts = np.concatenate([self.insts, other.insts + offset])
+        values = np.concatenate([self.values, other.values])
+        order = np.lexsort((insts, _order_keys(values, self.descending)))[:self.k]
+        return SnapshotTopK(self.term.copy(), self.descending, self.k, self.instances + other.instances,
+                            self.ok + other.ok, self.sample + other.sample, insts[order], values[order])
+
+    def __eq__(self, other):
+        return (isinstance(other, SnapshotTopK) and self.term.tobytes() == other.term.tobytes()
+                and (self.descending, self.k, self.instances, self.ok, self.sample)
+                == (other.descending, other.k, other.instances, other.ok, other.sample)
+                and bool(np.array_equal(self.insts, other.insts)) and bool(np.array_equal(self.values, other.values)))
+
+    __hash__ = None
+
+
+class SnapshotQuantiles:
+    """The result of ``ChandyLamportSim.snapshot_quantiles``: exact quantiles of a snapshot quantity.
+
+    ``q`` is the QUANTILE_DTYPE array of the call; ``ranks[j]`` the nearest-rank position of q[j]
+    in the ascending order of the sample, ``0 if num == 0 else ceil(num * sample / den) - 1`` (-1
+    on an empty sample), and ``values[j]`` the value there.  ``at(q)`` looks one up."""
+
+    def __init__(self, term, q, ranks, values, sample, instances=0, ok=0):
+        self.term = np.ascontiguousarray(term, dtype=GROUP_TERM_DTYPE).ravel()
+        self.q = np.ascontiguousarray(q, dtype=QUANTILE_DTYPE).ravel()
+        self.ranks = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
+        self.values = np.ascontiguousarray(values, dtype=np.int64).ravel()
+        self.sample, self.instances, self.ok = int(sample), int(instances), int(ok)
+        if not self.q.shape == self.ranks.shape == self.values.shape:
+            raise ValueError("SnapshotQuantiles: one rank and one value per quantile")
+
+    def at(self, q):
+        """The value of quantile `q` (any form snapshot_quantiles takes), which the call asked for."""
+        if self.sample == 0:
+            raise ValueError("SnapshotQuantiles.at: the sample is empty")
+        want = Fraction(*(int(x) for x in _quantiles([q])[0].tolist()))
+        for j, (num, den) in enumerate(self.q.tolist()):
+            if Fraction(num, den) == want:
+                return int(self.values[j])
+        raise KeyError(q)
+
+    def __eq__(self, other):
+        return (isinstance(other, SnapshotQuantiles) and self.term.tobytes() == other.term.tobytes()
+                and self.q.tobytes() == other.q.tobytes() and (self.sample, self.instances, self.ok)
+                == (other.sample, other.instances, other.ok) and bool(np.array_equal(self.ranks, other.ranks))
+                and (self.sample == 0 or bool(np.array_equal(self.values, other.values))))
+
+    __hash__ = None
+
+
+def order_plane_device(values, in_sample=None, k=0, largest=False, qs=None, device=0, return_ms=False):
+    """Engine-internal test aid (cl_order_plane_device): the select and compaction kernels of the
+    ordering calls on an uploaded int64 plane, element index = instance.  Returns (insts, vals,
+    q_values, q_ranks) -- the last two None without `qs` -- and the kernels' ms with return_ms."""
+    v = np.ascontiguousarray(values, dtype=np.int64).ravel()
+    m = None if in_sample is None else np.ascontiguousarray(in_sample, dtype=np.uint8).ravel()
+    if m is not None and m.shape != v.shape:
+        raise ValueError("order_plane_device: one in_sample flag per value")
+    q = None if qs is None else _quantiles(qs)
+    insts, vals = np.zeros(max(k, 0), dtype=np.int64), np.zeros(max(k, 0), dtype=np.int64)
+    n_q = 0 if q is None else q.size
+    qv, qr = np.zeros(n_q, dtype=np.int64), np.zeros(n_q, dtype=np.int64)
+    n_ret, ms = C.c_int64(0), C.c_double(0)
+    _check(lib().cl_order_plane_device(device, _p(v) if v.size else None, None if m is None else _p(m), v.size,
+                                       ORDER_DESC if largest else 0, k, _p(insts) if k > 0 else None,
+                                       _p(vals) if k > 0 else None, C.byref(n_ret), None if q is None else _p(q), n_q,
+                                       _p(qv) if n_q else None, _p(qr) if n_q else None, C.byref(ms)))
+    out = (insts[:n_ret.value].copy(), vals[:n_ret.value].copy(), qv if n_q else None, qr if n_q else None)
+    return out + (ms.value,) if return_ms else out
 
 
 class SnapshotSelection:
@@ -1287,6 +1480,94 @@ class ChandyLamportSim:
             return tuple(ms)
         ms = C.c_double(0)
         _check(self._L.cl_groups_time(self._h, C.byref(ms)))
+        return ms.value
+
+    def order_term(self, term):
+        """The term of an ordering call, (sid, field, index), as a GROUP_TERM_DTYPE array of one
+        entry (host only): resolved exactly as a term of snapshot_groups."""
+        return _order_term(term, self.node_ids(), self.channels())
+
+    def snapshot_topk(self, term, k, largest=False, lo=0, hi=None):
+        """ORDER BY `term` LIMIT k over the OK instances of [lo, hi) in which the term's snapshot
+        completed, on the GPU (cl_snapshot_topk): a SnapshotTopK with the first min(k, sample)
+        instances of the order and their values.  `term` is (sid, field, index) as in
+        snapshot_groups ("key" is refused); ascending by (value, instance), or with largest=True
+        by value descending, the instance still ascending.  k == 0 only counts."""
+        return self._topk(None, term, k, largest, lo, hi)
+
+    def _topk(self, iset, term, k, largest, lo, hi):
+        hi = self.n_instances if hi is None else hi
+        t = self.order_term(term)
+        k = int(k)
+        insts, vals = np.zeros(max(k, 0), dtype=np.int64), np.zeros(max(k, 0), dtype=np.int64)
+        info = np.zeros(4, dtype=np.int64)
+        tail = (_p(t), ORDER_DESC if largest else 0, k, _p(insts) if k > 0 else None, _p(vals) if k > 0 else None,
+                _p(info))
+        if iset is None:
+            _check(self._L.cl_snapshot_topk(self._h, lo, hi, *tail))
+        else:
+            _check(self._L.cl_snapshot_topk_in(self._h, lo, hi, iset._handle(), *tail))
+        instances, ok, sample, n = info.tolist()
+        return SnapshotTopK(t, largest, k, instances, ok, sample, insts[:n].copy(), vals[:n].copy())
+
+    def snapshot_topk_in(self, iset, term, k, largest=False, lo=0, hi=None):
+        """snapshot_topk over the members of the InstanceSet `iset` (cl_snapshot_topk_in);
+        `instances` and `ok` still count the whole range."""
+        return self._topk(iset, term, k, largest, lo, hi)
+
+    def snapshot_quantiles(self, term, qs, lo=0, hi=None):
+        """Exact quantiles of `term` over the sample of [lo, hi), on the GPU (cl_snapshot_quantiles):
+        a SnapshotQuantiles.  `qs`: up to 64 of (num, den), Fraction, 0, 1 or float (through
+        Fraction(q).limit_denominator(10**9)); nearest rank, r = 0 if num == 0 else
+        ceil(num * sample / den) - 1 in the ascending order."""
+        return self._quantiles(None, term, qs, lo, hi)
+
+    def _quantiles(self, iset, term, qs, lo, hi):
+        hi = self.n_instances if hi is None else hi
+        t, q = self.order_term(term), _quantiles(qs)
+        values, ranks = np.zeros(q.size, dtype=np.int64), np.zeros(q.size, dtype=np.int64)
+        info = np.zeros(4, dtype=np.int64)
+        tail = (_p(t), _p(q), q.size, _p(values), _p(ranks), _p(info))
+        if iset is None:
+            _check(self._L.cl_snapshot_quantiles(self._h, lo, hi, *tail))
+        else:
+            _check(self._L.cl_snapshot_quantiles_in(self._h, lo, hi, iset._handle(), *tail))
+        instances, ok, sample, _ = info.tolist()
+        return SnapshotQuantiles(t, q, ranks, values, sample, instances, ok)
+
+    def snapshot_quantiles_in(self, iset, term, qs, lo=0, hi=None):
+        """snapshot_quantiles over the members of the InstanceSet `iset` (cl_snapshot_quantiles_in)."""
+        return self._quantiles(iset, term, qs, lo, hi)
+
+    def snapshot_values(self, term, lo=0, hi=None):
+        """(values int64[hi - lo], in_sample bool[hi - lo]): `term` (any field, "key" as its int64
+        bit pattern) of every instance of [lo, hi), 0 outside the sample, evaluated on the GPU
+        (cl_snapshot_values): the bulk form of snapshot_ticks for any quantity."""
+        return self._values(None, term, lo, hi)
+
+    def _values(self, iset, term, lo, hi):
+        hi = self.n_instances if hi is None else hi
+        t = self.order_term(term)
+        values, member = np.zeros(max(hi - lo, 0), dtype=np.int64), np.zeros(max(hi - lo, 0), dtype=np.uint8)
+        if iset is None:
+            _check(self._L.cl_snapshot_values(self._h, lo, hi, _p(t), _p(values), _p(member)))
+        else:
+            _check(self._L.cl_snapshot_values_in(self._h, lo, hi, iset._handle(), _p(t), _p(values), _p(member)))
+        return values, member.astype(bool)
+
+    def snapshot_values_in(self, iset, term, lo=0, hi=None):
+        """snapshot_values over the members of the InstanceSet `iset` (cl_snapshot_values_in)."""
+        return self._values(iset, term, lo, hi)
+
+    def order_time(self, stages=False):
+        """Device ms of the latest snapshot_topk / snapshot_quantiles / snapshot_values kernels;
+        stages=True: the tuple (value walk, select passes, compaction) whose sum it is."""
+        if stages:
+            ms = (C.c_double * 3)()
+            _check(self._L.cl_order_stage_times(self._h, ms))
+            return tuple(ms)
+        ms = C.c_double(0)
+        _check(self._L.cl_order_time(self._h, C.byref(ms)))
         return ms.value
 
     def instance_set(self, snapshot_id, where=(), inst_lo=0, inst_hi=None):

@@ -1,6 +1,7 @@
 // cl_analytics.cpp -- the host layer of the batch analytics behind include/clsnap.h: statistics
 // (cl_stats.hip), census (cl_census.hip), selection (cl_select.hip), crosstab (cl_crosstab.hip) and
-// the device-resident instance sets (cl_iset.hip), and the tuple group-by (cl_groups.hip).
+// the device-resident instance sets (cl_iset.hip), the tuple group-by (cl_groups.hip) and the ordering
+// calls -- top-k, quantiles, values (cl_order.hip).
 //
 // It owns its scratch, its timers and the sets, and reads a sim through cl_host.h only: the facts
 // its argument checks need, the device and stream, and the record planes and tables of a sample.
@@ -27,6 +28,162 @@ struct cl_iset {
 };
 
 namespace clsnap {
+
+// The radix select and the top-k compaction of cl_order.hip over a value plane and its membership
+// bitmap on the device, with their scratch and their timer: what cl_snapshot_topk and
+// cl_snapshot_quantiles run after the value walk, and cl_order_plane_device on an uploaded plane.
+struct OrderEngine {
+  struct Plane {
+    const long long* values;           // [n]: element i is instance lo + i
+    const unsigned long long* bitmap;  // bit (lo + i - base) of it: element i is in the sample
+    int64_t n, lo, base;
+    long long vmin, vmax;              // of the sample (any values on an empty one)
+    int32_t desc;
+  };
+  DevBuf<OrderPos> d_pos;
+  DevBuf<uint32_t> d_hist;
+  DevBuf<unsigned long long> d_less, d_equal, d_cinfo;
+  DevBuf<long long> d_bsum, d_list_a, d_list_b, d_out_inst, d_out_val;
+  std::vector<OrderPos> h_pos;  // the positions' initial state, uploaded by select()
+  DevTimer<4> tm;    // select passes: 0 .. 1, compaction: 2 .. 3
+  int ran = 0;       // bit 0: the latest operation ran select passes, bit 1: a compaction
+
+  int64_t bytes() const {
+    return (int64_t)(d_pos.bytes() + d_hist.bytes() + d_less.bytes() + d_equal.bytes() + d_cinfo.bytes() +
+                     d_bsum.bytes() + d_list_a.bytes() + d_list_b.bytes() + d_out_inst.bytes() + d_out_val.bytes());
+  }
+
+  OrderSelectParams params(const Plane& pl, int32_t n_pos) const {
+    OrderSelectParams p{};
+    p.plane = pl.values, p.bitmap = pl.bitmap, p.n = pl.n, p.off = pl.lo - pl.base;
+    p.desc = pl.desc, p.n_pos = n_pos, p.pos = d_pos.p, p.hist = d_hist.p;
+    return p;
+  }
+
+  // Enqueues the digit passes that resolve the order positions `ranks` (ascending, each below the
+  // sample's size) and leaves their state in d_pos.  The keys of the sample lie in [kmin, kmax]: the
+  // bits above the highest one in which those differ are common, so only the digits below are passed.
+  int select(const Plane& pl, const std::vector<int64_t>& ranks, hipStream_t stream, int32_t n_cus) {
+    const int32_t n_pos = (int32_t)ranks.size();
+    int rc;
+    if ((rc = d_pos.ensure((size_t)n_pos)) || (rc = d_hist.ensure((size_t)n_pos * kOrderBins))) return rc;
+    const uint64_t kmin = order_key(pl.desc ? pl.vmax : pl.vmin, pl.desc);
+    const uint64_t kmax = order_key(pl.desc ? pl.vmin : pl.vmax, pl.desc);
+    const int32_t bits = kmin == kmax ? 0 : 64 - __builtin_clzll(kmin ^ kmax);
+    const int32_t passes = (bits + kOrderDigitBits - 1) / kOrderDigitBits;
+    h_pos.resize((size_t)n_pos);  // (a member: the host's until its copy is done)
+    for (int32_t j = 0; j < n_pos; ++j)
+      h_pos[(size_t)j] =
+          OrderPos{passes * kOrderDigitBits >= 64 ? 0 : kmin >> (passes * kOrderDigitBits), ranks[(size_t)j], 0, 0};
+    HIP_TRY(hipMemcpyAsync(d_pos.p, h_pos.data(), h_pos.size() * sizeof(OrderPos), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(d_hist.p, 0, (size_t)n_pos * kOrderBins * sizeof(uint32_t), stream));
+    const OrderSelectParams p = params(pl, n_pos);
+    const int32_t blocks = (int32_t)std::max<int64_t>(
+        1, std::min<int64_t>((pl.n + 8 * kOrderThreads - 1) / (8 * kOrderThreads), 4 * (int64_t)std::max(n_cus, 1)));
+    if ((rc = tm.mark(0, stream))) return rc;
+    for (int32_t q = 0; q < passes; ++q) {
+      const int e = launch_order_pass(p, (passes - 1 - q) * kOrderDigitBits, blocks, stream);
+      if (e) return set_err(CL_E_DEVICE, "order kernels: %s", hipGetErrorString((hipError_t)e));
+    }
+    if ((rc = tm.mark(1, stream))) return rc;
+    ran |= 1;
+    return CL_OK;
+  }
+
+  // The final state of the positions: *out[j] for ranks[j] of the latest select.
+  int read_positions(int32_t n_pos, std::vector<OrderPos>* out, hipStream_t stream) {
+    out->resize((size_t)n_pos);
+    HIP_TRY(hipMemcpyAsync(out->data(), d_pos.p, (size_t)n_pos * sizeof(OrderPos), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (const OrderPos& z : *out)
+      if (z.bad) return set_err(CL_E_DEVICE, "order select: a digit histogram does not hold its rank");
+    return CL_OK;
+  }
+
+  // The first k (1 <= k <= the sample's size) elements of the order into insts[k], values[k].
+  int topk(const Plane& pl, int64_t k, int64_t* insts, int64_t* values, hipStream_t stream, int32_t n_cus) {
+    ran = 0;
+    int rc = select(pl, std::vector<int64_t>{k - 1}, stream, n_cus);
+    if (rc) return rc;
+    const OrderSelectParams p = params(pl, 1);
+    SelectParams c{};  // the select's compaction, over the two bitmaps in turn
+    c.base = pl.base;
+    c.words = (pl.lo + pl.n - pl.base + kWave - 1) / kWave;
+    c.cap = k;
+    const int64_t n_blocks = (c.words + kSelBlockWords - 1) / kSelBlockWords;
+    if ((rc = d_less.ensure((size_t)c.words)) || (rc = d_equal.ensure((size_t)c.words)) || (rc = d_cinfo.ensure(8)) ||
+        (rc = d_bsum.ensure((size_t)n_blocks)) || (rc = d_list_a.ensure((size_t)k)) ||
+        (rc = d_list_b.ensure((size_t)k)) || (rc = d_out_inst.ensure((size_t)k)) || (rc = d_out_val.ensure((size_t)k)))
+      return rc;
+    c.bsum = d_bsum.p;
+    HIP_TRY(hipMemsetAsync(d_cinfo.p, 0, 8 * sizeof(unsigned long long), stream));
+    if ((rc = tm.mark(2, stream))) return rc;
+    int e = launch_order_mark(p, c.words, d_less.p, d_equal.p, stream);
+    c.bitmap = d_less.p, c.info = d_cinfo.p, c.out = d_list_a.p;
+    if (!e) e = launch_select_compact(c, stream);
+    c.bitmap = d_equal.p, c.info = d_cinfo.p + 4, c.out = d_list_b.p;
+    if (!e) e = launch_select_compact(c, stream);
+    if (!e)
+      e = launch_order_gather(p, pl.lo, k, d_list_a.p, d_cinfo.p, d_list_b.p, d_cinfo.p + 4, d_out_inst.p, d_out_val.p,
+                              stream);
+    if (e) return set_err(CL_E_DEVICE, "order kernels: %s", hipGetErrorString((hipError_t)e));
+    if ((rc = tm.mark(3, stream))) return rc;
+    ran |= 2;
+    std::vector<long long> gi((size_t)k), gv((size_t)k);
+    HIP_TRY(hipMemcpyAsync(gi.data(), d_out_inst.p, (size_t)k * sizeof(long long), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(gv.data(), d_out_val.p, (size_t)k * sizeof(long long), hipMemcpyDeviceToHost, stream));
+    std::vector<OrderPos> pos;
+    if ((rc = read_positions(1, &pos, stream))) return rc;
+    // ---- the rows are those of the answer, each list in instance order: sorted here by (key, instance)
+    std::vector<int64_t> order((size_t)k);
+    for (int64_t j = 0; j < k; ++j) {
+      if (gi[(size_t)j] < 0) return set_err(CL_E_DEVICE, "order top-k: the lists hold fewer than %lld rows", (long long)k);
+      order[(size_t)j] = j;
+    }
+    const int32_t desc = pl.desc;
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+      const uint64_t ka = order_key(gv[(size_t)a], desc), kb = order_key(gv[(size_t)b], desc);
+      return ka != kb ? ka < kb : gi[(size_t)a] < gi[(size_t)b];
+    });
+    for (int64_t j = 0; j < k; ++j) {
+      insts[j] = gi[(size_t)order[(size_t)j]];
+      values[j] = gv[(size_t)order[(size_t)j]];
+    }
+    return CL_OK;
+  }
+
+  // values[j] = the value at position ranks[j] (any order, each below the sample's size), j < n_q.
+  int at_ranks(const Plane& pl, const int64_t* ranks, int32_t n_q, int64_t* values, hipStream_t stream, int32_t n_cus) {
+    ran = 0;
+    std::vector<int32_t> by((size_t)n_q);
+    for (int32_t j = 0; j < n_q; ++j) by[(size_t)j] = j;
+    std::sort(by.begin(), by.end(), [&](int32_t a, int32_t b) { return ranks[a] < ranks[b]; });
+    std::vector<int64_t> sorted((size_t)n_q);
+    for (int32_t j = 0; j < n_q; ++j) sorted[(size_t)j] = ranks[by[(size_t)j]];
+    int rc = select(pl, sorted, stream, n_cus);
+    if (rc) return rc;
+    std::vector<OrderPos> pos;
+    if ((rc = read_positions(n_q, &pos, stream))) return rc;
+    for (int32_t j = 0; j < n_q; ++j) values[by[(size_t)j]] = order_value(pos[(size_t)j].prefix, pl.desc);
+    return CL_OK;
+  }
+
+  // Device ms of the latest operation's stages (the stream is idle): select passes, compaction.
+  int stage_ms(double* select_ms, double* compact_ms) const {
+    *select_ms = *compact_ms = 0;
+    int rc;
+    if ((ran & 1) && (rc = tm.ms(0, 1, select_ms))) return rc;
+    if ((ran & 2) && (rc = tm.ms(2, 3, compact_ms))) return rc;
+    return CL_OK;
+  }
+};
+
+// The nearest-rank position of quantile num / den in a sample of `sample` > 0 values.
+static int64_t quantile_rank(const cl_quantile& q, int64_t sample) {
+  if (q.num == 0) return 0;
+  const unsigned __int128 prod = (unsigned __int128)(uint64_t)q.num * (uint64_t)sample;
+  return (int64_t)((prod + (uint64_t)q.den - 1) / (uint64_t)q.den) - 1;
+}
 
 struct Analytics {
   cl_sim* const sim;
@@ -62,6 +219,13 @@ struct Analytics {
   // joint distribution of two snapshot quantities (cl_snapshot_crosstab, cl_crosstab.hip): the result words
   DevBuf<long long> d_xt;
   DevTimer<2> xt;
+  // ordering (cl_snapshot_topk, cl_snapshot_quantiles, cl_snapshot_values; cl_order.hip): the value
+  // plane, its membership bitmap and the walk's info; the select and the compaction are the engine's.
+  // ord: the walk's event pair; ord.done: the latest call ran a walk.
+  DevBuf<long long> d_ord_plane, d_ord_info;
+  DevBuf<unsigned long long> d_ord_bits;
+  OrderEngine order;
+  DevTimer<2> ord;
 
   explicit Analytics(cl_sim* s) : sim(s) {}
   ~Analytics() {
@@ -440,6 +604,105 @@ struct Analytics {
     return CL_OK;
   }
 
+  // The value walk of the ordering calls (arguments checked by the caller; lo < hi): the term's
+  // value of every instance of [lo, hi) into d_ord_plane, the sample's membership into d_ord_bits,
+  // the counters into *info, and the plane as the engine takes it into *pl.
+  int order_walk(int64_t lo, int64_t hi, const cl_group_term* term, cl_iset* in, int32_t desc, cl_order_info* info,
+                 OrderEngine::Plane* pl) {
+    OrderWalkParams p{};
+    SimTables t{};
+    int rc = sample_begin(term->sid, lo, hi, &p.s, &t, in);
+    if (rc) return rc;
+    const hipStream_t stream = dev.stream;
+    const int64_t n = hi - lo;
+    p.tab = t;
+    std::memcpy(&p.term, term, sizeof p.term);
+    p.staged = sample_staged(p.s) && term->field != SEL_TICK;
+    p.base = lo / kWave * kWave;
+    const int64_t words = (hi - p.base + kWave - 1) / kWave;
+    if ((rc = d_ord_plane.ensure((size_t)n)) || (rc = d_ord_bits.ensure((size_t)words)) ||
+        (rc = d_ord_info.ensure(ORD_INFO_WORDS)))
+      return rc;
+    p.plane = d_ord_plane.p, p.bitmap = d_ord_bits.p, p.info = d_ord_info.p;
+    long long h[ORD_INFO_WORDS] = {0, 0, 0, INT64_MAX, INT64_MIN, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(d_ord_info.p, h, sizeof h, hipMemcpyHostToDevice, stream));
+    // block-major: the lanes OR their bits in; instance-major: every word is stored
+    if (p.s.blocked) HIP_TRY(hipMemsetAsync(d_ord_bits.p, 0, (size_t)words * sizeof(unsigned long long), stream));
+    const int32_t blocks = sample_grid(p.s.tile_hi - p.s.tile_lo, order_walk_lds_bytes(p.staged != 0));
+    if ((rc = ord.mark(0, stream))) return rc;
+    const int e = launch_order_walk(p, blocks, stream);
+    if (e) return set_err(CL_E_DEVICE, "order kernels: %s", hipGetErrorString((hipError_t)e));
+    if ((rc = ord.mark(1, stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(h, d_ord_info.p, sizeof h, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    ord.done = 1;
+    if (h[ORD_SAMPLE] < 0 || h[ORD_SAMPLE] > n)
+      return set_err(CL_E_DEVICE, "order: a sample of %lld of %lld instances", h[ORD_SAMPLE], (long long)n);
+    info->instances = h[ORD_INSTANCES], info->ok = h[ORD_OK], info->sample = h[ORD_SAMPLE];
+    *pl = OrderEngine::Plane{d_ord_plane.p, d_ord_bits.p, n, lo, p.base, h[ORD_MIN], h[ORD_MAX], desc};
+    return CL_OK;
+  }
+
+  // cl_snapshot_topk (arguments checked by the caller).
+  int topk(int64_t lo, int64_t hi, const cl_group_term* term, int32_t flags, int64_t k, int64_t* insts,
+           int64_t* values, cl_order_info* info, cl_iset* in) {
+    *info = cl_order_info{};
+    ord.done = order.ran = 0;
+    if (hi == lo) return flush_only(term->sid, in);
+    OrderEngine::Plane pl{};
+    int rc = order_walk(lo, hi, term, in, (flags & kOrderDesc) != 0, info, &pl);
+    if (rc) return rc;
+    info->n_returned = std::min(k, info->sample);
+    if (info->n_returned == 0) return CL_OK;
+    return order.topk(pl, info->n_returned, insts, values, dev.stream, dev.n_cus);
+  }
+
+  // cl_snapshot_quantiles (arguments checked by the caller).
+  int quantiles(int64_t lo, int64_t hi, const cl_group_term* term, const cl_quantile* q, int32_t n_q, int64_t* values,
+                int64_t* ranks, cl_order_info* info, cl_iset* in) {
+    *info = cl_order_info{};
+    ord.done = order.ran = 0;
+    OrderEngine::Plane pl{};
+    int rc = hi == lo ? flush_only(term->sid, in) : order_walk(lo, hi, term, in, 0, info, &pl);
+    if (rc) return rc;
+    if (info->sample == 0) {
+      for (int32_t j = 0; j < n_q; ++j) ranks[j] = -1;
+      return CL_OK;
+    }
+    for (int32_t j = 0; j < n_q; ++j) ranks[j] = quantile_rank(q[j], info->sample);
+    info->n_returned = n_q;
+    return order.at_ranks(pl, ranks, n_q, values, dev.stream, dev.n_cus);
+  }
+
+  // cl_snapshot_values (arguments checked by the caller).
+  int values_of(int64_t lo, int64_t hi, const cl_group_term* term, int64_t* values, uint8_t* in_sample, cl_iset* in) {
+    ord.done = order.ran = 0;
+    if (hi == lo) return flush_only(term->sid, in);
+    cl_order_info info{};
+    OrderEngine::Plane pl{};
+    int rc = order_walk(lo, hi, term, in, 0, &info, &pl);
+    if (rc) return rc;
+    const hipStream_t stream = dev.stream;
+    HIP_TRY(hipMemcpyAsync(values, d_ord_plane.p, (size_t)pl.n * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    std::vector<unsigned long long> bits;
+    if (in_sample) {
+      bits.resize((size_t)((hi - pl.base + kWave - 1) / kWave));
+      HIP_TRY(hipMemcpyAsync(bits.data(), d_ord_bits.p, bits.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                             stream));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (in_sample)
+      for (int64_t i = lo; i < hi; ++i) in_sample[i - lo] = (uint8_t)((bits[(size_t)((i - pl.base) >> 6)] >> ((i - pl.base) & 63)) & 1);
+    return CL_OK;
+  }
+
+  // An empty range: what is pending is executed, as in every other result query; nothing is walked.
+  int flush_only(int32_t sid, cl_iset* in) {
+    SampleParams s{};
+    SimTables t{};
+    return sample_begin(sid, 0, 0, &s, &t, in);
+  }
+
   // ---- instance sets (cl_iset) -------------------------------------------------------------------
   cl_iset* iset_new() {
     cl_iset* s = new cl_iset();
@@ -582,6 +845,7 @@ int64_t analytics_device_bytes(const Analytics* a) {
   int64_t b = a->d_sel_bits.bytes() + a->d_sel_info.bytes() + a->d_sel_bsum.bytes() + a->d_sel_out.bytes() +
               a->d_sel_ticks.bytes();
   for (const cl_iset* s : a->isets) b += s->bits.bytes();
+  b += a->d_ord_plane.bytes() + a->d_ord_info.bytes() + a->d_ord_bits.bytes() + a->order.bytes();  // the ordering calls
   return b + a->d_is_list.bytes() + a->d_is_count.bytes() + a->d_xt.bytes() + a->d_gr_first.bytes() +
          a->d_gr_vals.bytes();
 }
@@ -799,6 +1063,76 @@ static int crosstab_call(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, bool con
 
 static_assert(CL_ISET_AND == ISET_AND && CL_ISET_OR == ISET_OR && CL_ISET_ANDNOT == ISET_ANDNOT,
               "CL_ISET_* mirror cl_analytics.h");
+
+static_assert(CL_ORDER_DESC == kOrderDesc && CL_ORDER_MAX_K == kOrderMaxK && CL_ORDER_MAX_QUANTILES == kOrderMaxPos &&
+                  sizeof(cl_quantile) == 16 && sizeof(cl_order_info) == 32,
+              "CL_ORDER_* mirror cl_analytics.h");
+
+// What the three ordering calls share, after the call's own arguments: the set, the term (fields up
+// to max_field), the range, its size, a sim that has run something, the term's sid.
+static int order_args_ok(const cl_sim* sim, bool conditional, const cl_iset* in, const cl_group_term* term,
+                         int32_t max_field, const char* what, int64_t inst_lo, int64_t inst_hi) {
+  if (conditional)
+    if (const int rc = iset_arg_ok(sim, in)) return rc;
+  if (!term) return set_err(CL_E_INVALID, "%s: null term", what);
+  const SimFacts f = sim_facts(sim);
+  if (term->reserved) return set_err(CL_E_INVALID, "%s term: non-zero reserved", what);
+  if (!quantity_ok(term->field, term->index, max_field, f.n_nodes, f.n_ch))
+    return set_err(CL_E_INVALID, "%s term: field %d is not one of CL_SEL_TICK .. %s, or index %d out of range", what,
+                   term->field, max_field == SEL_KEY ? "CL_SEL_KEY" : "CL_SEL_CH_TOK", term->index);
+  if (inst_lo < 0 || inst_hi > f.n_inst || inst_lo > inst_hi) return set_err(CL_E_INVALID, "instance range out of range");
+  if (inst_hi - inst_lo > ((int64_t)1 << 29)) return set_err(CL_E_LIMIT, "%s of more than 2^29 instances", what);
+  if (!f.ran) return set_err(CL_E_STATE, "nothing has run yet: no event was issued");
+  if (term->sid < 0 || term->sid >= f.n_sids) return set_err(CL_E_INVALID, "%s term: snapshot id out of range", what);
+  return CL_OK;
+}
+
+static int order_k_ok(int32_t flags, int64_t k, const int64_t* insts, const int64_t* values) {
+  if (flags & ~CL_ORDER_DESC) return set_err(CL_E_INVALID, "top-k: unknown flag bits");
+  if (k < 0 || k > CL_ORDER_MAX_K || (k > 0 && (!insts || !values)))
+    return set_err(CL_E_INVALID, "top-k: 0 <= k <= %d, with index and value arrays when k > 0", CL_ORDER_MAX_K);
+  return CL_OK;
+}
+
+static int order_q_ok(const cl_quantile* q, int32_t n_q, const int64_t* values, const int64_t* ranks) {
+  if (n_q < 1 || n_q > CL_ORDER_MAX_QUANTILES || !q || !values || !ranks)
+    return set_err(CL_E_INVALID, "quantiles: 1 <= n_q <= %d, with quantile, value and rank arrays",
+                   CL_ORDER_MAX_QUANTILES);
+  for (int32_t j = 0; j < n_q; ++j)
+    if (q[j].den < 1 || q[j].num < 0 || q[j].num > q[j].den)
+      return set_err(CL_E_INVALID, "quantile %d: den >= 1 and 0 <= num <= den", j);
+  return CL_OK;
+}
+
+// cl_snapshot_topk, and cl_snapshot_topk_in with its set (`conditional`).
+static int topk_call(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, bool conditional, const cl_iset* in,
+                     const cl_group_term* term, int32_t flags, int64_t k, int64_t* insts, int64_t* values,
+                     cl_order_info* info) {
+  SIM_CALL(sim);
+  // every argument is checked before any device work
+  if (!info) return set_err(CL_E_INVALID, "top-k: null info");
+  int rc = order_k_ok(flags, k, insts, values);
+  if (rc || (rc = order_args_ok(sim, conditional, in, term, SEL_CH_TOK, "top-k", inst_lo, inst_hi))) return rc;
+  return sim_analytics(sim)->topk(inst_lo, inst_hi, term, flags, k, insts, values, info, const_cast<cl_iset*>(in));
+}
+
+static int quantiles_call(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, bool conditional, const cl_iset* in,
+                          const cl_group_term* term, const cl_quantile* q, int32_t n_q, int64_t* values,
+                          int64_t* ranks, cl_order_info* info) {
+  SIM_CALL(sim);
+  if (!info) return set_err(CL_E_INVALID, "quantiles: null info");
+  int rc = order_q_ok(q, n_q, values, ranks);
+  if (rc || (rc = order_args_ok(sim, conditional, in, term, SEL_CH_TOK, "quantiles", inst_lo, inst_hi))) return rc;
+  return sim_analytics(sim)->quantiles(inst_lo, inst_hi, term, q, n_q, values, ranks, info, const_cast<cl_iset*>(in));
+}
+
+static int values_call(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, bool conditional, const cl_iset* in,
+                       const cl_group_term* term, int64_t* values, uint8_t* in_sample) {
+  SIM_CALL(sim);
+  if (!values && inst_hi > inst_lo) return set_err(CL_E_INVALID, "values: null output");
+  if (const int rc = order_args_ok(sim, conditional, in, term, SEL_KEY, "values", inst_lo, inst_hi)) return rc;
+  return sim_analytics(sim)->values_of(inst_lo, inst_hi, term, values, in_sample, const_cast<cl_iset*>(in));
+}
 
 static int iset_range_ok(const cl_iset* s, int64_t lo, int64_t hi) {
   if (lo < 0 || hi > sim_facts(s->sim).n_inst || lo > hi) return set_err(CL_E_INVALID, "instance range out of range");
@@ -1026,6 +1360,112 @@ int cl_iset_destroy(cl_iset* set) {
 
 int cl_iset_time(cl_sim* sim, double* device_ms) {
   return pair_time(sim, &Analytics::is, "no instance set kernel has run", device_ms);
+}
+
+// ---- ordering: top-k, quantiles, values -----------------------------------------------------------
+int cl_snapshot_topk(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_group_term* term, int32_t flags,
+                     int64_t k, int64_t* insts, int64_t* values, cl_order_info* info) {
+  return topk_call(sim, inst_lo, inst_hi, false, nullptr, term, flags, k, insts, values, info);
+}
+
+int cl_snapshot_topk_in(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_iset* in, const cl_group_term* term,
+                        int32_t flags, int64_t k, int64_t* insts, int64_t* values, cl_order_info* info) {
+  return topk_call(sim, inst_lo, inst_hi, true, in, term, flags, k, insts, values, info);
+}
+
+int cl_snapshot_quantiles(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_group_term* term,
+                          const cl_quantile* q, int32_t n_q, int64_t* values, int64_t* ranks, cl_order_info* info) {
+  return quantiles_call(sim, inst_lo, inst_hi, false, nullptr, term, q, n_q, values, ranks, info);
+}
+
+int cl_snapshot_quantiles_in(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_iset* in,
+                             const cl_group_term* term, const cl_quantile* q, int32_t n_q, int64_t* values,
+                             int64_t* ranks, cl_order_info* info) {
+  return quantiles_call(sim, inst_lo, inst_hi, true, in, term, q, n_q, values, ranks, info);
+}
+
+int cl_snapshot_values(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_group_term* term, int64_t* values,
+                       uint8_t* in_sample) {
+  return values_call(sim, inst_lo, inst_hi, false, nullptr, term, values, in_sample);
+}
+
+int cl_snapshot_values_in(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_iset* in, const cl_group_term* term,
+                          int64_t* values, uint8_t* in_sample) {
+  return values_call(sim, inst_lo, inst_hi, true, in, term, values, in_sample);
+}
+
+int cl_order_stage_times(cl_sim* sim, double* stage_ms) {
+  SIM_CALL(sim);
+  if (!stage_ms) return set_err(CL_E_INVALID, "null output");
+  const Analytics* a = sim_analytics(sim);
+  if (!a->ord.done) return set_err(CL_E_STATE, "no top-k, quantiles or values call has run");
+  int rc = a->marks_done();
+  if (rc) return rc;
+  // the value walk, the select passes, the compaction
+  if ((rc = a->ord.ms(0, 1, &stage_ms[0])) || (rc = a->order.stage_ms(&stage_ms[1], &stage_ms[2]))) return rc;
+  return CL_OK;
+}
+
+int cl_order_time(cl_sim* sim, double* device_ms) {
+  if (!device_ms) return set_err(CL_E_INVALID, "null output");
+  double ms[3];
+  const int rc = cl_order_stage_times(sim, ms);
+  if (rc) return rc;
+  *device_ms = ms[0] + ms[1] + ms[2];
+  return CL_OK;
+}
+
+int cl_order_plane_device(int32_t device, const int64_t* values, const uint8_t* in_sample, int64_t n, int32_t flags,
+                          int64_t k, int64_t* insts, int64_t* vals, int64_t* n_returned, const cl_quantile* q,
+                          int32_t n_q, int64_t* q_values, int64_t* q_ranks, double* device_ms) {
+  if (n < 1 || n > ((int64_t)1 << 29) || !values || !n_returned)
+    return set_err(CL_E_INVALID, "order plane: 1 <= n <= 2^29 values, with an output for n_returned");
+  int rc = order_k_ok(flags, k, insts, vals);
+  if (rc || (n_q != 0 && (rc = order_q_ok(q, n_q, q_values, q_ranks)))) return rc;
+  hipDeviceProp_t prop;
+  if ((rc = open_gfx950(device, &prop))) return rc;
+  // the plane as the value walk leaves it: the bitmap, the sample's size, minimum and maximum
+  std::vector<unsigned long long> bits((size_t)((n + kWave - 1) / kWave), 0);
+  int64_t sample = 0;
+  long long vmin = INT64_MAX, vmax = INT64_MIN;
+  for (int64_t i = 0; i < n; ++i) {
+    if (in_sample && !in_sample[i]) continue;
+    bits[(size_t)(i >> 6)] |= 1ULL << (i & 63);
+    ++sample;
+    vmin = std::min<long long>(vmin, values[i]);
+    vmax = std::max<long long>(vmax, values[i]);
+  }
+  struct Scratch {  // (the buffers and the engine free themselves on every return path)
+    DevBuf<long long> plane;
+    DevBuf<unsigned long long> bits;
+    OrderEngine order;
+    hipStream_t stream = nullptr;
+    ~Scratch() {
+      if (stream) (void)hipStreamDestroy(stream);
+    }
+  } s;
+  if ((rc = s.plane.ensure((size_t)n)) || (rc = s.bits.ensure(bits.size()))) return rc;
+  HIP_TRY(hipMemcpy(s.plane.p, values, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s.bits.p, bits.data(), bits.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+  HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+  const int32_t n_cus = prop.multiProcessorCount;
+  double total = 0, a = 0, b = 0;
+  OrderEngine::Plane pl{s.plane.p, s.bits.p, n, 0, 0, vmin, vmax, (flags & CL_ORDER_DESC) != 0};
+  *n_returned = std::min(k, sample);
+  if (*n_returned > 0) {
+    if ((rc = s.order.topk(pl, *n_returned, insts, vals, s.stream, n_cus)) || (rc = s.order.stage_ms(&a, &b))) return rc;
+    total += a + b;
+  }
+  for (int32_t j = 0; j < n_q; ++j) q_ranks[j] = sample ? quantile_rank(q[j], sample) : -1;
+  if (n_q > 0 && sample > 0) {
+    pl.desc = 0;  // (quantiles are positions of the ascending order)
+    if ((rc = s.order.at_ranks(pl, q_ranks, n_q, q_values, s.stream, n_cus)) || (rc = s.order.stage_ms(&a, &b)))
+      return rc;
+    total += a + b;
+  }
+  if (device_ms) *device_ms = total;
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  return CL_OK;
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// cl_analytics.h -- the batch analytics of the batch engine: what their kernels (cl_stats.hip,
+// cl_analytics.h -- the batch analytics of the batch engine: what their kernels (cl_stats.hip, cl_order.hip,
 // cl_census.hip, cl_select.hip, cl_iset.hip, cl_crosstab.hip, cl_groups.hip) and their host layer
 // (cl_analytics.cpp) share.  Declarations and host-and-device inline functions only; the device
 // code of the sample walk is cl_sample.h, of a snapshot quantity cl_quantity.h.  No exec kernel
@@ -327,5 +327,76 @@ int launch_groups_keys(const GroupsParams& p, int32_t blocks, void* stream);
 // of block-major records (SimTables::rec_slot), nullptr when they are instance-major.
 int launch_groups_values(const GroupsParams& p, const int32_t* rec_slot, const long long* first, int64_t n,
                          long long* values, void* stream);
+
+// ---- ordering a batch: top-k and exact quantiles (cl_order.hip; include/clsnap.h cl_snapshot_topk) ----
+// One quantity (SEL_TICK .. SEL_KEY) of one snapshot id over the sample of cl_snapshot_stats, as an
+// int64 value plane [hi - lo] and a membership bitmap in the select bitmap's convention; a radix
+// select on the plane finds the key at given order positions; the top-k is compacted with the
+// select's compaction.  The order is ascending by (key, instance), key = order_key(value).
+constexpr int32_t kOrderDesc = 1;
+constexpr int64_t kOrderMaxK = 65536;
+constexpr int32_t kOrderMaxPos = 64;     // order positions one select resolves (the quantiles of a call)
+constexpr int32_t kOrderDigitBits = 8, kOrderBins = 1 << kOrderDigitBits;
+constexpr int32_t kOrderThreads = 256;
+// The value with its sign bit flipped, complemented for descending: unsigned order of the keys is
+// the order asked for.  order_value is its inverse.
+ANALYTICS_HD inline uint64_t order_key(int64_t v, int32_t desc) {
+  const uint64_t k = (uint64_t)v ^ 0x8000000000000000ULL;
+  return desc ? ~k : k;
+}
+ANALYTICS_HD inline int64_t order_value(uint64_t k, int32_t desc) {
+  return (int64_t)((desc ? ~k : k) ^ 0x8000000000000000ULL);
+}
+// Words of the walk's info: the three counters, then the sample's min and max value (the host
+// initialises them to INT64_MAX / INT64_MIN).
+enum : int32_t { ORD_INSTANCES = 0, ORD_OK = 1, ORD_SAMPLE = 2, ORD_MIN = 3, ORD_MAX = 4, ORD_INFO_WORDS = 8 };
+struct OrderWalkParams {
+  SampleParams s;            // the walk of the term's snapshot (s.sid == term.sid)
+  RecordTables tab;
+  GroupTerm term;
+  int32_t staged;            // sample_staged(s) and the term reads the records
+  long long* plane;          // [hi - lo] value of instance lo + i (0 outside the sample)
+  // Membership bitmap: bit (inst - base) & 63 of word (inst - base) >> 6, base = lo rounded down to a
+  // multiple of 64.  Block-major: zeroed before the pass.
+  int64_t base;
+  unsigned long long* bitmap;
+  long long* info;           // [ORD_INFO_WORDS]
+};
+inline int32_t order_walk_lds_bytes(bool staged) {
+  return 8 * 8 + (staged ? kWavesPerBlock * kStatsStageWords * 4 : 0);
+}
+int launch_order_walk(const OrderWalkParams& p, int32_t blocks, void* stream);
+
+// An order position the select resolves: after a digit pass, `prefix` is the bits of its key from the
+// pass's digit up, `rank` its position among the candidates that share that prefix, `group` the index
+// of its prefix among the distinct prefixes of the positions (which are kept by ascending rank, so
+// the distinct prefixes ascend with the group index).
+struct OrderPos {
+  unsigned long long prefix;
+  long long rank;
+  int32_t group, bad;        // bad: no bucket held the rank (the histogram and the rank disagree)
+};
+struct OrderSelectParams {
+  const long long* plane;            // [n]
+  const unsigned long long* bitmap;  // element i is bit i + off (off = lo - base, < 64)
+  int64_t n, off;
+  int32_t desc, n_pos;
+  OrderPos* pos;                     // [n_pos]
+  uint32_t* hist;                    // [n_pos][kOrderBins], zero before the first pass
+};
+inline int32_t order_hist_lds_bytes(int32_t n_pos) { return n_pos * (kOrderBins * 4 + 8); }
+// One digit pass at bit `shift`: the histogram kernel (blocks workgroups), then the one-workgroup
+// choice, which also regroups the positions and zeroes the histogram for the next pass.
+int launch_order_pass(const OrderSelectParams& p, int32_t shift, int32_t blocks, void* stream);
+// Top-k compaction.  less[w] / equal[w]: the members with key < T / key == T, T = pos[0].prefix after
+// the last pass, as bitmaps of `words` words in the membership bitmap's convention.
+int launch_order_mark(const OrderSelectParams& p, int64_t words, unsigned long long* less, unsigned long long* equal,
+                      void* stream);
+// out_inst[j], out_val[j], j < k: all of list_a (n_a = info_a[3] entries) then the first k - n_a of
+// list_b; the values gathered from the plane (instance lo + i at plane[i]); -1 / 0 where a list is
+// short or an instance lies outside [lo, lo + n).
+int launch_order_gather(const OrderSelectParams& p, int64_t lo, int64_t k, const long long* list_a,
+                        const unsigned long long* info_a, const long long* list_b, const unsigned long long* info_b,
+                        long long* out_inst, long long* out_val, void* stream);
 
 }  // namespace clsnap

@@ -160,6 +160,35 @@ def gather_selection(sel, first_instance, device):
     return out
 
 
+def gather_topk(top, first_instance, device):
+    """A rank's SnapshotTopK (ChandyLamportSim.snapshot_topk of its shard, whose instance 0 is
+    global instance `first_instance`) combined over all ranks, in the manner of gather_selection:
+    one all_gather of the heads sizes one all_gather of the (instance, value) rows padded to the
+    longest, and the parts merge with each rank's first instance as offset (SnapshotTopK.merge,
+    which is exact: the top-k of a union lies within the union of the parts' top-k).  Every rank
+    passes the same term, direction and k.  Returns a new SnapshotTopK, the same on every rank,
+    with global instance indices; without an initialised group, a copy."""
+    cls = type(top)
+    mine = cls(top.term.copy(), top.descending, top.k, top.instances, top.ok, top.sample, top.insts.copy(),
+               top.values.copy())
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return mine
+    head = allgather_ints([mine.n_returned, first_instance, mine.instances, mine.ok, mine.sample], device)
+    rows = np.zeros((max(int(head[:, 0].max()), 1), 2), dtype=np.int64)
+    rows[:mine.n_returned, 0] = mine.insts
+    rows[:mine.n_returned, 1] = mine.values
+    t = torch.from_numpy(rows).to(device)
+    parts = [torch.empty_like(t) for _ in range(dist.get_world_size())]
+    dist.all_gather(parts, t)
+    out = cls(mine.term.copy(), mine.descending, mine.k, 0, 0, 0, rows[:0, 0], rows[:0, 1])
+    for r, part in enumerate(parts):
+        k, first, instances, ok, sample = (int(v) for v in head[r])
+        got = part.cpu().numpy()[:k]
+        out = out.merge(cls(mine.term.copy(), mine.descending, mine.k, instances, ok, sample, got[:, 0], got[:, 1]),
+                        offset=first)
+    return out
+
+
 # ---- exchange layer of the graph-partitioned mode (DESIGN.md §11) ---------------------
 # One simulation whose nodes are split into rank ranges exchanges, every tick, records
 # addressed to the owners of other nodes (deliveries, broadcast-trigger reports, draw

@@ -665,6 +665,86 @@ int cl_groups_time(cl_sim* sim, double* device_ms);
 int cl_groups_stage_times(cl_sim* sim, double* stage_ms);
 uint64_t cl_group_key(const int64_t* values, int32_t n);
 
+/* ---- ordering a batch: top-k instances and exact quantiles of a snapshot quantity -------------
+ * ORDER BY q LIMIT k, and the exact percentile of q, over the sample of one snapshot: "which 16
+ * runs finished snapshot 0 last", "the median and p99 of the tokens in flight".  The list feeds
+ * cl_collect_snapshot_list and cl_iset_from_list; cl_set_delay_go_seed_list(seed_base + insts)
+ * re-runs exactly those instances.
+ *
+ * Term.  (sid, field, index) as a cl_group_term: the meaning and the `index` rule of
+ * cl_select_clause.  The ordering calls (top-k, quantiles) take CL_SEL_TICK .. CL_SEL_CH_TOK and
+ * refuse CL_SEL_KEY: a hash has no order worth asking for.  cl_snapshot_values takes CL_SEL_KEY
+ * too, as the int64 bit pattern of the hash.
+ *
+ * Sample.  As everywhere: the instances of [inst_lo, inst_hi) with status CL_INST_OK in which
+ * snapshot `sid` completed (the _in forms: that are also members of `in`).  info->instances and
+ * info->ok count the range.
+ *
+ * Order.  Total and deterministic: ascending by (value, instance); with CL_ORDER_DESC by value
+ * descending, instance still ascending.  Ties always go to the smaller instance index, whatever
+ * the record layout, the slot map, the grid or the exec kernel.
+ *
+ * cl_snapshot_topk       the first n_returned = min(k, sample) instances of that order: insts[]
+ *     absolute instance indices, values[] their values.  0 <= k <= CL_ORDER_MAX_K; k == 0 with NULL
+ *     arrays only counts.
+ * cl_snapshot_quantiles  n_q quantiles q[j] = num / den (den >= 1, 0 <= num <= den), 1 <= n_q <=
+ *     CL_ORDER_MAX_QUANTILES, by the nearest-rank rule
+ *         r = num == 0 ? 0 : ceil(num * sample / den) - 1      (the product exact, in 128 bits)
+ *     values[j] = the value at position r of the ascending order, ranks[j] = r.  On an empty sample
+ *     ranks[j] = -1, values is untouched and n_returned = 0; else n_returned = n_q.
+ * cl_snapshot_values     the bulk form of cl_snapshot_ticks for any quantity: values[i - inst_lo] =
+ *     the value for a sample instance and 0 for the others, in_sample[i - inst_lo] (may be NULL) 1 or 0.
+ * The _in forms take the sample from the members of `in`; with a set holding the whole batch each
+ * returns byte for byte what the unconditional call returns.
+ *
+ * Errors, all found before any device work, nothing written:
+ *   CL_E_INVALID  a NULL sim, term or info; a field outside the call's range, an index out of range
+ *                 for its field, a non-zero reserved; unknown flag bits; k outside [0, CL_ORDER_MAX_K];
+ *                 NULL arrays with k > 0; a quantile with den < 1 or num outside [0, den], n_q outside
+ *                 [1, CL_ORDER_MAX_QUANTILES], NULL q, values or ranks; the instance range or sid out
+ *                 of bounds; (_in) a NULL set or a set of another sim
+ *   CL_E_STATE    no event was ever issued
+ *   CL_E_LIMIT    more than 2^29 instances in the range
+ * inst_lo == inst_hi is the empty sample.  Like the other result queries the calls execute pending
+ * events and never add a tick, hold the sim's lock and wait for a split replay's second half.  Their
+ * scratch (the value plane, bitmaps, lists) is counted by cl_device_bytes.  Only the info, 16 *
+ * n_returned bytes and a few words per digit pass cross to the host; cl_snapshot_values copies the
+ * plane.  cl_order_time: device ms (HIP events) of the latest call's kernels; cl_order_stage_times:
+ * ms[3] = the value walk, the select passes, the compaction (0 for a stage the call did not run);
+ * CL_E_STATE before any call. */
+#define CL_ORDER_DESC 1           /* flag: value descending (instance still ascending) */
+#define CL_ORDER_MAX_K 65536
+#define CL_ORDER_MAX_QUANTILES 64
+typedef struct { int64_t instances, ok, sample, n_returned; } cl_order_info;
+typedef struct { int64_t num, den; } cl_quantile;   /* 16 B */
+int cl_snapshot_topk(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_group_term* term, int32_t flags,
+                     int64_t k, int64_t* insts /* [k] or NULL iff k == 0 */, int64_t* values /* [k] likewise */,
+                     cl_order_info* info);
+int cl_snapshot_topk_in(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_iset* in, const cl_group_term* term,
+                        int32_t flags, int64_t k, int64_t* insts, int64_t* values, cl_order_info* info);
+int cl_snapshot_quantiles(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_group_term* term,
+                          const cl_quantile* q, int32_t n_q, int64_t* values /* [n_q] */, int64_t* ranks /* [n_q] */,
+                          cl_order_info* info);
+int cl_snapshot_quantiles_in(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_iset* in,
+                             const cl_group_term* term, const cl_quantile* q, int32_t n_q, int64_t* values,
+                             int64_t* ranks, cl_order_info* info);
+int cl_snapshot_values(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_group_term* term,
+                       int64_t* values /* [hi-lo] */, uint8_t* in_sample /* [hi-lo] or NULL */);
+int cl_snapshot_values_in(cl_sim* sim, int64_t inst_lo, int64_t inst_hi, const cl_iset* in,
+                          const cl_group_term* term, int64_t* values, uint8_t* in_sample);
+int cl_order_time(cl_sim* sim, double* device_ms);
+int cl_order_stage_times(cl_sim* sim, double* stage_ms /* [3] */);
+/* Engine-internal test aid (needs a gfx950 device, CL_E_DEVICE otherwise), like
+ * cl_go_delay_schedule_device: uploads a plane of n int64 values (in_sample[i] != 0: element i is in
+ * the sample; NULL: all are) and runs exactly the select and compaction kernels of the calls above
+ * on it, element index = instance.  Snapshot quantities are non-negative and below 2^31; this is the
+ * only way to pin the kernels over the whole int64 range.  k, insts, vals as in cl_snapshot_topk
+ * (*n_returned = min(k, sample)); q, n_q, q_values, q_ranks as in cl_snapshot_quantiles (n_q == 0: no
+ * quantiles).  *device_ms (may be NULL): the kernels' time. */
+int cl_order_plane_device(int32_t device, const int64_t* values, const uint8_t* in_sample, int64_t n, int32_t flags,
+                          int64_t k, int64_t* insts, int64_t* vals, int64_t* n_returned, const cl_quantile* q,
+                          int32_t n_q, int64_t* q_values, int64_t* q_ranks, double* device_ms);
+
 /* ---- device event trace: the reference's debug Logger (logger.go:12-76) ---- */
 /* One LogEvent (logger.go:18-23) per record, in the Logger's order.  Node ranks refer
  * to cl_node_id; `other` is the peer of a Sent/Received record (-1 for Start/End and
