@@ -1075,12 +1075,20 @@ int cl_add_node(cl_sim* sim, const char* id, int64_t tokens) {
   if (sim->frozen) return set_err(CL_E_STATE, "AddNode after events started is not supported");
   if (sim->node_of(id) >= 0) return set_err(CL_E_DUPLICATE_NODE, "node %s already exists", id);
   if (tokens < INT32_MIN || tokens > INT32_MAX) return set_err(CL_E_LIMIT, "token count out of int32 range");
+  // A node never drops below min(initial, 0) (send_one refuses a send it cannot cover), so none
+  // exceeds its initial tokens plus the others' positive ones: every node word stays in int32 iff
+  // the positive initial tokens sum to at most INT32_MAX; the total itself must also fit (checksums).
+  // All checks come before the node is recorded: a refused call leaves the sim as it was.
+  int64_t total = tokens, positive = tokens > 0 ? tokens : 0;
+  for (auto t : sim->init_tokens) {
+    total += t;
+    if (t > 0) positive += t;
+  }
+  if (positive > INT32_MAX) return set_err(CL_E_LIMIT, "positive token counts sum past int32 range");
+  if (total < INT32_MIN) return set_err(CL_E_LIMIT, "total tokens out of int32 range");
   sim->id_index[id] = (int)sim->ids.size();
   sim->ids.emplace_back(id);
   sim->init_tokens.push_back(tokens);
-  int64_t total = 0;
-  for (auto t : sim->init_tokens) total += t;
-  if (total > INT32_MAX || total < INT32_MIN) return set_err(CL_E_LIMIT, "total tokens out of int32 range");
   return CL_OK;
 }
 

@@ -96,7 +96,10 @@ int cl_sim_create(int64_t n_instances, cl_sim** out);
  * them to leave before freeing the sim; no other call may overlap it. */
 int cl_sim_destroy(cl_sim* sim);
 
-/* AddNode (sim.go:40-43; node.go:45-55). Token counts must fit int32 in total. */
+/* AddNode (sim.go:40-43; node.go:45-55). Each token count is an int32, negative allowed. The
+ * positive counts of all nodes must sum to at most INT32_MAX (a node never drops below min(start, 0), so
+ * none exceeds its start plus the others' positive counts: every node word stays in int32) and
+ * the total must be at least INT32_MIN: CL_E_LIMIT otherwise. A refused call adds nothing. */
 int cl_add_node(cl_sim* sim, const char* id, int64_t tokens);
 /* AddLink (sim.go:46-56; node.go:87-94): self links ignored, duplicates replace. */
 int cl_add_link(cl_sim* sim, const char* src, const char* dest);
