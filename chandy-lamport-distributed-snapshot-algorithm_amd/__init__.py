@@ -132,6 +132,7 @@ def lib():
         "cl_lanes_compile_check": [vp, vp, vp, i64],
         "cl_set_program_kernels": [vp, i32],
         "cl_exec_program_kernels": [vp, vp],
+        "cl_exec_program_cover": [vp, vp],
         "cl_lanes_program_compile_check": [vp, vp, vp, vp, i64],
         "cl_stats_layout_of": [vp, vp, vp],
         "cl_snapshot_stats": [vp, i32, i64, i64, vp, vp, i64],
@@ -1769,6 +1770,12 @@ class ChandyLamportSim:
     def exec_program_kernels(self):
         """True when the most recent launch ran program-specialized kernels."""
         return bool(self._i32(self._L.cl_exec_program_kernels))
+
+    def exec_program_cover(self):
+        """True when the program-specialized kernels of the most recent launch, or of a later
+        lanes_program_compile_check(), were compiled for delay rows that hold every draw the
+        program can make (no row-end test in their broadcast guard) -- cl_exec_program_cover."""
+        return bool(self._i32(self._L.cl_exec_program_cover))
 
     def lanes_program_compile_check(self):
         """Compile the kernels specialized on the current program without a device: (compile ms,

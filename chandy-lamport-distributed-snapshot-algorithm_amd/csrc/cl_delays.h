@@ -51,6 +51,8 @@ class DelaySource {
     const int64_t d = go_seeds_ ? draws_needed : user_draws_;
     return std::max<int64_t>(16, (d + 15) / 16 * 16);
   }
+  // ... and the valid draws of those rows, as rows().draws has them after ensure(need).
+  int64_t draws_for(int64_t draws_needed) const { return go_seeds_ ? row_for(draws_needed) : user_draws_; }
   // Makes rows for `need` draws resident, on dev.stream.  *rewritten: the plane was (or was about
   // to be) written, so what the caller derived from the old rows is void.
   int ensure(const SimDevice& dev, int64_t n_inst, int64_t need, bool* rewritten);

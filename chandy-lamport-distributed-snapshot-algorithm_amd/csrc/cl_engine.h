@@ -355,6 +355,12 @@ struct ExecLaunch {
   // the generic kernels; *prog_used is set to 1 when the specialized kernels were launched
   const Op* prog;
   int32_t* prog_used;
+  // (with prog) the most delays an instance of the program can draw (cl_host.cpp draws_needed);
+  // 0: not given.  Where the rows hold that many, the specialized kernels are compiled with the
+  // program type's COVER (cl_lanes.h Guard); *cover_used (may be null) is set to 1 when the
+  // launched kernels were, else to 0
+  int64_t prog_draws;
+  int32_t* cover_used;
 };
 int launch_exec(const ExecParams& p, const uint32_t* topo, const Op* ops, const uint8_t* sched, const ExecLaunch& L);
 // The instance-per-lane kernel (cl_lanes.h, compiled per topology by cl_jit.cpp): lanes_fit
@@ -386,8 +392,11 @@ void lanes_jit_stats(double* compile_ms, int64_t* compiles);
 #if !defined(__HIPCC_RTC__)
 #include <string>
 namespace clsnap {
-// (prog: the program-specialized kernels of the device program [0, n_prog) instead)
-int lanes_compile_only(const ExecParams& p, double* ms, std::string* log, const Op* prog = nullptr, int n_prog = 0);
+// (prog: the program-specialized kernels of the device program [0, n_prog) instead, for rows of
+// p.draws delays and a program that draws at most prog_draws, as ExecLaunch::prog_draws;
+// *cover: whether they were compiled with the program type's COVER)
+int lanes_compile_only(const ExecParams& p, double* ms, std::string* log, const Op* prog = nullptr, int n_prog = 0,
+                       int64_t prog_draws = 0, int32_t* cover = nullptr);
 }  // namespace clsnap
 #endif
 namespace clsnap {

@@ -136,6 +136,9 @@ struct cl_sim {
   // (cl_set_program_kernels), and whether the latest launch ran them
   int32_t prog_mode = CL_PROGRAM_AUTO;
   int32_t last_prog = 0;
+  // the program kernels of the latest launch, or of the latest cl_lanes_program_compile_check if
+  // that came later, were compiled with the program type's COVER (cl_lanes.h Guard)
+  int32_t last_cover = 0;
 
   // limits
   int32_t cap_log2 = 3;
@@ -715,9 +718,10 @@ struct cl_sim {
                       (prog_mode == CL_PROGRAM_ON ||
                        (kProgramKernelsByDefault && (int64_t)n_inst >= kLanesAutoMinInstances &&
                         std::max(max_out, max_in) >= 2));
-    int32_t prog_used = 0;
+    int32_t prog_used = 0, cover_used = 0;
     const ExecLaunch el{stream, pr.start, pr.stop, stream2, ev_fork, ev_join, (!pipe || s_dirty) ? 1 : 0,
-                        pipe ? 0 : 1, pr.stop2, &pr.stop2_used, pr.start2, prog ? dops.data() : nullptr, &prog_used};
+                        pipe ? 0 : 1, pr.stop2, &pr.stop2_used, pr.start2, prog ? dops.data() : nullptr, &prog_used,
+                        draws_needed(), &cover_used};
     // a replay through the slot map with no state image (so the next launch starts from the
     // initial state again) writes its records block-major by slot: a wave's stores of one
     // node's records are contiguous (both kernels; C3 2^20 1.636 -> 1.567 ms per replay on the
@@ -742,6 +746,7 @@ struct cl_sim {
     }
     last_engine = used_lanes ? CL_ENGINE_LANES : CL_ENGINE_NODES;
     last_prog = used_lanes ? prog_used : 0;
+    last_cover = used_lanes ? cover_used : 0;
     if (begin == 0) plan.wrote_records(blocked);
     if (pipe) {
       s2_live = true;
@@ -1426,7 +1431,11 @@ static int lanes_check(cl_sim* sim, double* compile_ms, int32_t* specialized, ch
     sim->dops_for = (size_t)-1;
     *specialized = lanes_prog_fit(p, sim->dops.data(), (int)sim->dops.size()) ? 1 : 0;
     if (compile_ms) *compile_ms = 0;
-    rc = *specialized ? lanes_compile_only(p, compile_ms, &l, sim->dops.data(), (int)sim->dops.size()) : 0;
+    // (the rows the next launch would run on: whether they cover the program's draws)
+    p.draws = sim->delays.draws_for(sim->draws_needed());
+    rc = *specialized ? lanes_compile_only(p, compile_ms, &l, sim->dops.data(), (int)sim->dops.size(),
+                                           sim->draws_needed(), &sim->last_cover)
+                      : 0;
   } else {
     rc = lanes_compile_only(p, compile_ms, &l);
   }
@@ -1436,6 +1445,13 @@ static int lanes_check(cl_sim* sim, double* compile_ms, int32_t* specialized, ch
     log[n] = 0;
   }
   return rc ? set_err(CL_E_DEVICE, "instance-per-lane kernel compilation failed") : CL_OK;
+}
+
+int cl_exec_program_cover(cl_sim* sim, int32_t* on) {
+  SIM_CALL(sim);
+  if (!on) return set_err(CL_E_INVALID, "null output");
+  *on = sim->last_cover;
+  return CL_OK;
 }
 
 int cl_lanes_compile_check(cl_sim* sim, double* compile_ms, char* log, int64_t log_cap) {

@@ -302,6 +302,7 @@ struct Pairs {
 // cl_jit.cpp generates are described with send_c / snap_c below).
 struct NoProg {
   static constexpr bool SPEC = false;
+  static constexpr bool COVER = false;
 };
 
 // The in-links that can carry a token.  A program-specialized kernel starts from the initial
@@ -310,7 +311,14 @@ struct NoProg {
 // a == src(v, j) and b == oix(v, j).  A send counts wherever it stands (the arm after the last
 // tick op included) and whether or not it succeeds at run time; one with an unknown destination
 // (b < 0) names no channel.  Every other in-link delivers markers only: phase B has no token
-// path there, and its recording cursor is the constant 0.  NoProg: true everywhere.
+// path there, and its recording cursor is the constant 0.  Nor does it store an end cursor when
+// its marker closes the channel: the store's value would be the constant 0, and the record holds
+// that 0 already.  The kernel starts from the initial state (program(): P::SPEC || p.fresh), so
+// a node's pending nibble for a snapshot id is non-zero only after this lane ran create_record
+// for (node, sid) earlier in this same launch, and create_record writes the whole record in one
+// vector store: c = 0 on a token-free in-link, c | c << 16 = 0 where the marker arrived on it.
+// That holds on planes nobody zeroed, and only here: a kernel that can resume from a state image
+// may close a record that an earlier launch created.  NoProg: true everywhere.
 template <class T, class P>
 struct TokIn {
   struct Tab {
@@ -442,6 +450,12 @@ __device__ __forceinline__ void push(const Ctx& x, uint32_t& hw, uint32_t sh, ui
 // ring's slots (a power of two: some count >= CAP), masked to the node's own half of its pair's
 // registers.  On the deep-ring kernel the bound is the
 // layout's ring, so the probe's flag store stays in push().
+// A program type with COVER set was compiled for a launch whose rows hold at least the program's
+// own bound on draws (the host's draws_needed: one per send, one per snapshot id and channel), so
+// no broadcast of an instance can run past its row and the first question is not asked at all.
+// That concerns tick()'s first pass and snap_c only: push() on the slow path and in the further
+// passes keeps its own row test, and start_snapshot, which only the generic kernels run, asks
+// both questions as before.
 template <class T>
 struct Guard {
   static constexpr uint32_t LIM = 1u << (T::PCAPL < T::CAPL ? T::PCAPL : T::CAPL);
@@ -647,14 +661,17 @@ __device__ __forceinline__ bool tick(const Ctx& x, State<T>& s, bool act) {
       }
       const uint32_t rb = plane_off(x, sid) + x.lrec;
       if (first) create_record<T, P>(x, snod, s, v, j, rb);
+      // the channel's end cursor.  No store where no token travels: the 0 it would write is in the
+      // record since this launch created it (TokIn)
+      if (tl) {
 #ifndef CLSNAP_ABL_NOSTORE
-      if (later)  // the channel's end cursor (0 where no token travels; stored all the same, the
-                  // plane holds no zeros of its own)
+        if (later)
 #else
-      if (later && rb == 0xffffffffu)
+        if (later && rb == 0xffffffffu)
 #endif
-        st_at(reinterpret_cast<uint16_t*>(snod), rb + node_off<T>(x, (uint32_t)v) + (uint32_t)(4 * (1 + j) + 2),
-              (uint16_t)(tl ? cur_get(s, v, j) : 0u));
+          st_at(reinterpret_cast<uint16_t*>(snod), rb + node_off<T>(x, (uint32_t)v) + (uint32_t)(4 * (1 + j) + 2),
+                (uint16_t)cur_get(s, v, j));
+      }
     }
     sched_fence();
   }
@@ -663,10 +680,23 @@ __device__ __forceinline__ bool tick(const Ctx& x, State<T>& s, bool act) {
 #pragma unroll
     for (int w = 0; w < T::SW; ++w) {
       uint32_t all = 0x88888888u;
+      if constexpr (P::SPEC) {
+        // reduced over the nodes first: every node's nibble is 1 exactly when the nibble of the
+        // words' OR and the nibble of their AND both are -- one zero-nibble test per word
+        uint32_t por = 0u, pand = 0xffffffffu;
 #pragma unroll
-      for (int v = 0; v < N; ++v) {
-        const uint32_t y = s.pd[v][w] ^ 0x11111111u;  // nibble == 1 -> 0
+        for (int v = 0; v < N; ++v) {
+          por |= s.pd[v][w];
+          pand &= s.pd[v][w];
+        }
+        const uint32_t y = (por ^ 0x11111111u) | (pand ^ 0x11111111u);
         all &= ~(((y & 0x77777777u) + 0x77777777u) | y);
+      } else {
+#pragma unroll
+        for (int v = 0; v < N; ++v) {
+          const uint32_t y = s.pd[v][w] ^ 0x11111111u;  // nibble == 1 -> 0
+          all &= ~(((y & 0x77777777u) + 0x77777777u) | y);
+        }
       }
       uint32_t fresh = all & 0x88888888u & ~s.done[w];
       if (fresh) {
@@ -746,7 +776,8 @@ __device__ __forceinline__ bool tick(const Ctx& x, State<T>& s, bool act) {
 #pragma unroll
             for (int k = 0; k < D; ++k)
               if (k < T::od(v)) any |= s.hw[Pr::pr(v)][k];
-            hard = on && (k0 + T::od(v) > x.draws || (any & (Guard<T>::FULL << Pr::sh(v))) != 0);
+            const bool past = !P::COVER && k0 + T::od(v) > x.draws;
+            hard = on && (past || (any & (Guard<T>::FULL << Pr::sh(v))) != 0);
           }
           if (!FAST || __builtin_expect(__ballot(hard) != 0, 0)) {
             int32_t nf = 0;
@@ -953,6 +984,7 @@ __device__ __forceinline__ void start_snapshot(const Ctx& x, State<T>& s, const 
 // per segment the host ops (sends and snapshot starts, OP_SENDS groups as their sends in order)
 // that precede its tick op, and the tick op's fields (all constexpr):
 //   SPEC              true (NoProg: false, the generic kernels that read `ops`)
+//   COVER             the launch's delay rows hold every draw the program can make (Guard)
 //   NSEG, NARM        tick segments; arms of host ops: NSEG, + 1 for host ops after the last tick
 //   h0(g)             first host op of arm g (h0(NARM): their number)
 //   hk(h), ha(h), hb(h), hc(h)   host op h: OP_SEND or OP_SNAP and its fields a, b, c
@@ -1006,7 +1038,8 @@ __device__ __forceinline__ void snap_c(const Ctx& x, State<T>& s) {
     uint32_t any = 0;
 #pragma unroll
     for (int k = 0; k < od; ++k) any |= s.hw[Pairs<T>::pr(A)][k];
-    const bool hard = on && (s.draw + od > x.draws || (any & (Guard<T>::FULL << Pairs<T>::sh(A))) != 0);
+    const bool past = !P::COVER && s.draw + od > x.draws;
+    const bool hard = on && (past || (any & (Guard<T>::FULL << Pairs<T>::sh(A))) != 0);
     if (__builtin_expect(__ballot(hard) != 0, 0)) {
 #pragma unroll
       for (int k = 0; k < od; ++k)

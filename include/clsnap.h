@@ -250,6 +250,11 @@ int cl_lanes_compile_check(cl_sim* sim, double* compile_ms, char* log, int64_t l
  * as a replay would run it): *specialized = 1 and they are compiled, or 0 and nothing is -- the
  * program is over the cap and replays on the generic kernels. */
 int cl_lanes_program_compile_check(cl_sim* sim, double* compile_ms, int32_t* specialized, char* log, int64_t log_cap);
+/* *on = 1 when the program-specialized kernels of the latest launch -- or of the latest
+ * cl_lanes_program_compile_check, if that came later -- were compiled for delay rows that hold
+ * every draw the program can make (cl_delay_draws_needed): their broadcast guard has no row-end
+ * test.  0 with shorter rows (a caller's schedule), and when no such kernels were used. */
+int cl_exec_program_cover(cl_sim* sim, int32_t* on);
 
 /* Test/benchmark aid (no reference counterpart): overwrite every result plane the exec
  * kernel writes -- node snapshot records, completion ticks, per-instance result rows,
